@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s of the Fresnel + refraction step on synthetic grids (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4096] [--positions 64] [--no-cpu-baseline] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4096] [--dump-outputs DIR] [--full [--positions 64] ...]
 
 One STEP = one pass of the hot path over one membrane position of the 4096x4096 workload (BASELINE.json configs[2],
 SURVEY.md section 8d): the membrane exit wave (2-material transmission fused into the load) is Fresnel-propagated to the
@@ -14,8 +14,13 @@ N GPUs: one process per GPU, each rank runs its own membrane position (seed 1000
 collective.  `python bench.py --gpus N` with no RANK in the environment starts its own N ranks (a child
 `python -m torch.distributed.run`, decided before anything touches the GPU); under torchrun it is one of the ranks.
 
-Config 4 of BASELINE.json (the 64-position membrane batch) is measured in the SAME run, after the timed steps, and reported
-in the `positions_batch` object of the JSON line: the whole position loop of main.py:63-110 -- membrane synthesis with
+A plain run does only what `value` needs: set-up, the clock spin-up, W warm-up steps, the K timed steps, the outputs of the
+last timed step with --dump-outputs DIR, the result line.  Everything else on the line is measured with --full only:
+`value_cold`, `steady`, the per-kernel event pass and `roofline`, `shader_clock_mhz`, `other_far_ray_mode`, the positions
+batch, the `configs` entries, the CPU baseline and the parity of the step's images against it.
+
+With --full, config 4 of BASELINE.json (the 64-position membrane batch) is measured in the SAME run, after the timed steps, and
+reported in the `positions_batch` object of the JSON line: the whole position loop of main.py:63-110 -- membrane synthesis with
 seed(pointNum), the image-formation chain, detection, shot noise -- for 64 positions strided over the ranks, the RCCL
 gather of all 64 x 2 detector stacks onto rank 0 INSIDE its timed region; rank 0 then re-computes positions it did not
 own and checks the gathered images bit for bit.
@@ -46,6 +51,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything else on the line as well (value_cold, steady, per-kernel times and roofline, shader "
+                         "clock, other far-ray mode, positions batch, configs, CPU baseline and parity); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the images of the last one as DIR/fresnel.npy and DIR/refraction.npy "
+                         "(float32, one row per distance; larger images at the fixed pixels of DIR/sample_index.npy)")
     ap.add_argument("--engine", default="auto", choices=["auto", "rocfft", "lds"])
     ap.add_argument("--halo", type=int, default=0, choices=[0, 4, 6, 8, 12, 16],
                     help="refraction gather halo of the headline step (a speed knob; 0 = 6 with the order-independent replay, 4 with "
@@ -247,7 +258,7 @@ def main():
     # `value_cold`: the contract's W warm-up + K timed steps FIRST, on a process whose clocks have not
     # ramped -- what rounds 1-2 reported as `value`, kept so that rounds stay comparable.  (With --spinup-ms 0 it is `value`.)
     cold = None
-    if a.spinup_ms > 0:
+    if a.spinup_ms > 0 and a.full:
         for _ in range(a.warmup):
             step()
         barrier()
@@ -256,6 +267,10 @@ def main():
             step()
         barrier()
         cold = time.perf_counter() - tc0
+    elif a.spinup_ms > 0:
+        # set-up in place of the cold pass: the first step loads the kernels' code, so that the spin-up below is all load
+        step()
+        barrier()
     spin = {"ms": 0.0, "steps": 0}
     if a.spinup_ms > 0:
         ts = time.perf_counter()
@@ -284,10 +299,12 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     ops.check_status(dev, "bench")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, fres, refr)
     # per-kernel durations for the roofline: the same K steps once more with the library recording a HIP event pair
     # around each of its launches on the launch stream (the event records cost ~4 % of a step, so they stay out of `value`)
     kern = {}
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         import ctypes
         lib.psx_profile_enable(1)
         for _ in range(a.steps):
@@ -303,24 +320,25 @@ def main():
     # of a process take 1.36-1.62 ms, steps 30+ 1.25 ms), so a short timed region right after W = 5 warm-up steps reads a few
     # per cent high.  `value` stays what the contract says -- W warm-up steps, then exactly K timed steps -- and the same K
     # un-instrumented steps are timed once more here, after the event pass, as `steady`.
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        run_step()
-    barrier()
-    dt_steady = time.perf_counter() - t1
-    # what this box sustains: the shader clock right behind the steady steps (psx_clock_probe: a 30 us spin on every CU).  The
-    # boxes of the pool differ by 12 % in step time with the same library; the probe says how much of a
-    # run's time is the box's clock.  Outside every timed region.
-    try:
-        shader_mhz = round(ops.clock_probe(), 1)
-    except Exception as exc:                               # diagnostics only: never fails the run
-        shader_mhz = None
-        sys.stderr.write("bench: clock probe failed: %s\n" % exc)
+    dt_steady = shader_mhz = None
+    if a.full:
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(a.steps):
+            run_step()
+        barrier()
+        dt_steady = time.perf_counter() - t1
+        # what this box sustains: the shader clock right behind the steady steps (psx_clock_probe: a 30 us spin on every CU).
+        # The boxes of the pool differ by 12 % in step time with the same library; the probe says how
+        # much of a run's time is the box's clock.  Outside every timed region.
+        try:
+            shader_mhz = round(ops.clock_probe(), 1)
+        except Exception as exc:                               # diagnostics only: never fails the run
+            sys.stderr.write("bench: clock probe failed: %s\n" % exc)
     # ... and K steps in the OTHER far-ray mode (order-independent fixed-point replay <-> float atomics), so that the cost of
     # reproducible sums is on the line whichever mode `value` was measured in
     other_mode = {"far_rays": "float atomics" if ops.get_deterministic() else "order-independent fixed-point replay"}
-    if not a.graph:
+    if a.full and not a.graph:
         ops.set_deterministic(not ops.get_deterministic())
         for _ in range(a.warmup):
             step()
@@ -343,9 +361,11 @@ def main():
     if cold is None:
         cold = dt
     if world > 1:
-        tt = torch.tensor([dt, dt_steady, cold], dtype=torch.float64, device=cpu_dev)
+        tt = torch.tensor([dt, dt_steady or 0.0, cold], dtype=torch.float64, device=cpu_dev)
         td.all_reduce(tt, op=td.ReduceOp.MAX)
-        dt, dt_steady, cold = float(tt[0].item()), float(tt[1].item()), float(tt[2].item())
+        dt, cold = float(tt[0].item()), float(tt[2].item())
+        if dt_steady is not None:
+            dt_steady = float(tt[1].item())
         one = torch.ones(1, dtype=torch.int64, device=cpu_dev)
         td.all_reduce(one)                                  # every rank really took part in the collective
         ranks_seen = int(one.item())
@@ -365,30 +385,32 @@ def main():
                       "streams": 1 if side is None else 2,
                       "parallelism": "positions sharded, 1 per GPU" if world > 1 else "single GPU"},
            "ranks_seen": ranks_seen,
+           "debug_switches": ops.debug_switches_active(),
+           "env_switches": {k: v for k, v in sorted(os.environ.items()) if k.startswith("PSX_")},
+           "far_rays": "order-independent fixed-point replay" if ops.get_deterministic() else "float atomics",
+           "spinup": {"ms": spin["ms"], "steps": spin["steps"],
+                      "note": "the same step run untimed BEFORE the W warm-up steps until the clocks have ramped (--spinup-ms)"}}
+    if a.full:
+        out.update({
            "value_cold": round(units * N * N * world / (cold / a.steps) / 1e6, 1),
            "cold": {"ms_per_step": round(cold / a.steps * 1e3, 4),
                     "note": "the same W warm-up + K timed steps run FIRST, before the spin-up (clocks not ramped): the protocol of "
                             "rounds 1-2, for comparison across rounds"},
-           "debug_switches": ops.debug_switches_active(),
-           "env_switches": {k: v for k, v in sorted(os.environ.items()) if k.startswith("PSX_")},
-           "far_rays": "order-independent fixed-point replay" if ops.get_deterministic() else "float atomics",
            "other_far_ray_mode": other_mode,
-           "spinup": {"ms": spin["ms"], "steps": spin["steps"],
-                      "note": "the same step run untimed BEFORE the W warm-up steps until the clocks have ramped (--spinup-ms)"},
            "shader_clock_mhz": shader_mhz,
            "shader_clock_note": "measured right behind the `steady` steps with the shader-clock and the 100 MHz counters (psx_clock_probe); "
                                 "the step time of one library scales with it from box to box",
            "steady": {"ms_per_step": round(dt_steady / a.steps * 1e3, 4),
                       "value": round(units * N * N * world / (dt_steady / a.steps) / 1e6, 1),
                       "note": "the same K un-instrumented steps timed a second time, after the per-kernel event pass: the device "
-                              "needs ~40 ms of load to reach its steady step time (tools/step_ramp.py)"}}
+                              "needs ~40 ms of load to reach its steady step time (tools/step_ramp.py)"}})
 
     # the library's own default (float atomics, measured unit) for what follows: the position batches set the mode through the
     # Experiment class, the `configs` entries say which mode they ran in
     ops.set_deterministic(False)
     ops.set_deterministic_scale(0.0)
     # ---- BASELINE.json config 4: the membrane-position batch, its own timed region (all ranks take part)
-    if a.positions > 0:
+    if a.full and a.positions > 0:
         import contextlib
         pn = a.positions_size or min(N, 4096)
         with contextlib.redirect_stdout(sys.stderr):     # the mirrors print like the reference; stdout carries the JSON line only
@@ -419,7 +441,7 @@ def main():
                     out["positions_batch"][key] = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
     # ---- BASELINE.json configs 1, 2 and 5 on the same line (rank 0 of a one-rank run only: they are single-GPU configurations)
-    if rank == 0 and world == 1 and not a.no_configs and N == 4096:
+    if a.full and rank == 0 and world == 1 and not a.no_configs and N == 4096:
         import contextlib
         with contextlib.redirect_stdout(sys.stderr):
             try:
@@ -428,7 +450,7 @@ def main():
                 import traceback
                 traceback.print_exc()
                 out["configs"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-    if rank == 0:
+    if a.full and rank == 0:
         P = N + 30
         nmat = 2
         # TWO price lists.  `frac` uses SURVEY.md section 8(d)'s price for what this step IS -- a batch
@@ -541,8 +563,9 @@ def main():
                                                 "engine's instructions are packed fp32 (v_pk_*), which hold the pipe twice as "
                                                 "long, so the pipe is busier than this fraction says",
                                         "profile": prof.get("_file") if prof else None}
+    if rank == 0:
         rc = 0
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline(N, geo, delta, beta, E, M, pix, I0, fres, refr)
             if not out["parity"]["ok"]:
                 rc = 3
@@ -565,6 +588,31 @@ def main():
         td.barrier()
         td.destroy_process_group()
     sys.exit(rc)
+
+
+DUMP_PIXELS = 1 << 20        # pixels kept per image by --dump-outputs: 8 images x 4 MiB + an 8 MiB index stay under 64 MB
+DUMP_SEED = 20261016
+
+
+def dump_index(n):
+    """Flat pixel indices --dump-outputs keeps of an n-pixel image: all of them up to DUMP_PIXELS, else a fixed seeded sample
+    (sorted, no repeats), the same on every run and every build."""
+    if n <= DUMP_PIXELS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, DUMP_PIXELS, replace=False))
+
+
+def dump_outputs(d, fres, refr):
+    """--dump-outputs DIR: what the timed step hands its caller -- the 4 Fresnel intensities and the 4 refraction intensities --
+    as DIR/fresnel.npy and DIR/refraction.npy (float32, one row per distance, the pixels of DIR/sample_index.npy, flat
+    indices stored as float64)."""
+    import torch
+    idx = dump_index(fres[0].numel())
+    ix = torch.from_numpy(idx).to(fres[0].device)
+    os.makedirs(d, exist_ok=True)
+    for name, imgs in (("fresnel", fres), ("refraction", refr)):
+        np.save(os.path.join(d, name + ".npy"), torch.stack([t.reshape(-1)[ix] for t in imgs]).cpu().numpy())
+    np.save(os.path.join(d, "sample_index.npy"), idx.astype(np.float64))
 
 
 def positions_batch(a, sim, N, rank, world, dev, reproducible=False):

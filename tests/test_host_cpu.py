@@ -531,6 +531,20 @@ def test_bench_starts_its_own_ranks_and_rejects_a_world_mismatch(monkeypatch, ca
     assert "WORLD_SIZE=2" in str(e.value.code)
 
 
+def test_bench_dump_outputs_sample_is_fixed_and_bounded():
+    """`bench.py --dump-outputs`: the pixels kept of each image are the same on every call (two builds are compared output for
+    output), distinct and in range, every pixel of a small image, and the 8 float32 images plus the float64 index of the
+    4096^2 and 16384^2 steps stay within 64 MB."""
+    import bench
+    for n in (4096 * 4096, 16384 * 16384):
+        idx = bench.dump_index(n)
+        assert np.array_equal(idx, bench.dump_index(n))
+        assert len(idx) == bench.DUMP_PIXELS and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+        assert 8 * len(idx) * 4 + len(idx) * 8 <= 64e6
+        assert np.array_equal(idx.astype(np.float64).astype(np.int64), idx)       # exact as stored
+    assert np.array_equal(bench.dump_index(512 * 512), np.arange(512 * 512))
+
+
 def test_energy_bins_of_the_batched_chains_follow_the_reference_loop():
     """Experiment._bins_of_spectrum (the batched energy chains take a detector bin at a time) against the bin bookkeeping of
     the reference's energy loop (Experiment.py:296-301, 378-401): a bin closes at the first energy above its threshold minus

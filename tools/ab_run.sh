@@ -8,7 +8,7 @@ cp paresis_amd/libparesis_hip.so $OUT/.lib_saved.so
 for rep in 1 2; do
   for tag in "$@"; do
     cp tools/ab/libparesis_hip_$tag.so paresis_amd/libparesis_hip.so
-    timeout -k 10 200 python bench.py --no-configs --no-cpu-baseline --positions 0 --steps 30 $AB_FLAGS > $OUT/${tag}_$rep.out 2> $OUT/${tag}_$rep.err || echo "$tag rc $?"
+    timeout -k 10 200 python bench.py --full --no-configs --no-cpu-baseline --positions 0 --steps 30 $AB_FLAGS > $OUT/${tag}_$rep.out 2> $OUT/${tag}_$rep.err || echo "$tag rc $?"
     python - <<PY
 import json
 d = json.loads(open("$OUT/${tag}_$rep.out").read().strip().splitlines()[-1])

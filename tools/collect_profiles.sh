@@ -16,7 +16,7 @@ for arg in "$@"; do
         --gpus|--gpus=*) echo "collect_profiles.sh: profile ONE rank (bench.py --gpus N would start its ranks from a process the profiler's library has already initialised the GPU in)" >&2; exit 2;;
     esac
 done
-CMD="python3 $ROOT/bench.py --no-cpu-baseline --positions 0 --no-configs $*"      # the bench run (timed steps + the per-kernel event pass), minus the CPU leg and the positions batch
+CMD="python3 $ROOT/bench.py --full --no-cpu-baseline --positions 0 --no-configs $*"      # the bench run (timed steps + the per-kernel event pass), minus the CPU leg and the positions batch
 case " $* " in
     *" --only-configs "*) CMD="python3 $ROOT/bench.py $*";;     # a `configs` entry alone, as the driver's line runs it (GPU membrane, halo 8, detector)
 esac

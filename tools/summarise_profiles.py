@@ -38,7 +38,7 @@ for k in sorted(set(fetch) | set(write) | set(sq)):
 cmd = ("`python3 bench.py --only-configs --configs 16384 --no-config-parity` (config 5 as the driver's line runs it: GPU-synthesised "
        "membrane, halo picked by ops.tune_refract_halo -- its three candidates appear as three k_refract instances --, detector "
        "inside the step)") if sfx == "_cfg5" else (
-       "`python3 bench.py --no-cpu-baseline --positions 0%s` (warm-up + timed steps + the per-kernel event pass)" % (" (" + sfx.strip("_") + "^2 grid)" if sfx else ""))
+       "`python3 bench.py --full --no-cpu-baseline --positions 0%s` (warm-up + timed steps + the per-kernel event pass)" % (" (" + sfx.strip("_") + "^2 grid)" if sfx else ""))
 def csrc_sha1(root="."):
     """One hash over the kernel sources (paresis_amd/csrc/*.hip, *.hpp, Makefile, sorted by name): stamped into the summary so that
     bench.py can say whether the profile it quotes was collected on the sources it runs (roofline.traffic_sources_match)."""

@@ -555,15 +555,13 @@ __global__ __launch_bounds__(T) void k_fresnel_lines(LineArgs a) {
 // output multiplies.  Round E leaves ye in a line buffer private to the workgroup (it is read back 20 us later by the same
 // CU: L2 / MALL traffic), round O combines and stores the N wanted samples, whose index wraps once along the 24 outputs of a
 // butterfly.  Per line: 2 rounds and 2 x 18432 loads instead of 4 and 4 x 16398; no partial sums in the output image.
-template <bool CONTIG, bool PAIR, bool DIF = false>
+template <bool CONTIG, bool DIF>
 __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
-    static_assert(!DIF || PAIR, "DIF rounds are PAIR rounds");
     constexpr int R3 = 16;
-    using GE = LineGeom<R3, PAIR>;
+    using GE = LineGeom<R3, true>;
     constexpr int M = GE::M, LINES = GE::LINES, S1 = GE::S1, MP = GE::MP;
-    static_assert(LINES == 2, "the partitioned engine works on the two LDS lines of the M = 9216 transform");
-    constexpr int LPG = PAIR ? 1 : LINES;               // image lines per round
-    constexpr int SLAB = GE::SLAB, WSLABS = GE::WSLABS, TWB_LD = GE::TWB_LD;
+    static_assert(LINES == 2, "the partitioned engine couples the two LDS lines of the M = 9216 transform");
+    constexpr int SLAB = GE::SLAB, TWB_LD = GE::TWB_LD;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     const int tid = threadIdx.x;
     const int N = a.N, mg = a.margin;
@@ -590,7 +588,7 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
     // a.dist_inner (pass 1: every distance reads the SAME source): the chunks are cut over (block, line group) pairs and a
     // workgroup takes the n_dist distances of its pair in consecutive units -- the DIF loaders then keep most of the line in
     // registers for all of them (below) instead of fetching it 2 n_dist times.
-    const int ngroups = (a.nlines + LPG - 1) / LPG;
+    const int ngroups = a.nlines;                                             // one image line per round
     const int ndin = a.dist_inner ? a.n_dist : 1;                             // distances inside a chunk item
     const int nwork = ngroups * a.NB * (a.dist_inner ? 1 : a.n_dist);
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
@@ -673,7 +671,7 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
         auto fetch_half = [&](int j, int h) __attribute__((always_inline)) {
             int d, g;
             item(j, d, g);
-            const int l = PAIR ? g : g * LINES + line;
+            const int l = g;
             const int lc = min(l, a.nlines - 1);          // addresses stay inside the image for the idle lines of the last group
             // PART sources are the blocked intermediate or contiguous lines (in_si == 1): 32-bit element offsets from the line's base
             const float2 *srcl = a.src[d] + (a.in_blocked ? ((int64_t)(lc / IB) * N) * IB + lc % IB : (int64_t)lc * a.in_sl);
@@ -681,14 +679,14 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
             // DIF: the window is the first 2M points of the extension, every position holds a sample
             const int a0 = DIF ? 0 : pb * a.B + P - (ps + 1) * a.Lh;
             const unsigned tlim = l < a.nlines ? (unsigned)(DIF ? 2 * M : Lw) : 0u;
-            int tb = PAIR ? 2 * i0 + line : i0;          // window position of this thread's first sample; opaque, so that the
+            int tb = 2 * i0 + line;                      // window position of this thread's first sample; opaque, so that the
             asm volatile("" : "+v"(tb));                 // 72 positions are formed here and not kept across the rounds
             vm0 = 0u;
             vm1 = 0u;
 #pragma unroll
             for (int k = 0; k < NH; ++k) {
-                // PAIR: LDS line `line` holds the samples of parity `line`, LDS index = window position / 2
-                const int t = tb + (PAIR ? 2 : 1) * STEP * (k + NH * h);
+                // LDS line `line` holds the samples of parity `line`, LDS index = window position / 2
+                const int t = tb + 2 * STEP * (k + NH * h);
                 const int te = a0 + t;
                 const bool ok = (unsigned)t < tlim && (unsigned)te < (unsigned)Etot;
                 int jp = te - (P - 1) + mg;                  // index into the padded line, one period either side
@@ -857,32 +855,27 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
 
     // =================================== engine waves =========================================================================
     // stage A and B thread mapping (one butterfly per thread per stage)
-    // PAIR: adjacent lanes take butterfly n of the even line and of the odd line -- their outputs are adjacent samples, so a
+    // adjacent lanes take butterfly n of the even line and of the odd line -- their outputs are adjacent samples, so a
     // wave's stores (and its partial-sum loads) cover whole cache lines
-    const int lineA = PAIR ? (tid & 1) : tid / S1, nA = PAIR ? (tid >> 1) : tid % S1;
-    // stage B: thread -> (line, block q1 of S1 points, element n < R3).  PAIR: a wave takes blocks {2w, 2w+1} of BOTH lines
+    const int lineA = tid & 1, nA = tid >> 1;
+    // stage B: thread -> (line, block q1 of S1 points, element n < R3).  A wave takes blocks {2w, 2w+1} of BOTH lines
     // (lanes 0-31 line 0, 32-63 line 1), so that the points it owns between the barriers are the same range of the two lines
     // the middle stage couples
-    // (the PAIR values are re-derived inside the round loop from an opaque copy of the thread index: hoisted out of it
+    // (these values are re-derived inside the round loop from an opaque copy of the thread index: hoisted out of it
     // they would stay live through inverse stage A, which has no register to spare)
-    const int remB = tid % S1, q1B = remB / R3, nB = PAIR ? (tid & 31) % R3 : remB % R3, p0B = q1B * S1 + nB;
+    const int remB = tid % S1, q1B = remB / R3, nB = (tid & 31) % R3, p0B = q1B * S1 + nB;
     v2f *baseA = reinterpret_cast<v2f *>(lds) + lineA * MP;
-    auto stageB_at = [&](v2f *&bB, int &pB, bool paired) __attribute__((always_inline)) {
+    auto stageB_at = [&](v2f *&bB, int &pB) __attribute__((always_inline)) {
+        // (overwritten below, and yet not dead to the compiler: without these two stores and the values they capture the
+        // DIF instances come out with a different register allocation)
         bB = baseA;
         pB = p0B;
-        if (paired) {
-            int to = ftid();
-            // a half-wave (32 butterflies = 768 points) takes the wave's range of line 0 (lanes 0-31) or of line 1 (lanes 32-63)
-            const int gb = (to >> 6) * (32 / R3) + (to & 31) / R3;          // block inside the half: 24 blocks per line
-            bB = reinterpret_cast<v2f *>(lds) + (gb / RAD + ((to & 63) >> 5)) * MP;
-            pB = (gb % RAD) * S1 + (to & 31) % R3;
-        }
+        int to = ftid();
+        // a half-wave (32 butterflies = 768 points) takes the wave's range of line 0 (lanes 0-31) or of line 1 (lanes 32-63)
+        const int gb = (to >> 6) * (32 / R3) + (to & 31) / R3;          // block inside the half: 24 blocks per line
+        bB = reinterpret_cast<v2f *>(lds) + (gb / RAD + ((to & 63) >> 5)) * MP;
+        pB = (gb % RAD) * S1 + (to & 31) % R3;
     };
-    // middle stage: slab of this lane inside the wave's own 96 (round 2: 32 lanes).  Within each half-wave the first 16
-    // lanes take the even slabs and the last 16 the odd ones: the 16 lanes of a ds_write_b64 group then carry 16
-    // different pad offsets (one pad slot per TWO slabs) and hit 16 different bank pairs instead of 8.
-    const int slabw = ((tid & 63) & 32) + ((tid & 31) < 16 ? 2 * (tid & 31) : 2 * ((tid & 31) - 16) + 1);
-    const int slab0 = (tid >> 6) * WSLABS + slabw;
     const v2f *rowA1 = tw.tw1 + (nA / R3) * TWB_LD, *rowA0 = tw.tw0 + (nA % R3) * TWB_LD;
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 32 + 0] = wall_clock64();
     lds_barrier();                                       // (0) first group is in LDS
@@ -890,7 +883,7 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
     for (int j = 0; j < nj; ++j) {
         int d, g;
         item(j, d, g);
-        const int l0 = g * LPG;
+        const int l0 = g;
         PSX_STAMP(2);
 
         // ---- 2. forward stage A: radix 24 over stride S1, twiddle w_M^{n q}
@@ -950,25 +943,17 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
         // The kernel spectrum (the engine's only global loads) travels one step ahead of its use: the first slab's 128
         // bytes are requested here, before barrier (1); the second slab's right after the first one's multiply.
         float4 hh[SLAB / 2];
-        // PAIR: lane u < 48 of wave w couples slab 48 w + u of line 0 with the same slab of line 1; its table is the interleaved
+        // lane u < 48 of wave w couples slab 48 w + u of line 0 with the same slab of line 1; its table is the interleaved
         // pair (H[k], H[k + M]) per point: 4 points = 4 float4 per chunk; the first chunk travels here, the others under the
         // arithmetic of the chunk before (a slab pair already holds 64 registers of data)
-        const int tp = PAIR ? ftid() : tid;
-        const int pslab = 48 * (tp >> 6) + (tp & 63);                         // slab index inside a line (PAIR)
+        const int tp = ftid();
+        const int pslab = 48 * (tp >> 6) + (tp & 63);                         // slab index inside a line
         const bool pact = (tp & 63) < 48;
         const float4 *hp4 = reinterpret_cast<const float4 *>(a.H[d] + (size_t)ps * 2 * M) + (size_t)(pact ? pslab : 0) * SLAB;
-        v2f w0p = (v2f){1.f, 0.f};
-        if constexpr (PAIR) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) hh[q] = hp4[q];
-            const float2 w = a.w2[pact ? pslab : 0];
-            w0p = (v2f){w.x, w.y};
-        } else {
-            const int sl = slab0;
-            const float4 *h4 = reinterpret_cast<const float4 *>(a.H[d] + ps * M + (unsigned)((sl % (M / SLAB)) * SLAB));
-#pragma unroll
-            for (int q = 0; q < SLAB / 2; ++q) hh[q] = h4[q];
-        }
+        for (int q = 0; q < 4; ++q) hh[q] = hp4[q];
+        const float2 w0 = a.w2[pact ? pslab : 0];
+        const v2f w0p = (v2f){w0.x, w0.y};
         PSX_STAMP(3);
         lds_barrier();                               // (1)
         PSX_STAMP(4);
@@ -976,7 +961,7 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
         {
             v2f *bB;
             int pB;
-            stageB_at(bB, pB, PAIR);
+            stageB_at(bB, pB);
             fwd_stage_B<GE>(bB, pB, tw.twl + nB * TWB_LD);
         }
         PSX_STAMP(5);
@@ -990,45 +975,41 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
 
         // ---- 4+5. middle stage, slab by slab: forward radix R3 on contiguous chunks, x FFT_M(h_d), inverse radix R3,
         // back to LDS.  Each thread rewrites exactly the slabs it read.
-        if constexpr (PAIR) {
-            if (pact) {
-                v2f *b0 = reinterpret_cast<v2f *>(lds) + phys(pslab * SLAB), *b1 = b0 + MP;
-                v2f f0[SLAB], f1[SLAB];
+        if (pact) {
+            v2f *b0 = reinterpret_cast<v2f *>(lds) + phys(pslab * SLAB), *b1 = b0 + MP;
+            v2f f0[SLAB], f1[SLAB];
 #pragma unroll
-                for (int q = 0; q < SLAB; ++q) f0[q] = lds_read(b0 + q);
+            for (int q = 0; q < SLAB; ++q) f0[q] = lds_read(b0 + q);
 #pragma unroll
-                for (int q = 0; q < SLAB; ++q) f1[q] = lds_read(b1 + q);
-                DftPk<SLAB, false>::run(f0);
-                DftPk<SLAB, false>::run(f1);
-                // radix-2 of the 2M-point transform around the product with the kernel spectrum, 4 points per table chunk: chunk
-                // c + 1 is requested (into the other half of hh) before chunk c is used
-                pk_static_for<0, 4>([&](auto cc) __attribute__((always_inline)) {
-                    constexpr int c = decltype(cc)::value;
-                    if constexpr (c < 3) {
-                        __builtin_amdgcn_sched_barrier(0);
+            for (int q = 0; q < SLAB; ++q) f1[q] = lds_read(b1 + q);
+            DftPk<SLAB, false>::run(f0);
+            DftPk<SLAB, false>::run(f1);
+            // radix-2 of the 2M-point transform around the product with the kernel spectrum, 4 points per table chunk: chunk
+            // c + 1 is requested (into the other half of hh) before chunk c is used
+            pk_static_for<0, 4>([&](auto cc) __attribute__((always_inline)) {
+                constexpr int c = decltype(cc)::value;
+                if constexpr (c < 3) {
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) hh[4 * ((c + 1) & 1) + q] = hp4[4 * (c + 1) + q];
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    pk_static_for<0, 4>([&](auto qc) __attribute__((always_inline)) {
-                        constexpr int qq = decltype(qc)::value, q = 4 * c + qq, hq = 4 * (c & 1) + qq;
-                        const v2f wq = pk_twiddle<32, q, false>(w0p);       // w^k = w^{k0} exp(-2 pi i q3 / 32), q3 = q
-                        const v2f t = pk_cmul(f1[q], wq);
-                        const v2f x0 = f0[q] + t, x1 = f0[q] - t;
-                        const v2f y0 = pk_cmul(x0, (v2f){hh[hq].x, hh[hq].y}), y1 = pk_cmul(x1, (v2f){hh[hq].z, hh[hq].w});
-                        f0[q] = y0 + y1;
-                        f1[q] = pk_cmulc(y0 - y1, wq);
-                    });
+                    for (int q = 0; q < 4; ++q) hh[4 * ((c + 1) & 1) + q] = hp4[4 * (c + 1) + q];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                pk_static_for<0, 4>([&](auto qc) __attribute__((always_inline)) {
+                    constexpr int qq = decltype(qc)::value, q = 4 * c + qq, hq = 4 * (c & 1) + qq;
+                    const v2f wq = pk_twiddle<32, q, false>(w0p);       // w^k = w^{k0} exp(-2 pi i q3 / 32), q3 = q
+                    const v2f t = pk_cmul(f1[q], wq);
+                    const v2f x0 = f0[q] + t, x1 = f0[q] - t;
+                    const v2f y0 = pk_cmul(x0, (v2f){hh[hq].x, hh[hq].y}), y1 = pk_cmul(x1, (v2f){hh[hq].z, hh[hq].w});
+                    f0[q] = y0 + y1;
+                    f1[q] = pk_cmulc(y0 - y1, wq);
                 });
-                DftPk<SLAB, true>::run(f0);
+            });
+            DftPk<SLAB, true>::run(f0);
 #pragma unroll
-                for (int q = 0; q < SLAB; ++q) b0[q] = f0[q];
-                DftPk<SLAB, true>::run(f1);
+            for (int q = 0; q < SLAB; ++q) b0[q] = f0[q];
+            DftPk<SLAB, true>::run(f1);
 #pragma unroll
-                for (int q = 0; q < SLAB; ++q) b1[q] = f1[q];
-            }
-        } else {
-            middle_plain<GE>(lds, a.H[d] + ps * M, slabw, slab0, hh);
+            for (int q = 0; q < SLAB; ++q) b1[q] = f1[q];
         }
         PSX_STAMP(7);
         wave_sync();
@@ -1038,7 +1019,7 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
         {
             v2f *bB;
             int pB;
-            stageB_at(bB, pB, PAIR);
+            stageB_at(bB, pB);
             inv_stage_B<GE>(bB, pB, tw.twl + nB * TWB_LD);
         }
         PSX_STAMP(9);
@@ -1070,8 +1051,8 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
             // output sample i = nA + q*S1 - jout (jout = LDS position of output sample 0).  The first index is made opaque
             // so that the 48 per-q addresses are formed here from ONE pointer, not hoisted out of the group loop (they
             // would occupy 96 VGPRs there and spill).
-            // PART: index inside the output block; PAIR: LDS line = parity of the position in the 2M-point result
-            int ifirst = (PAIR ? 2 * nA + lineA : nA) - (a.Lh - 1);
+            // index inside the output block; LDS line = parity of the position in the 2M-point result
+            int ifirst = 2 * nA + lineA - (a.Lh - 1);
 
             asm volatile("" : "+v"(ifirst));
             const int dd = d;
@@ -1175,11 +1156,11 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
             } else {
                 // A wave's 64 butterflies belong to ONE line: its outputs go through a buffer descriptor whose range is exactly
                 // the window they may touch (store_window)
-                const int l = l0 + (PAIR ? 0 : __builtin_amdgcn_readfirstlane(lineA));
+                const int l = l0;
                 const bool lok = l < a.nlines;
                 // element index of output i inside the window: plain rows: i (window = row l); blocked: ((i>>3)*nlines+l)*8 + i%8
                 const int e0 = a.out_blocked ? ((ifirst >> IBS) * a.nlines + l) * IB + (ifirst & (IB - 1)) : ifirst;
-                constexpr int QS = PAIR ? 2 * S1 : S1;                    // output samples between two outputs of a butterfly
+                constexpr int QS = 2 * S1;                                // output samples between two outputs of a butterfly
                 const int estep = a.out_blocked ? (QS / IB) * a.nlines * IB : QS;
                 // the window is the output block only -- samples [b*B, b*B + Bv) of the line; in the blocked layout
                 // they are the contiguous range of B/8 sample-blocks (B is a multiple of 8)
@@ -1480,16 +1461,16 @@ int pick_r3(int N, int margin) {
 }
 
 // Lines longer than that: partition outputs (blocks of B, a multiple of 8) and kernel taps (segments of Lh) so that one
-// block x segment product is an M-point convolution, B + Lh - 1 <= M; fewest products, then fewest segments.
+// block x segment product is a convolution of the two coupled LDS lines, B + Lh - 1 <= 2 PART_M; fewest products, then
+// fewest segments.
 constexpr int PART_M = 576 * 16;
 constexpr int BR = IB > 8 ? IB : 8;      // output blocks start on a block boundary of the intermediate
-// mconv: points of one product -- PART_M, or 2 * PART_M when the two LDS lines are coupled into one transform (PAIR)
-void part_geometry(int N, int margin, int &B, int &Lh, int &S, int &NB, int mconv = 2 * PART_M) {
+void part_geometry(int N, int margin, int &B, int &Lh, int &S, int &NB) {
     const int P = N + 2 * margin;
     long best = -1;
     for (int s = 1; s <= 64; ++s) {
         const int lh = (P + s - 1) / s;
-        const int bmax = (mconv - lh + 1) / BR * BR;
+        const int bmax = (2 * PART_M - lh + 1) / BR * BR;
         if (bmax < BR) continue;
         const int nb = (N + bmax - 1) / bmax;
         const long cost = (long)s * nb;
@@ -1501,30 +1482,53 @@ void part_geometry(int N, int margin, int &B, int &Lh, int &S, int &NB, int mcon
     }
 }
 
-// Does a line of N samples run as the two-round DIF convolution (k_fresnel_lines, DIF)?  It must be too long for one coupled
-// product, fit one convolution of 4 x 9216 points, and the block x segment partition must need more than two rounds.
-bool dif_geometry(int N, int margin) {
-    // diagnostics (psx_debug_switch "no_dif" / "no_pair"): the round-2 / round-1 partition, read when a plan is created
-    if (debug_switch(DBG_NO_DIF) || debug_switch(DBG_NO_PAIR) || pick_r3(N, margin)) return false;
-    int B, Lh, S, NB;
-    part_geometry(N, margin, B, Lh, S, NB);
-    const int P = N + 2 * margin, Mc = 2 * PART_M;
-    return S * NB > 2 && P <= Mc && N + P - 1 <= 2 * Mc && N + P - 1 >= Mc;
+// The line kernel of an axis.  Every axis of a plan runs exactly one of them.
+enum class Kind {
+    R3,      // k_fresnel_lines: one 576 R3-point transform per line (N <= 4593)
+    P2,      // fresnel_p2.hip: one 256 R1-point transform with the wrapped outputs put right, where it is the shorter one
+    P2X,     // fresnel_p2x.hip: one 32768-point convolution per line in two coupled rounds of 16384 points (N ~ 16384)
+    DIF,     // k_fresnel_part<DIF>: one 4 x 9216-point convolution per line in two coupled rounds (12 280 <= N <= 18 402)
+    PAIR,    // k_fresnel_part: block x segment products of 2 x 9216 points (every other long line)
+};
+
+// R3 and P2 lines take one transform per line and round: the only kinds that run several distances per round (DUAL) or the
+// batched sources path
+bool one_transform(Kind k) { return k == Kind::R3 || k == Kind::P2; }
+
+struct AxisKind {
+    Kind kind = Kind::R3;
+    int radix = 0;                          // R3: M = 576 R3 (16 for DIF, PAIR); R1: M = 256 R1 (P2; 32 for P2X's stage tables)
+    int M = 0, Mconv = 0;                   // points of one LDS transform; of one convolution (2M where the two lines are coupled)
+    int B = 0, Lh = 0, S = 1, NB = 1;       // P2X, DIF, PAIR: NB output blocks of B, S kernel segments (rounds) of Lh taps
+};
+
+// Which kind serves lines of N samples with this margin.  no_p2 (diagnostics: psx_debug_switch "no_p2", read when a plan is
+// created): P2 lines take R3, P2X lines the DIF / PAIR rule.
+AxisKind choose(int N, int margin, bool no_p2 = false) {
+    if (const int r3 = pick_r3(N, margin)) {
+        const int r1 = no_p2 ? 0 : p2::pick_r1(N, margin);
+        if (r1 && 256 * r1 < 576 * r3) return {Kind::P2, r1, 256 * r1, 256 * r1};
+        return {Kind::R3, r3, 576 * r3, 576 * r3};
+    }
+    // the two-round kinds: the whole line is one output block and the whole kernel one segment, a round per half-spectrum
+    const int P = N + 2 * margin, L = N + P - 1, B = (N + BR - 1) / BR * BR;
+    if (!no_p2 && p2::x_serves(N, margin)) return {Kind::P2X, 32, p2::x_points() / 2, p2::x_points(), B, P, 2, 1};
+    AxisKind a{Kind::PAIR, 16, PART_M, 2 * PART_M};
+    part_geometry(N, margin, a.B, a.Lh, a.S, a.NB);
+    // lines that fit ONE convolution of 2 Mconv points take it in two rounds whenever the block x segment partition needs
+    // more; the extension must have a partner for some positions and none beyond 2 Mconv
+    if (a.S * a.NB > 2 && P <= a.Mconv && L <= 2 * a.Mconv && L >= a.Mconv) return {Kind::DIF, 16, PART_M, 2 * PART_M, B, P, 2, 1};
+    return a;
 }
 
 }  // namespace
 
 namespace psx {
 
-struct AxisTables {
-    int N = 0, R3 = 0, M = 0;
-    int p2 = 0;                                     // radix R1 of the power-of-two line kernels (fresnel_p2.hip; M = 256 R1), 0: the 576 R3-point ones
-    int p2x = 0;                                    // lines of ~16384 samples on the two-round power-of-two kernel (fresnel_p2x.hip)
-    int part = 0, B = 0, Lh = 0, S = 1, NB = 1;     // partitioned convolution (lines that do not fit one transform)
-    int pair = 0, Mconv = 0;                        // part: the two LDS lines coupled into one transform of Mconv = 2M points
-    int dif = 0;                                    // pair: one 2*Mconv-point convolution per line in two rounds (radix-2 DIF split)
-    float2 *w2 = nullptr;                           // pair: slab twiddles
-    float2 *w4 = nullptr;                           // dif: thread factors of w_{2 Mconv}
+struct AxisTables : AxisKind {
+    int N = 0;
+    float2 *w2 = nullptr;                           // DIF, PAIR, P2X: slab twiddles
+    float2 *w4 = nullptr;                           // DIF, P2X: thread factors of the radix-2 split
     float2 *twA = nullptr, *twB = nullptr;
     // float64 transforms of the kernel-spectrum build: taps = IDFT_P(chirp), spectrum = FFT_M(zero-padded taps) x S segments
     rocfft_plan planP = nullptr, planM = nullptr;
@@ -1574,86 +1578,59 @@ bool lds_engine_supported(int Nx, int Ny, int margin) {
     // block of it (B/8 sample-blocks x Ny lines) for a partitioned one; a row of the result in pass 2.
     if (!(margin >= 0 && margin <= Nx - 1 && margin <= Ny - 1 && margin <= 2048 && (int64_t)Nx * Ny < (1ll << 31))) return false;
     int64_t span = (int64_t)cdiv(Nx, IB) * IB;                       // samples of a pass-1 line inside one window
-    if (dif_geometry(Nx, margin)) {
-        // the window is the whole blocked intermediate and its byte offsets are unsigned: the furthest leg of a butterfly
-        // (dropped by the range check) must still be below 2^32
-        const int64_t imax = 2 * (2 * PART_M) - (Nx + 2 * margin - 1) + 2 * (PART_M / RAD);
-        return cdiv(imax, IB) * IB * (int64_t)Ny * (int64_t)sizeof(float2) < (1ll << 32);
-    }
-    if (!pick_r3(Nx, margin)) {
-        int B, Lh, S, NB;
-        part_geometry(Nx, margin, B, Lh, S, NB);      // the coupled-line partition (B is largest there)
-        span = B;
+    const AxisKind ax = choose(Nx, margin);
+    switch (ax.kind) {
+        case Kind::P2X:          // the DIF rounds' limit: with no_p2 these lines are DIF lines
+        case Kind::DIF: {
+            // the window is the whole blocked intermediate and its byte offsets are unsigned: the furthest leg of a butterfly
+            // (dropped by the range check) must still be below 2^32
+            const int64_t imax = 2 * (2 * PART_M) - (Nx + 2 * margin - 1) + 2 * (PART_M / RAD);
+            return cdiv(imax, IB) * IB * (int64_t)Ny * (int64_t)sizeof(float2) < (1ll << 32);
+        }
+        case Kind::PAIR: span = ax.B; break;           // one output block
+        default: break;
     }
     return span * (int64_t)Ny * (int64_t)sizeof(float2) < (1ll << 31);
 }
 
 static int make_axis(AxisTables &t, int N, int margin, size_t &bytes) {
     t.N = N;
-    t.R3 = pick_r3(N, margin);
-    // a power of two just below N + P - 1 with the wrapped outputs put right (fresnel_p2.hip) wherever it is the shorter transform
-    if (const int r1 = debug_switch(DBG_NO_P2) ? 0 : p2::pick_r1(N, margin); r1 && t.R3 && 256 * r1 < 576 * t.R3) t.p2 = r1;
-    const bool no_pair = debug_switch(DBG_NO_PAIR) != 0;     // diagnostics: the round-1 partition (M-point products)
-    if (!t.R3 && !debug_switch(DBG_NO_P2) && !debug_switch(DBG_NO_DIF) && !no_pair && p2::x_serves(N, margin)) {
-        t.p2x = 1;                                           // one 32768-point convolution per line, two rounds of 16384 points
-        t.R3 = 16;
-        t.S = 2;
-        t.NB = 1;
-        t.B = (N + BR - 1) / BR * BR;
-        t.Lh = N + 2 * margin;
-    }
-    if (!t.R3) {
-        t.R3 = 16;
-        t.part = 1;
-        t.pair = no_pair ? 0 : 1;
-        part_geometry(N, margin, t.B, t.Lh, t.S, t.NB, t.pair ? 2 * PART_M : PART_M);
-        // Lines that fit ONE convolution of 4 x 9216 points take it in two coupled rounds (k_fresnel_lines, DIF) whenever the
-        // block x segment partition needs more; the extension must have a partner for some positions and none beyond 2M
-        if (t.pair && dif_geometry(N, margin)) {
-            t.dif = 1;
-            t.S = 2;
-            t.NB = 1;
-            t.B = (N + BR - 1) / BR * BR;
-            t.Lh = N + 2 * margin;
-        }
-    }
-    t.M = t.p2 ? 256 * t.p2 : (t.p2x ? p2::x_points() / 2 : 576 * t.R3);
-    t.Mconv = (t.pair || t.p2x) ? 2 * t.M : t.M;
+    static_cast<AxisKind &>(t) = choose(N, margin, debug_switch(DBG_NO_P2) != 0);
+    auto table = [&](float2 *&buf, size_t n) {
+        bytes += sizeof(float2) * n;
+        return hipMalloc((void **)&buf, sizeof(float2) * n);
+    };
     const int S1 = t.M / RAD;
-    if (t.p2x) {
-        PSX_HIP(hipMalloc((void **)&t.twA, sizeof(float2) * p2::twA_elems(32)));
-        PSX_HIP(hipMalloc((void **)&t.twB, sizeof(float2) * p2::twB_elems()));
-        PSX_HIP(hipMalloc((void **)&t.w2, sizeof(float2) * 512));
-        PSX_HIP(hipMalloc((void **)&t.w4, sizeof(float2) * 512));
-        bytes += sizeof(float2) * (p2::twA_elems(32) + p2::twB_elems() + 1024);
-        if (int rc = p2::build_tables(t.twA, t.twB, 32, nullptr)) return rc;
-        if (int rc = p2::x_build_twiddles(t.w2, t.w4, nullptr)) return rc;
-    } else if (t.p2) {
-        PSX_HIP(hipMalloc((void **)&t.twA, sizeof(float2) * p2::twA_elems(t.p2)));
-        PSX_HIP(hipMalloc((void **)&t.twB, sizeof(float2) * p2::twB_elems()));
-        bytes += sizeof(float2) * (p2::twA_elems(t.p2) + p2::twB_elems());
-        if (int rc = p2::build_tables(t.twA, t.twB, t.p2, nullptr)) return rc;
-    } else {
-        PSX_HIP(hipMalloc((void **)&t.twA, sizeof(float2) * RAD * S1));
-        PSX_HIP(hipMalloc((void **)&t.twB, sizeof(float2) * RAD * t.R3));
-        bytes += sizeof(float2) * RAD * (S1 + t.R3);
-        k_stage_twiddles<<<(int)cdiv(RAD * S1, 256), 256>>>(t.twA, t.twB, t.M, t.R3);
-        if (int rc = launch_check("k_stage_twiddles")) return rc;
+    switch (t.kind) {
+        case Kind::P2X:
+            PSX_HIP(table(t.w2, 512));
+            PSX_HIP(table(t.w4, 512));
+            if (int rc = p2::x_build_twiddles(t.w2, t.w4, nullptr)) return rc;
+            [[fallthrough]];
+        case Kind::P2:
+            PSX_HIP(table(t.twA, p2::twA_elems(t.radix)));
+            PSX_HIP(table(t.twB, p2::twB_elems()));
+            if (int rc = p2::build_tables(t.twA, t.twB, t.radix, nullptr)) return rc;
+            break;
+        case Kind::DIF:
+            PSX_HIP(table(t.w4, 2 * S1));
+            k_dif_twiddles<<<(int)cdiv(2 * S1, 256), 256>>>(t.w4, t.M);
+            if (int rc = launch_check("k_dif_twiddles")) return rc;
+            [[fallthrough]];
+        case Kind::PAIR:
+            PSX_HIP(table(t.w2, t.M / t.radix));
+            k_pair_twiddles<<<(int)cdiv(t.M / t.radix, 256), 256>>>(t.w2, t.M, t.radix);
+            if (int rc = launch_check("k_pair_twiddles")) return rc;
+            [[fallthrough]];
+        case Kind::R3:
+            PSX_HIP(table(t.twA, RAD * S1));
+            PSX_HIP(table(t.twB, RAD * t.radix));
+            k_stage_twiddles<<<(int)cdiv(RAD * S1, 256), 256>>>(t.twA, t.twB, t.M, t.radix);
+            if (int rc = launch_check("k_stage_twiddles")) return rc;
+            break;
     }
     // float64 transforms of the kernel-spectrum build
     if (int rc = rocfft_ensure_setup()) return rc;
-    if (t.pair) {
-        PSX_HIP(hipMalloc((void **)&t.w2, sizeof(float2) * (t.M / t.R3)));
-        bytes += sizeof(float2) * (t.M / t.R3);
-        k_pair_twiddles<<<(int)cdiv(t.M / t.R3, 256), 256>>>(t.w2, t.M, t.R3);
-        if (int rc = launch_check("k_pair_twiddles")) return rc;
-    }
-    if (t.dif) {
-        PSX_HIP(hipMalloc((void **)&t.w4, sizeof(float2) * 2 * S1));
-        bytes += sizeof(float2) * 2 * S1;
-        k_dif_twiddles<<<(int)cdiv(2 * S1, 256), 256>>>(t.w4, t.M);
-        if (int rc = launch_check("k_dif_twiddles")) return rc;
-    }
     const size_t P = (size_t)(N + 2 * margin), M = (size_t)t.Mconv;
     PSX_ROCFFT(rocfft_plan_create(&t.planP, rocfft_placement_inplace, rocfft_transform_type_complex_inverse,
                                   rocfft_precision_double, 1, &P, 1, nullptr));
@@ -1694,14 +1671,18 @@ int lds_engine_create(psx_fresnel_plan *p) {
     p->bytes += sizeof(float2) * npix;
     PSX_HIP(hipMalloc((void **)&e->queue, sizeof(unsigned) * 2 * QUEUE_WORDS));
     PSX_HIP(hipMemset(e->queue, 0, sizeof(unsigned) * 2 * QUEUE_WORDS));
-    if (e->ax[0].dif || e->ax[1].dif || e->ax[0].p2x || e->ax[1].p2x) {
+    // the two-round kinds park a line's first round per workgroup: DIF 2 * PART_M points, P2X 2 * 16384 (ye and round O's
+    // input); one buffer serves both axes.  PAIR with several segments in pass 2: complex partial sums when only |.|^2 leaves
+    size_t per_wg = 0;
+    for (const AxisTables &t : e->ax)
+        if (t.kind == Kind::DIF || t.kind == Kind::P2X)
+            per_wg = std::max({per_wg, (size_t)2 * PART_M, t.kind == Kind::P2X ? p2::x_line_buffer_elems() : (size_t)0});
+    if (per_wg) {
         e->wgpart_groups = current_cu_count();
-        // DIF rounds park 2 * PART_M points per workgroup, the two-round power-of-two kernel 2 * 16384 (ye and round O's input)
-        const size_t per_wg = std::max((size_t)2 * PART_M, (e->ax[0].p2x || e->ax[1].p2x) ? p2::x_line_buffer_elems() : (size_t)0);
         PSX_HIP(hipMalloc((void **)&e->wgpart, sizeof(float2) * per_wg * (size_t)e->wgpart_groups));
         p->bytes += sizeof(float2) * per_wg * (size_t)e->wgpart_groups;
     }
-    if (e->ax[1].part && e->ax[1].S > 1 && !e->ax[1].dif) {      // complex partial sums of pass 2 when only |.|^2 leaves the pass
+    if (e->ax[1].kind == Kind::PAIR && e->ax[1].S > 1) {
         PSX_HIP(hipMalloc((void **)&e->part, sizeof(float2) * npix * p->max_dist));
         p->bytes += sizeof(float2) * npix * p->max_dist;
     }
@@ -1755,7 +1736,7 @@ static int kernel_spectrum(psx_fresnel_plan *p, AxisTables &t, double a, double 
     if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
         return fail(PSX_E_STATE, "psx_fresnel_propagate: kernel spectrum (a=%g, du=%g) is not cached and cannot be built while "
                                  "the stream is being captured: run the call once outside the capture first", a, du);
-    const size_t elems = t.p2x ? p2::x_spectrum_elems() : (t.p2 ? p2::spectrum_elems(t.p2) : (size_t)t.Mconv * t.S);
+    const size_t elems = t.kind == Kind::P2X ? p2::x_spectrum_elems() : (t.kind == Kind::P2 ? p2::spectrum_elems(t.radix) : (size_t)t.Mconv * t.S);
     KernEntry k{nullptr, t.Mconv, t.S, elems, ++e->clock};
     const size_t bytes = sizeof(float2) * elems;
     if (e->cache_bytes + bytes > CACHE_CAP_BYTES && !e->cache.empty()) {   // evict the least recently used table
@@ -1785,36 +1766,38 @@ static int kernel_spectrum(psx_fresnel_plan *p, AxisTables &t, double a, double 
         void *buf = t.bufP;
         PSX_ROCFFT(rocfft_execute(t.planP, &buf, nullptr, t.infoP));
     }
-    if (t.p2x) {
-        if (int rc = p2::x_pad_taps(t.bufP, t.bufM, P, st)) return rc;
-    } else
-        PSX_TIMED("k_kern_pad", st, k_kern_pad<<<(int)cdiv((int64_t)t.Mconv * t.S, 256), 256, 0, st>>>(t.bufP, t.bufM, P, t.Mconv, t.Lh, t.S, t.dif ? 2 : t.part));
+    auto give_back = [&](int rc) {               // not cached: give the table back
+        (void)hipFree(k.H);
+        e->cache_bytes -= bytes;
+        return rc;
+    };
+    // taps -> the zero-padded sequences of the forward transform
+    if (t.kind == Kind::P2X) {
+        if (int rc = p2::x_pad_taps(t.bufP, t.bufM, P, st)) return give_back(rc);
+    } else {
+        const int mode = t.kind == Kind::DIF ? 2 : (t.kind == Kind::PAIR ? 1 : 0);     // k_kern_pad's `part`
+        PSX_TIMED("k_kern_pad", st, k_kern_pad<<<(int)cdiv((int64_t)t.Mconv * t.S, 256), 256, 0, st>>>(t.bufP, t.bufM, P, t.Mconv, t.Lh, t.S, mode));
+    }
     {
         ProfScope ps("kern_fft_M", st);
         void *buf = t.bufM;
         PSX_ROCFFT(rocfft_execute(t.planM, &buf, nullptr, t.infoM));
     }
-    if (t.p2x) {
-        if (int rc = p2::x_perm_spectrum(t.bufM, t.bufP, k.H, P, st)) {
-            (void)hipFree(k.H);
-            e->cache_bytes -= bytes;
-            return rc;
-        }
-    } else if (t.p2) {
-        if (int rc = p2::perm_spectrum(t.bufM, t.bufP, k.H, t.p2, P, st)) {
-            (void)hipFree(k.H);
-            e->cache_bytes -= bytes;
-            return rc;
-        }
-    } else if (t.pair)
-        PSX_TIMED("k_kern_perm", st, k_kern_perm_pair<<<(int)cdiv((int64_t)t.M * t.S, 256), 256, 0, st>>>(t.bufM, reinterpret_cast<float4 *>(k.H), t.M, t.R3, t.S, t.dif ? 0.5 : 1.0));
-    else
-        PSX_TIMED("k_kern_perm", st, k_kern_perm<<<(int)cdiv((int64_t)t.M * t.S, 256), 256, 0, st>>>(t.bufM, k.H, t.M, t.R3, t.S));
-    if (int rc = launch_check("kernel spectrum")) {
-        (void)hipFree(k.H);                       // not cached: give the table back
-        e->cache_bytes -= bytes;
-        return rc;
+    // spectra -> the point order of the kind's LDS transform
+    const int grid = (int)cdiv((int64_t)t.M * t.S, 256);
+    int rc = 0;
+    switch (t.kind) {
+        case Kind::P2X: rc = p2::x_perm_spectrum(t.bufM, t.bufP, k.H, P, st); break;
+        case Kind::P2: rc = p2::perm_spectrum(t.bufM, t.bufP, k.H, t.radix, P, st); break;
+        case Kind::DIF:
+        case Kind::PAIR:
+            PSX_TIMED("k_kern_perm", st, k_kern_perm_pair<<<grid, 256, 0, st>>>(t.bufM, reinterpret_cast<float4 *>(k.H), t.M, t.radix, t.S,
+                                                                               t.kind == Kind::DIF ? 0.5 : 1.0));
+            break;
+        case Kind::R3: PSX_TIMED("k_kern_perm", st, k_kern_perm<<<grid, 256, 0, st>>>(t.bufM, k.H, t.M, t.radix, t.S)); break;
     }
+    if (!rc) rc = launch_check("kernel spectrum");
+    if (rc) return give_back(rc);
     e->cache.emplace(key, k);
     *out = k.H;
     return 0;
@@ -1855,37 +1838,90 @@ static int launch_lines(const LineArgs &la, hipStream_t st, const char *name) {
     return rc;
 }
 
-// longer lines: partitioned convolution, coupled lines (PAIR), DIF rounds
-template <bool CONTIG, bool PAIR, bool DIF = false>
+template <int R3>
+static int launch_lines_r(bool contig, bool dual, const LineArgs &la, hipStream_t st, const char *name) {
+    if (dual) return launch_lines<R3, true, true>(la, st, name);
+    return contig ? launch_lines<R3, true>(la, st, name) : launch_lines<R3, false>(la, st, name);
+}
+
+// longer lines: block x segment products of the coupled lines (PAIR), DIF rounds
+template <bool CONTIG, bool DIF>
 static int launch_part(const LineArgs &la, hipStream_t st, const char *name) {
-    using GE = LineGeom<16, PAIR>;
-    constexpr int LPG = PAIR ? 1 : GE::LINES;
+    using GE = LineGeom<16, true>;
     static std::atomic<unsigned long long> attr_mask{0};
     if (first_on_device(attr_mask))
-        PSX_HIP(hipFuncSetAttribute((const void *)k_fresnel_part<CONTIG, PAIR, DIF>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        PSX_HIP(hipFuncSetAttribute((const void *)k_fresnel_part<CONTIG, DIF>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)GE::lds_bytes));
-    const int nwork = ((la.nlines + LPG - 1) / LPG) * la.NB * (la.dist_inner ? 1 : la.n_dist);
+    const int nwork = la.nlines * la.NB * (la.dist_inner ? 1 : la.n_dist);      // one image line per round
     const int nslot = line_grid_slots(nwork, 0);
     if constexpr (DIF) {
         if (!la.wgpart || !la.w4 || 8 * nslot > la.wg_groups)
             return fail(PSX_E_STATE, "LDS engine: %d workgroups for %d private line buffers", 8 * nslot, la.wg_groups);
     }
-    PSX_TIMED(name, st, k_fresnel_part<CONTIG, PAIR, DIF><<<8 * nslot, T, GE::lds_bytes, st>>>(la));
+    PSX_TIMED(name, st, k_fresnel_part<CONTIG, DIF><<<8 * nslot, T, GE::lds_bytes, st>>>(la));
     return launch_check(name);
 }
 
-template <bool CONTIG>
-static int launch_lines_r3(int R3, const LineArgs &la, hipStream_t st, const char *name, bool part = false, bool pair = false,
-                           bool dif = false) {
-    if (part && pair && dif) return launch_part<CONTIG, true, true>(la, st, name);
-    if (part && pair) return launch_part<CONTIG, true>(la, st, name);
-    if (part) return launch_part<CONTIG, false>(la, st, name);
-    switch (R3) {
-        case 4: return launch_lines<4, CONTIG>(la, st, name);
-        case 8: return launch_lines<8, CONTIG>(la, st, name);
-        case 16: return launch_lines<16, CONTIG>(la, st, name);
+// One pass over the lines of an axis on the kernel of its kind.  contig: pass 1 (the samples of a line are adjacent); dual:
+// pass 1 with one line x two distances per round (R3 and P2 only, la.dist_inner set).  A line longer than the kind's transform
+// is refused.
+static int launch_axis(const AxisTables &t, bool contig, bool dual, const LineArgs &la, hipStream_t st, const char *name) {
+    bool fits = false;
+    switch (t.kind) {
+        case Kind::R3: fits = la.L <= 576 * t.radix; break;
+        case Kind::P2: fits = la.L - t.M <= p2::LXMAX; break;
+        case Kind::P2X: fits = la.L - 2 * t.Mconv <= p2::LXMAX; break;
+        case Kind::DIF: fits = la.L <= 2 * t.Mconv; break;
+        case Kind::PAIR: fits = la.B + la.Lh - 1 <= t.Mconv; break;
+    }
+    if (!fits || la.N != t.N)
+        return fail(PSX_E_UNSUPPORTED, "LDS engine: a line of %d samples (%d points) on an axis built for %d", la.N, la.L, t.N);
+    switch (t.kind) {
+        case Kind::R3:
+            switch (t.radix) {
+                case 4: return launch_lines_r<4>(contig, dual, la, st, name);
+                case 8: return launch_lines_r<8>(contig, dual, la, st, name);
+                case 16: return launch_lines_r<16>(contig, dual, la, st, name);
+            }
+            break;
+        case Kind::P2: return p2::launch(t.radix, contig, dual, la, st, name);
+        case Kind::P2X: return p2::x_launch(contig, la, st, name);
+        case Kind::DIF: return contig ? launch_part<true, true>(la, st, name) : launch_part<false, true>(la, st, name);
+        case Kind::PAIR: return contig ? launch_part<true, false>(la, st, name) : launch_part<false, false>(la, st, name);
     }
     return fail(PSX_E_UNSUPPORTED, "LDS engine: unsupported line length");
+}
+
+// line groups of `nlines` lines on an R3 or P2 axis (dual: shared-forward rounds take half the LDS lines)
+static int line_groups(const AxisTables &t, int nlines, bool dual) {
+    const int lpg = t.kind == Kind::P2 ? p2::lines_per_round(t.radix, dual) : TOT / t.M / (dual ? 2 : 1);
+    return (nlines + lpg - 1) / lpg;
+}
+
+// The geometry and tables of pass 1 (pass == 0: lines along axis 0 = rows of the transposed source, contiguous reads, into
+// the blocked intermediate) or pass 2 (pass == 1: lines along axis 1 = columns of the intermediate, strided reads: the second
+// transpose, into rows of the result) for n_dist distances; the caller sets the per-distance pointers, the work order and
+// the diagnostics.
+static LineArgs pass_args(const psx_fresnel_plan *p, int pass, int n_dist) {
+    const LdsEngine *e = p->lds;
+    const AxisTables &t = e->ax[pass];
+    LineArgs la;
+    if (pass == 0) {
+        la.N = p->Nx; la.nlines = p->Ny; la.P = p->Px;
+        la.in_si = 1; la.in_sl = p->Nx; la.in_blocked = 0; la.out_ld = 0; la.out_blocked = 1;
+    } else {
+        la.N = p->Ny; la.nlines = p->Nx; la.P = p->Py;
+        la.in_si = 0; la.in_sl = 0; la.in_blocked = 1; la.out_ld = p->Ny; la.out_blocked = 0;
+    }
+    la.margin = p->margin; la.L = la.N + la.P - 1;
+    la.twA = t.twA; la.twB = t.twB;
+    la.B = t.B; la.Lh = t.Lh; la.S = t.S; la.NB = t.NB;
+    la.w2 = t.w2; la.w4 = t.w4; la.wgpart = e->wgpart; la.wg_groups = e->wgpart_groups;
+    la.dsh = 2 * PART_M - la.P; la.thr = la.L - 2 * PART_M;
+    la.queue = e->use_queue ? e->queue + (size_t)pass * QUEUE_WORDS : nullptr;
+    la.n_dist = n_dist; la.dist_inner = 0; la.accumulate = 0;
+    la.stamps = nullptr; la.stamp_j = 1;
+    return la;
 }
 
 int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
@@ -1924,26 +1960,9 @@ int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
     const bool stamp_pass1 = debug_switch(DBG_STAMP_PASS1) != 0;   // diagnostics only (psx_debug_switch)
     const int stamp_round = debug_switch(DBG_STAMP_ROUND);
     {
-        LineArgs la;
-        la.N = p->Nx; la.nlines = p->Ny; la.margin = p->margin; la.P = p->Px; la.L = p->Nx + p->Px - 1;
-        la.in_si = 1; la.in_sl = p->Nx; la.in_blocked = 0; la.out_ld = 0; la.out_blocked = 1;
-        la.twA = e->ax[0].twA; la.twB = e->ax[0].twB;
-        la.accumulate = 0; la.stamps = stamp_pass1 ? g_stamps : nullptr; la.stamp_j = stamp_round;
-        la.queue = e->use_queue ? e->queue : nullptr;
-        la.n_dist = nnz;
-        const bool no_inner = debug_switch(DBG_NO_DIST_INNER) != 0;   // diagnostics: A/B of the work order
-        // one source for all distances: a workgroup takes the distances of a line group in consecutive rounds and fetches the
-        // group once -- but only when there are enough line groups to occupy every CU that way (small grids: 32 groups of 16
-        // lines at 512^2 would leave 224 CUs idle; there every (distance, group) pair is its own work item)
-        const int lds_lines = e->ax[0].p2 ? p2::lines_per_round(e->ax[0].p2, false) : TOT / (576 * e->ax[0].R3);
-        const int lines_per_group = (nnz >= 2 && !e->ax[0].part) ? lds_lines / 2 : lds_lines;   // shared-forward rounds take half the LDS lines
-        const int ngroups0 = (p->Ny + lines_per_group - 1) / lines_per_group;
-        la.dist_inner = (no_inner || e->ax[0].part || ngroups0 < current_cu_count()) ? 0 : 1;
-        // DIF rounds: the distances of a line in consecutive units of one workgroup, whose loaders keep the line in registers
-        // (k_fresnel_part) -- when the lines alone fill the chip
-        if (e->ax[0].dif && !no_inner && nnz >= 2 && p->Ny >= current_cu_count()) la.dist_inner = 1;
-        if (e->ax[0].p2x) la.dist_inner = (!no_inner && p->Ny >= current_cu_count()) ? 1 : 0;     // a line fetched once for all its rounds
-        la.B = e->ax[0].B; la.Lh = e->ax[0].Lh; la.S = e->ax[0].S; la.NB = e->ax[0].NB;
+        const AxisTables &t = e->ax[0];
+        LineArgs la = pass_args(p, 0, nnz);
+        la.stamps = stamp_pass1 ? g_stamps : nullptr; la.stamp_j = stamp_round;
         for (int i = 0; i < PSX_MAX_DIST; ++i) {
             const int k = i < nnz ? i : 0;
             la.src[i] = e->pre;
@@ -1958,68 +1977,46 @@ int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
             la.scale[i] = 1.f;
             la.gph[i] = make_float2(1.f, 0.f);
         }
-        la.w2 = e->ax[0].w2;
-        la.w4 = e->ax[0].w4; la.wgpart = e->wgpart; la.wg_groups = e->wgpart_groups;
-        la.dsh = 2 * PART_M - p->Px; la.thr = p->Nx + p->Px - 1 - 2 * PART_M;
-        const bool no_dual = debug_switch(DBG_NO_DUAL) != 0;        // diagnostics: A/B of the shared forward transform
-        if (e->ax[0].p2x) {
-            if (int rc = p2::x_launch(true, la, st, "k_fresnel_cols")) return rc;
-        } else if (!no_dual && la.dist_inner && nnz >= 2 && !e->ax[0].part) {
-            // one line x two distances per round: the forward transform of a line is shared by the pair
-            if (nnz & 1) {
-                la.H[nnz] = la.H[nnz - 1];
-                la.wave_out[nnz] = nullptr;       // odd count: the last pair's second result is computed and dropped
-            }
-            int rc = 0;
-            if (e->ax[0].p2) rc = p2::launch(e->ax[0].p2, true, true, la, st, "k_fresnel_cols");
-            else switch (e->ax[0].R3) {
-                case 4: rc = launch_lines<4, true, true>(la, st, "k_fresnel_cols"); break;
-                case 8: rc = launch_lines<8, true, true>(la, st, "k_fresnel_cols"); break;
-                default: rc = launch_lines<16, true, true>(la, st, "k_fresnel_cols"); break;
-            }
-            if (rc) return rc;
-        } else if (e->ax[0].p2) {
-            if (int rc = p2::launch(e->ax[0].p2, true, false, la, st, "k_fresnel_cols")) return rc;
-        } else if (int rc = launch_lines_r3<true>(e->ax[0].R3, la, st, "k_fresnel_cols", e->ax[0].part, e->ax[0].pair, e->ax[0].dif)) return rc;
+        // the work order: a workgroup takes the distances of a line (group) in consecutive rounds and fetches it once
+        // (dist_inner) -- but only when the lines alone occupy every CU that way (small grids: 32 groups of 16 lines at 512^2
+        // would leave 224 CUs idle; there every (distance, group) pair is its own work item)
+        const int cus = current_cu_count();
+        switch (t.kind) {
+            case Kind::R3:
+            case Kind::P2: la.dist_inner = line_groups(t, p->Ny, nnz >= 2) >= cus; break;
+            case Kind::DIF: la.dist_inner = nnz >= 2 && p->Ny >= cus; break;     // the loaders keep the line in registers
+            case Kind::P2X: la.dist_inner = p->Ny >= cus; break;                 // a line fetched once for all its rounds
+            case Kind::PAIR: break;
+        }
+        // one line x two distances per round: the forward transform of a line is shared by the pair
+        const bool dual = one_transform(t.kind) && la.dist_inner && nnz >= 2;
+        if (dual && (nnz & 1)) {
+            la.H[nnz] = la.H[nnz - 1];
+            la.wave_out[nnz] = nullptr;       // odd count: the last pair's second result is computed and dropped
+        }
+        if (int rc = launch_axis(t, true, dual, la, st, "k_fresnel_cols")) return rc;
     }
 
     // ---- pass 2: lines along axis 1 of the image = columns of the intermediate (strided reads: the second transpose);
     // line x writes row x of the result.  Again one launch for all distances.
-    {
-        LineArgs lb;
-        lb.N = p->Ny; lb.nlines = p->Nx; lb.margin = p->margin; lb.P = p->Py; lb.L = p->Ny + p->Py - 1;
-        lb.in_si = 0; lb.in_sl = 0; lb.in_blocked = 1; lb.out_ld = p->Ny; lb.out_blocked = 0;
-        lb.twA = e->ax[1].twA; lb.twB = e->ax[1].twB;
-        lb.accumulate = a.accumulate; lb.stamps = stamp_pass1 ? nullptr : g_stamps; lb.stamp_j = stamp_round;
-        lb.queue = e->use_queue ? e->queue + QUEUE_WORDS : nullptr;
-        lb.n_dist = nnz;
-        lb.dist_inner = 0;
-        lb.B = e->ax[1].B; lb.Lh = e->ax[1].Lh; lb.S = e->ax[1].S; lb.NB = e->ax[1].NB;
-        for (int i = 0; i < PSX_MAX_DIST; ++i) {
-            const int k = i < nnz ? i : 0, d = nz[k];
-            lb.src[i] = e->inter + (size_t)k * e->inter_elems;
-            if (i < nnz) {
-                if (int rc2 = kernel_spectrum(p, e->ax[1], a.a[d], a.du_y, st, &lb.H[i])) return rc2;
-            } else {
-                lb.H[i] = lb.H[0];
-            }
-            lb.wave_out[i] = a.wave_out ? a.wave_out[d] : nullptr;
-            lb.part[i] = lb.wave_out[i] ? lb.wave_out[i] : (e->part ? e->part + (size_t)k * npix : nullptr);
-            lb.inten_out[i] = a.inten_out ? a.inten_out[d] : nullptr;
-            lb.scale[i] = a.inten_scale ? a.inten_scale[d] : 1.f;
-            const double g = a.gphase ? a.gphase[d] : 0.0;
-            lb.gph[i] = make_float2((float)std::cos(g), (float)std::sin(g));   // exact reduction of ~1e11 rad (EXP:250)
+    LineArgs lb = pass_args(p, 1, nnz);
+    lb.accumulate = a.accumulate; lb.stamps = stamp_pass1 ? nullptr : g_stamps; lb.stamp_j = stamp_round;
+    for (int i = 0; i < PSX_MAX_DIST; ++i) {
+        const int k = i < nnz ? i : 0, d = nz[k];
+        lb.src[i] = e->inter + (size_t)k * e->inter_elems;
+        if (i < nnz) {
+            if (int rc = kernel_spectrum(p, e->ax[1], a.a[d], a.du_y, st, &lb.H[i])) return rc;
+        } else {
+            lb.H[i] = lb.H[0];
         }
-        lb.w2 = e->ax[1].w2;
-        lb.w4 = e->ax[1].w4; lb.wgpart = e->wgpart; lb.wg_groups = e->wgpart_groups;
-        lb.dsh = 2 * PART_M - p->Py; lb.thr = p->Ny + p->Py - 1 - 2 * PART_M;
-        if (e->ax[1].p2x) {
-            if (int rc2 = p2::x_launch(false, lb, st, "k_fresnel_rows")) return rc2;
-        } else if (e->ax[1].p2) {
-            if (int rc2 = p2::launch(e->ax[1].p2, false, false, lb, st, "k_fresnel_rows")) return rc2;
-        } else if (int rc2 = launch_lines_r3<false>(e->ax[1].R3, lb, st, "k_fresnel_rows", e->ax[1].part, e->ax[1].pair, e->ax[1].dif)) return rc2;
+        lb.wave_out[i] = a.wave_out ? a.wave_out[d] : nullptr;
+        lb.part[i] = lb.wave_out[i] ? lb.wave_out[i] : (e->part ? e->part + (size_t)k * npix : nullptr);
+        lb.inten_out[i] = a.inten_out ? a.inten_out[d] : nullptr;
+        lb.scale[i] = a.inten_scale ? a.inten_scale[d] : 1.f;
+        const double g = a.gphase ? a.gphase[d] : 0.0;
+        lb.gph[i] = make_float2((float)std::cos(g), (float)std::sin(g));   // exact reduction of ~1e11 rad (EXP:250)
     }
-    return 0;
+    return launch_axis(e->ax[1], false, false, lb, st, "k_fresnel_rows");
 }
 
 // ---- a batch of source waves in ONE launch per pass ------------------------------------------------------------------------
@@ -2035,12 +2032,12 @@ int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
     hipStream_t st = a.stream;
     const int V = a.n_src * a.n_dist;
     const size_t npix = (size_t)p->Nx * p->Ny;
-    // one launch per pass only pays where a launch is mostly overhead and the generic (pair, group) work order applies
-    const int lds_lines = e->ax[0].p2 ? p2::lines_per_round(e->ax[0].p2, false) : TOT / (576 * e->ax[0].R3);
-    const int ngroups0 = (p->Ny + lds_lines - 1) / lds_lines;
-    bool batched = a.n_src > 1 && !e->ax[0].part && !e->ax[1].part && ngroups0 < current_cu_count() && V <= MAX_LINE &&
-                   (!e->ax[0].p2 || V <= p2::max_distances(e->ax[0].p2)) && (!e->ax[1].p2 || V <= p2::max_distances(e->ax[1].p2)) &&
-                   a.n_src <= PSX_MAX_SRC;
+    // one launch per pass only pays where a launch is mostly overhead and the generic (pair, group) work order applies: one
+    // transform per line on both axes (the kinds whose rounds take any number of "distances" side by side)
+    bool batched = a.n_src > 1 && a.n_src <= PSX_MAX_SRC && V <= MAX_LINE;
+    for (const AxisTables &t : e->ax)
+        batched = batched && one_transform(t.kind) && (t.kind != Kind::P2 || V <= p2::max_distances(t.radix));
+    batched = batched && line_groups(e->ax[0], p->Ny, false) < current_cu_count();
     for (int v = 0; v < V && batched; ++v) batched = a.a[v] != 0.0;         // z == 0 pairs take the one-source path
     if (!batched) {
         for (int s = 0; s < a.n_src; ++s) {
@@ -2095,20 +2092,7 @@ int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
         if (int rc = launch_check("k_source_transposed")) return rc;
     }
     // ---- pass 1 and pass 2: pair v = (source v / n_dist, distance v % n_dist) is "distance" v of the line kernels
-    LineArgs la;
-    la.N = p->Nx; la.nlines = p->Ny; la.margin = p->margin; la.P = p->Px; la.L = p->Nx + p->Px - 1;
-    la.in_si = 1; la.in_sl = p->Nx; la.in_blocked = 0; la.out_ld = 0; la.out_blocked = 1;
-    la.twA = e->ax[0].twA; la.twB = e->ax[0].twB;
-    la.accumulate = 0; la.stamps = nullptr; la.stamp_j = 1; la.n_dist = V; la.dist_inner = 0; la.queue = e->use_queue ? e->queue : nullptr;
-    la.B = e->ax[0].B; la.Lh = e->ax[0].Lh; la.S = e->ax[0].S; la.NB = e->ax[0].NB; la.w2 = e->ax[0].w2;
-    la.w4 = nullptr; la.wgpart = nullptr; la.wg_groups = 0; la.dsh = 0; la.thr = 0;
-    LineArgs lb;
-    lb.N = p->Ny; lb.nlines = p->Nx; lb.margin = p->margin; lb.P = p->Py; lb.L = p->Ny + p->Py - 1;
-    lb.in_si = 0; lb.in_sl = 0; lb.in_blocked = 1; lb.out_ld = p->Ny; lb.out_blocked = 0;
-    lb.twA = e->ax[1].twA; lb.twB = e->ax[1].twB;
-    lb.accumulate = 0; lb.stamps = nullptr; lb.stamp_j = 1; lb.n_dist = V; lb.dist_inner = 0; lb.queue = e->use_queue ? e->queue + QUEUE_WORDS : nullptr;
-    lb.B = e->ax[1].B; lb.Lh = e->ax[1].Lh; lb.S = e->ax[1].S; lb.NB = e->ax[1].NB; lb.w2 = e->ax[1].w2;
-    lb.w4 = nullptr; lb.wgpart = nullptr; lb.wg_groups = 0; lb.dsh = 0; lb.thr = 0;
+    LineArgs la = pass_args(p, 0, V), lb = pass_args(p, 1, V);
     for (int i = 0; i < MAX_LINE; ++i) {
         const int v = i < V ? i : 0;
         la.src[i] = e->pre_b + (size_t)(v / a.n_dist) * npix;
@@ -2132,10 +2116,8 @@ int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
             lb.H[i] = lb.H[0];
         }
     }
-    if (int rc = e->ax[0].p2 ? p2::launch(e->ax[0].p2, true, false, la, st, "k_fresnel_cols")
-                             : launch_lines_r3<true>(e->ax[0].R3, la, st, "k_fresnel_cols")) return rc;
-    return e->ax[1].p2 ? p2::launch(e->ax[1].p2, false, false, lb, st, "k_fresnel_rows")
-                       : launch_lines_r3<false>(e->ax[1].R3, lb, st, "k_fresnel_rows");
+    if (int rc = launch_axis(e->ax[0], true, false, la, st, "k_fresnel_cols")) return rc;
+    return launch_axis(e->ax[1], false, false, lb, st, "k_fresnel_rows");
 }
 
 }  // namespace psx

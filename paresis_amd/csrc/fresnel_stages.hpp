@@ -75,10 +75,11 @@ struct LineArgs {
     float scale[MAX_LINE];
     float2 gph[MAX_LINE];               // global phase factor exp(i k z / M) of the complex result
     int accumulate;
-    // Partitioned convolution (PART instantiations; lines too long for one M-point transform in LDS): the N outputs of a
-    // line are cut into NB blocks of B, the P-tap kernel into S segments of Lh (B + Lh - 1 <= M); a work unit is
-    // (distance, line group, block) and takes S consecutive rounds, one per segment, whose results add up in `part`
-    // (complex, same layout as the complex output; it IS the complex output when that is wanted).  H[d] then holds S spectra.
+    // Partitioned convolution (k_fresnel_part; lines too long for one M-point transform in LDS): the N outputs of a
+    // line are cut into NB blocks of B, the P-tap kernel into S segments of Lh (B + Lh - 1 <= 2M: the two LDS lines are
+    // coupled into one transform); a work unit is (distance, line, block) and takes S consecutive rounds, one per segment,
+    // whose results add up in `part` (complex, same layout as the complex output; it IS the complex output when that is
+    // wanted).  H[d] then holds S spectra.
     int B, Lh, S, NB;
     float2 *part[MAX_LINE];
     const float2 *w2;       // PAIR: w_2M^{k0} of each 16-point slab, k0 = q1 + 24 q2  (576 entries)

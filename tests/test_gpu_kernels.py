@@ -748,11 +748,13 @@ def test_pack_counts_roundtrip_and_overflow(ops):
         ops.pack_counts(torch.zeros(4, device="cuda"), torch.zeros(5, dtype=torch.int16, device="cuda"), 0, exc, cnt, flag)
 
 
-@pytest.mark.parametrize("case", [(200, 312, 5, 2, 2), (512, 512, 25, 1, 2), (96, 130, 3, 2, 1), (640, 384, 18, 2, 2)])
+@pytest.mark.parametrize("case", [(200, 312, 5, 2, 2), (512, 512, 25, 1, 2), (96, 130, 3, 2, 1), (640, 384, 18, 2, 2),
+                                  (16384, 36, 3, 1, 2), (36, 16384, 2, 2, 2)])
 def test_propagate_sources_matches_one_call_per_source(ops, case):
     """psx_fresnel_propagate_sources (the energies of a detector bin in three launches on small grids): every (source,
     distance) result is bit for bit what psx_fresnel_propagate gives for that source -- own input wave, amplitude,
-    coefficients, chirp, phase and scale; more sources than one launch holds; a z = 0 pair (one-source path); both engines."""
+    coefficients, chirp, phase and scale; more sources than one launch holds; a z = 0 pair (one-source path); both engines;
+    lines of about 16384 samples on either axis (two-round kernel: the one-source path)."""
     Nx, Ny, ns, nd, engine = case
     g = torch.Generator(device="cuda").manual_seed(Nx + ns)
     T = torch.rand((2, Nx, Ny), generator=g, device="cuda") * 1e-4

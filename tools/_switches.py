@@ -1,5 +1,5 @@
-"""Diagnostic switches for the tools: `PSX_SWITCHES="no_dif=1 stamp_round=2" python tools/x.py` (read HERE, by the tool, and
-handed to psx_debug_switch -- the library itself reads nothing from the environment) or apply("no_dual=1")."""
+"""Diagnostic switches for the tools: `PSX_SWITCHES="no_p2=1 stamp_round=2" python tools/x.py` (read HERE, by the tool, and
+handed to psx_debug_switch -- the library itself reads nothing from the environment) or apply("stamp_pass1=1")."""
 import os
 import sys
 

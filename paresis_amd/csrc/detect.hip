@@ -465,12 +465,11 @@ struct PsfArgs {
     float gx[20], gy[20];
 };
 
-#ifndef PSX_PSF_TR
-#define PSX_PSF_TR 16        // output rows per workgroup (build-time A/B, gpurun_out/r5s71: 16 -> 25 KB of LDS, six workgroups per CU: 0.0270 against 0.0287 ms with 32)
-#endif
+// output rows per workgroup (session r5s71: 16 -> 25 KB of LDS, six workgroups per CU: 0.0270 against 0.0287 ms with 32)
+constexpr int PSF_TR = 16;
 template <int WQ>
 __global__ __launch_bounds__(256) void k_psf_tile(PsfArgs a) {
-    constexpr int WT = 4 * WQ - 3, TR = PSX_PSF_TR, TC = 128, SR = TR + WT - 1, SC = TC + 4 * WQ - 4;   // SC: TC + WT - 1, a multiple of 4
+    constexpr int WT = 4 * WQ - 3, TR = PSF_TR, TC = 128, SR = TR + WT - 1, SC = TC + 4 * WQ - 4;   // SC: TC + WT - 1, a multiple of 4
     __shared__ __attribute__((aligned(16))) float sin_[SR * SC];
     __shared__ __attribute__((aligned(16))) float mid[SR * TC];
     const float *const in = a.in[blockIdx.z];
@@ -1138,7 +1137,7 @@ int psf_tile(const BandOp &C, const BandOp &R, const float *const *in, int in_pi
     a.Rin = R.n_in; a.Cin = C.n_in; a.Rout = R.n_out; a.Cout = C.n_out; a.ox = R.h_start[0]; a.oy = C.h_start[0];
     for (int k = 0; k < R.W; ++k) a.gx[k] = R.h_w0[k];
     for (int l = 0; l < C.W; ++l) a.gy[l] = C.h_w0[l];
-    const dim3 grid((C.n_out + 127) / 128, (R.n_out + PSX_PSF_TR - 1) / PSX_PSF_TR, nimg);
+    const dim3 grid((C.n_out + 127) / 128, (R.n_out + PSF_TR - 1) / PSF_TR, nimg);
     const int W = std::max(C.W, R.W);
     if (W <= 9) PSX_TIMED("k_psf_tile", st, k_psf_tile<3><<<grid, 256, 0, st>>>(a));
     else if (W <= 13) PSX_TIMED("k_psf_tile", st, k_psf_tile<4><<<grid, 256, 0, st>>>(a));

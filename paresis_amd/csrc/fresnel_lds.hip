@@ -634,7 +634,7 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
         // reflect(((t + 1 + mg) mod P) - mg) of the line: five vector instructions and a buffer load whose descriptor is the
         // line.  The 72 positions of a thread then move as NHA + NHB instead of 36 + 36: the more of them travel during the
         // transform, the shorter the fetch that is exposed between barriers (3) and (4).
-        constexpr int NHA = DIF ? PSX_DIF_NHA : NH, NHB = 2 * NH - NHA;
+        constexpr int NHA = DIF ? DIF_NHA : NH, NHB = 2 * NH - NHA;
         float2 xs[NHA];
         auto fetch_dif = [&](int j, auto k0_tag, auto cnt_tag) __attribute__((always_inline)) {
             constexpr int K0 = decltype(k0_tag)::value, CNT = decltype(cnt_tag)::value;
@@ -715,9 +715,9 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
             // the previous form (all 72 fetched every round, 60 + 12): the loaders needed 13-18 us to ISSUE a round's loads --
             // pass 2 reads one 64-byte sector per 8-byte sample and is bound by the L2 -> L1 path, pass 1 by HBM -- and the engine
             // waited for them at barrier (2) for 2.7-9.3 us of every round (gpurun_out/r4s10).
-            constexpr int NK = PSX_DIF_KEEP, NR = (2 * NH - NK) / 2;
-            static_assert(NK + 2 * NR == 2 * NH && NK >= 0 && NR >= 1, "kept + 2 rotating chunks = the 72 positions of a loader thread");
-            float2 xk[NK > 0 ? NK : 1], xr[NR];
+            constexpr int NK = DIF_KEEP, NR = (2 * NH - NK) / 2;
+            static_assert(NK + 2 * NR == 2 * NH && NK > 0 && NR >= 1, "kept + 2 rotating chunks = the 72 positions of a loader thread");
+            float2 xk[NK], xr[NR];
             auto fetch_pos = [&](int j, auto k0_tag, auto cnt_tag, auto &dst) __attribute__((always_inline)) {
                 constexpr int K0 = decltype(k0_tag)::value, CNT = decltype(cnt_tag)::value;
                 int d, g;
@@ -758,11 +758,9 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
                 sp = a.src[d];
             };
             if (nj > 0) {
-                if constexpr (NK > 0) {
-                    fetch_pos(0, K0{}, KK{}, xk);
-                    spread_pos(K0{}, KK{}, xk);
-                    line_of(0, ksrc, kg);
-                }
+                fetch_pos(0, K0{}, KK{}, xk);
+                spread_pos(K0{}, KK{}, xk);
+                line_of(0, ksrc, kg);
                 fetch_pos(0, KK{}, KR{}, xr);
                 spread_pos(KK{}, KR{}, xr);
                 fetch_pos(0, KB{}, KR{}, xr);
@@ -775,15 +773,13 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
                 lds_barrier();                               // (1)
                 if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 16] = wall_clock64();
                 if (more) {
-                    if constexpr (NK > 0) {
-                        const float2 *sp;
-                        int g;
-                        line_of(j + 1, sp, g);
-                        if (sp != ksrc || g != kg) {         // uniform: a new line
-                            fetch_pos(j + 1, K0{}, KK{}, xk);
-                            ksrc = sp;
-                            kg = g;
-                        }
+                    const float2 *sp;
+                    int g;
+                    line_of(j + 1, sp, g);
+                    if (sp != ksrc || g != kg) {             // uniform: a new line
+                        fetch_pos(j + 1, K0{}, KK{}, xk);
+                        ksrc = sp;
+                        kg = g;
                     }
                     fetch_pos(j + 1, KK{}, KR{}, xr);
                 }
@@ -793,7 +789,7 @@ __global__ __launch_bounds__(T) void k_fresnel_part(LineArgs a) {
                 if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 18] = wall_clock64();
                 __builtin_amdgcn_s_setprio(3);
                 if (more) {
-                    if constexpr (NK > 0) spread_pos(K0{}, KK{}, xk);
+                    spread_pos(K0{}, KK{}, xk);
                     spread_pos(KK{}, KR{}, xr);
                     if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 21] = wall_clock64();
                     fetch_pos(j + 1, KB{}, KR{}, xr);

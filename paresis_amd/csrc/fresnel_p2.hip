@@ -41,19 +41,6 @@ constexpr int TLD = 256;       // loader threads
 constexpr int TT = TE + TLD;
 constexpr int TOT2 = 16384;    // complex points resident in LDS per workgroup
 constexpr int LXM = psx::p2::LXMAX;
-// build-time A/B switches (tools/ab_p2.sh builds one library per setting; both arms of a comparison run on ONE box)
-#ifndef PSX_P2_SKIP_LEGS
-#define PSX_P2_SKIP_LEGS 1     // inverse stage A: the legs that lie before sample 0 for every butterfly are not stored
-#endif
-#ifndef PSX_P2_PRIO
-#define PSX_P2_PRIO 0          // 1: static priority 1 for engine waves 4-7 (the younger wave of every SIMD)
-#endif
-#ifndef PSX_P2_TWEARLY
-#define PSX_P2_TWEARLY 0       // 1: stage A's twiddle powers are read together with the butterfly's inputs
-#endif
-#ifndef PSX_P2_LDPRIO
-#define PSX_P2_LDPRIO 0        // priority of the loader waves while they issue a round's fetch
-#endif
 
 template <int R1_, bool DUAL_>
 struct G2 {
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
     const int tid = threadIdx.x;
     const int N = a.N, mg = a.margin;
     const int Lx = a.L - M;                // outputs whose window wraps (<= 0: none)
-    const bool upper_half = PSX_P2_SKIP_LEGS && ((a.P - 1) >> 8) >= R1 / 2;   // the lower half of an inverse stage-A butterfly's legs lies before sample 0 (store_legs)
+    const bool upper_half = ((a.P - 1) >> 8) >= R1 / 2;   // the lower half of an inverse stage-A butterfly's legs lies before sample 0 (store_legs)
 
     // ---- work units: exactly k_fresnel_lines' order (XCD-contiguous chunks of line groups, static shares or queues)
     const int ngroups = (a.nlines + LPG - 1) / LPG;
@@ -364,9 +351,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             const bool claiming = qround && ring_ok(ucur + 1);
             unsigned mine = 0xffffffffu;
             if (claiming && !own_dry && lt == 0) mine = atomicAdd(qcount(slot), 1u);
-            if (PSX_P2_LDPRIO) __builtin_amdgcn_s_setprio(PSX_P2_LDPRIO);
             if (more) fetch(j + 1);
-            if (PSX_P2_LDPRIO) __builtin_amdgcn_s_setprio(0);
             if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 17] = wall_clock64();
             fixup(j);
             lds_barrier();                               // (2) engine: wave-private stages done
@@ -435,7 +420,6 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
     // line = the butterflies of the first four waves; with smaller radices every thread has its share
     const bool fwdA_on = !(DUAL && R1 == 32) || tid < TE / 2;
     constexpr int NBAF = DUAL ? (R1 == 32 ? 1 : NBA / 2) : NBA;      // forward stage-A butterflies per thread
-    if (PSX_P2_PRIO && tid >= TE / 2) __builtin_amdgcn_s_setprio(1);
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 32 + 0] = wall_clock64();
     lds_barrier();                                       // (0) first group is in LDS
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 32 + 1] = wall_clock64();
@@ -460,14 +444,13 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
 #pragma unroll
                 for (int q = 0; q < R1; ++q) v[i][q] = p[q * BSTR];
             }
-            if (PSX_P2_TWEARLY) tw_powers<R1>(pw, tP + (tid & 255) * LDP);      // n = b & 255 is the same for every butterfly of a thread
 #pragma unroll
             for (int i = 0; i < NBAF; ++i) {
                 const int b = tid + TE * i;
                 v2f *p = Lb + (b >> 8) * MP + (b & 255) + ((b & 255) >> 5);
                 DftPk<R1, false>::run(v[i]);
                 __builtin_amdgcn_sched_barrier(0);
-                if (!PSX_P2_TWEARLY && i == 0) tw_powers<R1>(pw, tP + (tid & 255) * LDP);
+                if (i == 0) tw_powers<R1>(pw, tP + (tid & 255) * LDP);      // n = b & 255 is the same for every butterfly of a thread
                 twiddle_A2<R1, false>(v[i], pw);
 #pragma unroll
                 for (int q = 0; q < R1; ++q) p[q * BSTR] = v[i][q];
@@ -599,7 +582,6 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
         // 32 points LDS is free: the loaders fill it with the next group meanwhile.
         {
             v2f v[NBA][R1], cf[NBA], pw[5];
-            if (PSX_P2_TWEARLY) tw_powers<R1>(pw, tP + (tid & 255) * LDP);
 #pragma unroll
             for (int i = 0; i < NBA; ++i) {
                 const int b = tid + TE * i, n = b & 255;
@@ -617,7 +599,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
                 int bo = tid + TE * i;
                 asm volatile("" : "+v"(bo));         // opaque: the per-leg addresses are formed here, not hoisted out of the round loop
                 const int n = bo & 255, lb = bo >> 8;
-                if (!PSX_P2_TWEARLY && i == 0) tw_powers<R1>(pw, tP + n * LDP);
+                if (i == 0) tw_powers<R1>(pw, tP + n * LDP);
                 twiddle_A2<R1, true>(v[i], pw);
                 __builtin_amdgcn_sched_barrier(0);
                 // (computing only the upper half of the legs when the lower half is not stored -- 23 instead of 27 instructions per

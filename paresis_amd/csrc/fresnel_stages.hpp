@@ -31,26 +31,23 @@ constexpr int RAD = 24;       // radix of the two big stages
 // The intermediate between the two passes is stored in blocks of IB samples of a pass-1 line: [Nx/IB][Ny][IB].  Pass 1
 // still writes whole 128-byte lines (2 image rows x 8 samples), and the 16-byte pieces a pass-2 workgroup reads (two
 // adjacent pass-2 lines) sit 64 bytes apart instead of a whole image row: half the cache lines per wave load.
-#ifndef PSX_IB
-#define PSX_IB 8              // build-time A/B of the block shape (tools/ab_ib.sh): 4, 8, 16
-#endif
-constexpr int IB = PSX_IB;
-constexpr int IBS = IB == 4 ? 2 : (IB == 8 ? 3 : 4);      // log2(IB)
+constexpr int IB = 8;
+constexpr int IBS = 3;                                    // log2(IB)
 static_assert((1 << IBS) == IB, "intermediate block size");
 // Byte stride of consecutive samples of ONE pass-1 line inside the blocked intermediate, as a shift: the ONLY place it is
-// derived.  (Round 4, gpurun_out/r4s2: a loader's buffer-descriptor range was written `N << 6` -- right for IB = 8 only -- and
-// the IB = 4 A/B build read twice past its intermediate until 5b1bf8b; every such stride now comes from these two constants.)
+// derived.  (Round 4, session r4s2: a loader's buffer-descriptor range was written `N << 6` -- right for IB = 8 only -- and
+// an IB = 4 build read twice past its intermediate until 5b1bf8b; every such stride now comes from these two constants.)
 constexpr int SAMPLE_SHIFT = 3;                           // log2(sizeof(float2)): contiguous lines
 constexpr int BLOCKED_SAMPLE_SHIFT = IBS + SAMPLE_SHIFT;  // log2(IB * sizeof(float2)): lines of the blocked intermediate
 static_assert((1 << SAMPLE_SHIFT) == sizeof(float2) && (1 << BLOCKED_SAMPLE_SHIFT) == IB * sizeof(float2),
               "sample strides of the intermediate");
 constexpr int QUEUE_WORDS = 16 * 257;     // work queues: a counter per workgroup (<= 256, 64 bytes apart) + the count of workgroups done
-#ifndef PSX_DIF_KEEP
-#define PSX_DIF_KEEP 48       // DIF rounds: positions (of 72 per loader thread) fetched once per line and kept in registers for its
-#endif                        // later rounds; the other 24 rotate through a 12-position buffer every round (0: nothing kept)
-#ifndef PSX_DIF_NHA
-#define PSX_DIF_NHA 60        // DIF rounds: window positions (of 72 per loader thread) that travel during the transform; the rest is
-#endif                        // fetched between barriers (3) and (4).  52 / 56 / 60: 16384^2 passes 13.17 + 10.99 / 13.02 + 11.05 / 13.00 + 10.88 ms
+// DIF rounds: positions (of 72 per loader thread) fetched once per line and kept in registers for its later rounds; the other
+// 24 rotate through a 12-position buffer every round
+constexpr int DIF_KEEP = 48;
+// DIF rounds: window positions (of 72 per loader thread) that travel during the transform; the rest is fetched between
+// barriers (3) and (4).  52 / 56 / 60: 16384^2 passes 13.17 + 10.99 / 13.02 + 11.05 / 13.00 + 10.88 ms
+constexpr int DIF_NHA = 60;
 
 __host__ __device__ constexpr int phys(int p) { return p + (p >> 5); }   // one pad slot per 32: conflict-free slabs
 

@@ -16,15 +16,12 @@ using namespace psx;
 namespace {
 
 constexpr int MT = 32;   // tile side
-// Cell side of the plan's sphere bins (a build-time A/B: tools/ab_membrane.sh).  A tile's candidates are the spheres of every
-// cell its window (tile + the largest sphere window on either side) meets: with 32-pixel cells that is 96 x 96 pixels of cells
-// for a 46-pixel window at the bench's sphere size -- ~126 candidates for ~26 hits.  Finer cells stage fewer candidates but make
-// more (layer, cell row) jobs, i.e. more staging rounds with their barriers: k_membrane per 4096^2 position 0.084 ms (32-pixel
-// cells) / 0.098 (16) / 0.111 (8) -- gpurun_out/r5s13, two rounds on one box.  The candidates are not what costs; 32 stays.
-#ifndef PSX_MEMBRANE_CELL
-#define PSX_MEMBRANE_CELL 32
-#endif
-constexpr int MC = PSX_MEMBRANE_CELL;
+// Cell side of the plan's sphere bins.  A tile's candidates are the spheres of every cell its window (tile + the largest sphere
+// window on either side) meets: with 32-pixel cells that is 96 x 96 pixels of cells for a 46-pixel window at the bench's sphere
+// size -- ~126 candidates for ~26 hits.  Finer cells stage fewer candidates but make more (layer, cell row) jobs, i.e. more
+// staging rounds with their barriers: k_membrane per 4096^2 position 0.084 ms (32-pixel cells) / 0.098 (16) / 0.111 (8) --
+// session r5s13, two rounds on one box.  The candidates are not what costs; 32 stays.
+constexpr int MC = 32;
 
 struct Sphere {
     double xf, yf, r;
@@ -94,27 +91,15 @@ struct CellSphere {
 // compacts the spheres of one job whose window meets the tile, eight jobs per round -- both layers of the usual two-layer
 // membrane in one round -- into one flat list.  The layers of a position (same list, one integer offset each,
 // getMembraneFromFile.py:139-142) are summed before the single store, and the uniform support map is written by the same launch.
-#ifndef PSX_ML_OFF
-#define PSX_ML_OFF 0          // timing experiments: 1 no splat, 2 no stores, 4 no search for spheres at all
-#endif
-// Tile (rows x columns) and workgroup size of the layers kernel -- build-time A/B, tools/ab_membrane_tile.sh.  Timing experiments
-// on the 32 x 32 x 256 form (PSX_ML_OFF; gpurun_out/r5s63, kernel by event pairs, 4096^2, two layers of 15 um spheres): whole kernel
-// 0.0733 ms; without the splat 0.0310; without the stores 0.0685; launch + zeroing alone 0.0142 -- the splat is 58 % of it, and a
-// sphere whose window straddles a tile border is splatted once per tile it touches (2.07 tiles per sphere at 32 x 32, 1.75 at
-// 32 x 64).  Measured (gpurun_out/r5s64): 32x32x256 0.0733, 32x64x256 **0.0596**, 64x64x512 0.0610, 32x128x512 0.0656, 32x64x512
-// 0.0777, 64x32x512 0.0796, 64x64x256 0.0738 (three workgroups per CU), 128x32x256 0.0912.
-#ifndef PSX_ML_TX
-#define PSX_ML_TX 32
-#endif
-#ifndef PSX_ML_TY
-#define PSX_ML_TY 64
-#endif
-constexpr int MLX = PSX_ML_TX, MLY = PSX_ML_TY;   // rows (axis 0) x columns
+// Tile (rows x columns) and workgroup size of the layers kernel.  Timing experiments on the 32 x 32 x 256 form (a build-time
+// experiment, since removed; session r5s63, kernel by event pairs, 4096^2, two layers of 15 um spheres): whole kernel 0.0733 ms;
+// without the splat 0.0310; without the stores 0.0685; launch + zeroing alone 0.0142 -- the splat is 58 % of it, and a sphere
+// whose window straddles a tile border is splatted once per tile it touches (2.07 tiles per sphere at 32 x 32, 1.75 at 32 x 64).
+// Measured (session r5s64): 32x32x256 0.0733, 32x64x256 **0.0596**, 64x64x512 0.0610, 32x128x512 0.0656, 32x64x512 0.0777,
+// 64x32x512 0.0796, 64x64x256 0.0738 (three workgroups per CU), 128x32x256 0.0912.
+constexpr int MLX = 32, MLY = 64;   // rows (axis 0) x columns
 constexpr int ML_MAX = 8;        // layers per launch
-#ifndef PSX_ML_THREADS
-#define PSX_ML_THREADS 256
-#endif
-constexpr int MLT = PSX_ML_THREADS;           // threads per workgroup
+constexpr int MLT = 256;         // threads per workgroup
 constexpr int ML_SEGS = MLT / 32;             // jobs staged per round: one per half-wave
 constexpr int ML_CAP = 32;       // spheres per job and batch
 constexpr int ML_FRAC = 36;      // fractional bits of the accumulators: chords below 2^14 pixels, sums below 2^27
@@ -131,10 +116,8 @@ struct StagedSphere {
 
 // sqrt of a positive float64 from the float32 reciprocal square root and one Newton step in float64 (relative error
 // ~2e-14; the library's correctly rounded sqrt costs three times the instructions and the result is stored as float32)
-template <bool CLAMP>
 __device__ __forceinline__ double chord_sqrt(double t) {
-    const float tf = CLAMP ? fmaxf((float)t, 1e-30f) : (float)t;
-    const double y = (double)__builtin_amdgcn_rsqf(tf);
+    const double y = (double)__builtin_amdgcn_rsqf((float)t);
     const double s0 = t * y, h0 = 0.5 * y;
     const double r = fma(-s0, h0, 0.5);
     return fma(s0, r, s0);
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(MLT) void k_membrane_layers(const CellSphere *__res
     const int njobs = la.nlayers * la.rows;
     const int tx0 = t0 + margin, ty0 = c0 + margin;  // the tile on the margin-extended grid
     for (int k = tid; k < MLX * MLY; k += MLT) acc[k] = 0ull;
-    for (int j0 = 0; j0 < ((PSX_ML_OFF & 4) ? 0 : njobs); j0 += ML_SEGS) {
+    for (int j0 = 0; j0 < njobs; j0 += ML_SEGS) {
         // this half-wave's job: layer l, cell row cx0(l) + g, the spheres of cells [cy0, cy1] of that row
         const int job = j0 + seg, l = min(job / la.rows, ML_MAX - 1), g = job % la.rows;
         const int offx = la.offx[l], offy = la.offy[l];
@@ -208,7 +191,7 @@ __global__ __launch_bounds__(MLT) void k_membrane_layers(const CellSphere *__res
             }
             if (hit) flat[base + __popc(mh & ((1u << hl) - 1u))] = sp;
             __syncthreads();
-            for (int s = grp; s < ((PSX_ML_OFF & 1) ? 0 : total); s += MLT / 16) {     // (PSX_ML_OFF: timing experiments, wrong images)
+            for (int s = grp; s < total; s += MLT / 16) {
                 const StagedSphere c = flat[s];
                 // window rows clipped to the tile; columns: one per lane of the group, 16 at a time
                 const int i_lo = max(c.xi - c.radInt, tx0), i_hi = min(c.xi + c.radInt, tx0 + MLX);
@@ -218,27 +201,20 @@ __global__ __launch_bounds__(MLT) void k_membrane_layers(const CellSphere *__res
                     // getMembraneFromFile.py:157-159 takes dist = sqrt(dx^2 + dy^2), tests dist < r and adds
                     // 2 sqrt(r^2 - dist^2); comparing the squares saves one of the two square roots and moves the chord by
                     // one rounding of dist^2 (below 1e-9 of the membrane thickness, also at a sphere's rim)
-                    // Build-time A/B (tools/ab_membrane_inc.sh): PSX_MEMBRANE_SPLAT 0 = the row offset converted per row, lengths in
-                    // pixels; 1 = the row offset by repeated addition (exact: both operands sit on one grid); 2 = also every length
-                    // in the accumulator's unit of 2^-ML_FRAC pixel (powers of two: the same bits), so that the chord leaves the
+                    // The row offset advances by repeated addition (exact: both operands sit on one grid) and every length is in
+                    // the accumulator's unit of 2^-ML_FRAC pixel (powers of two: the same bits), so that the chord leaves the
                     // square root already in fixed point: doubling and rounding are one fma with an inline constant.
-#ifndef PSX_MEMBRANE_SPLAT
-#define PSX_MEMBRANE_SPLAT 2
-#endif
-                    constexpr double U = PSX_MEMBRANE_SPLAT == 2 ? (double)(1ull << ML_FRAC) : 1.0;
+                    constexpr double U = (double)(1ull << ML_FRAC);
                     const double dy = ((double)pyc - c.yf) * U;
                     const double dy2 = dy * dy;
                     const double r2 = c.r2 * (U * U);
-                    double dxr = ((double)i_lo - c.xf) * U;
-                    for (int pxr = i_lo; pxr < i_hi; ++pxr, dxr += U) {
-                        const double dx = PSX_MEMBRANE_SPLAT ? dxr : (double)pxr - c.xf;
+                    double dx = ((double)i_lo - c.xf) * U;
+                    for (int pxr = i_lo; pxr < i_hi; ++pxr, dx += U) {
                         const double d2 = fma(dx, dx, dy2);
                         if (d2 < r2) {
                             // 2 sqrt(.) in units of 2^-ML_FRAC pixel, rounded to nearest through the 2^52 + 2^51 offset
                             // (scaled: r2 - d2 > 0 is at least an ulp of r2, far above the float32 range's floor: no clamp)
-                            const double v = PSX_MEMBRANE_SPLAT == 2
-                                                 ? fma(chord_sqrt<false>(r2 - d2), 2.0, 6755399441055744.0)
-                                                 : fma(chord_sqrt<true>(r2 - d2), (double)(2ull << ML_FRAC), 6755399441055744.0);
+                            const double v = fma(chord_sqrt(r2 - d2), 2.0, 6755399441055744.0);
                             atomicAdd(&acc[(pxr - tx0) * MLY + j], (unsigned long long)(__double_as_longlong(v) - 0x4338000000000000ll));
                         }
                     }
@@ -253,7 +229,6 @@ __global__ __launch_bounds__(MLT) void k_membrane_layers(const CellSphere *__res
         if (i < dimX && j < dimY) {
             const float v = (float)((double)acc[k] * unit);
             const int64_t p = (int64_t)i * dimY + j;
-            if ((PSX_ML_OFF & 2) && v >= 0.f) continue;
             out[p] = accumulate ? out[p] + v : v;
             if (support) support[p] = support_value;
         }

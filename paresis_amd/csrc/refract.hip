@@ -37,29 +37,14 @@ struct Geo {
     static constexpr int SR = TH + 2 * H + 2, SC = TW + 2 * H + 2;   // staged phase (one more ring for the stencil)
     static constexpr int GR = TH + 2 * H, GC = TW + 2 * H;           // source pixels gathered by one tile
     // accumulator: the tile plus a one-pixel guard ring (a ray whose base pixel lies in [-1, TH-1] x [-1, TW-1] deposits
-    // its four shares at base + {0, 1, AW, AW+1} with no per-share test; the ring is never written out), then a trash
-    // area for rays that miss altogether.
-    // Two layout choices, kept as build-time switches for the A/B of VERDICT r3 item 3 (tools/ab_refract.sh):
-    //   PSX_ACC_PITCH  row pitch AW in entries: 58 -> TW + 2 (116 dwords = 52 mod 64 banks: lanes 6 or 26 apart share a bank as
-    //                  soon as their floor(dx) differ), 64 -> 128 dwords (lanes collide only in the same column of different rows)
-    //   PSX_MISS       where a ray that misses the tile adds its shares: 0 -> a slot of its own behind the accumulator
-    //                  (ACC + 2*lane; pitch 58 only: with pitch 64 the area no longer fits two workgroups per CU), 1 -> the
-    //                  bottom guard row (never read) at its lane's column, 2 -> the guard row at the column of its would-be
-    //                  target modulo the pitch (pitch 64 only)
-    // Measured (round 4, gpurun_out/r4s1; k_refract_near per 4-distance launch at 4096^2 / 16384^2): 58/0 267.5 us / 3.92 ms
-    // (round 2's layout), 58/1 266.7 / 3.91, 64/1 268.6 / 3.89, 64/2 275.3 / 4.00 (round 3's: the regression): the default
-    // is 58/1.  (Measured conflict ratios hardly differ: what is counted are same-address collisions of the scatter.)
-#ifndef PSX_ACC_PITCH
-#define PSX_ACC_PITCH 58
-#endif
-#ifndef PSX_MISS
-#define PSX_MISS 1
-#endif
-    static constexpr int AW = PSX_ACC_PITCH == 64 ? 64 : TW + 2, ACC = (TH + 2) * AW;
-    static constexpr int MISS = PSX_MISS;
-    static constexpr int TRASH = MISS == 0 ? 2 * 64 + AW + 2 : 64 + 2;
-    static_assert(AW >= TW + 2, "accumulator pitch");
-    static_assert(MISS != 2 || (AW & (AW - 1)) == 0, "target-column misses need a power-of-two pitch");
+    // its four shares at base + {0, 1, AW, AW+1} with no per-share test; the ring is never written out).  A ray that misses
+    // the tile adds its shares to the bottom guard row (never read) at its lane's column; the trash area behind the
+    // accumulator takes the shares that fall past that row.
+    // Row pitch TW + 2 and misses at the lane's column won the A/B of VERDICT r3 item 3 (round 4, session r4s1; k_refract_near
+    // per 4-distance launch at 4096^2 / 16384^2): 266.7 us / 3.91 ms, against 267.5 / 3.92 for a miss slot of its own and
+    // 268.6 / 3.89 and 275.3 / 4.00 for a 64-entry pitch.
+    static constexpr int AW = TW + 2, ACC = (TH + 2) * AW;
+    static constexpr int TRASH = 64 + 2;
     static constexpr size_t LDS = sizeof(double) * SR * SC + sizeof(float) * GR * GC + sizeof(long long) * (ACC + TRASH) + 16;
 };
 using GeoSmall = Geo<56, 56, 4, 1024>;   // 80 KiB of LDS: two workgroups per CU; 1.31 source evaluations per pixel
@@ -124,7 +109,6 @@ struct RefractArgs {
     unsigned *far_count;     // workspace: [ndist][ntiles] far rays found by each tile at each distance
     FarRay *far_list;        // then [ndist][ntiles][TH*TW] records (a tile can never overflow its slot)
     int tiles_x, tiles_y, tile_cap;
-    unsigned far_stride;          // diagnostics (psx_debug_switch "far_stride"): the replay walks the lists in a strided order
     unsigned long long *stamps;   // diagnostics (psx_debug_stamps): 16 phase timestamps per workgroup
     // order-independent far-ray replay (psx_set_deterministic; null otherwise), all inside the caller's workspace:
     unsigned *det_gmax;           // largest finite |source intensity| any tile staged (float bits; cleared by a 16-byte memset node)
@@ -365,8 +349,8 @@ __device__ __forceinline__ void refract_near_body(const RefractArgs &a) {
 
     // ---- every source pixel of tile+halo deposits what lands inside this tile.
     // Written with as few divergent branches as possible (each costs a save/restore of the exec mask): pixels outside
-    // the image carry I = 0, deposits that miss the tile (or rays that are not "near") add 0 to a per-lane trash slot,
-    // so the four LDS atomics are unconditional.
+    // the image carry I = 0, deposits that miss the tile (or rays that are not "near") go to a per-lane slot of the unread
+    // guard row, so the four LDS atomics are unconditional.
     // All distances of the call share the staged tile (the phase gradient is linear in z): the thickness maps are read
     // and the transmission evaluated ONCE per tile, then each distance runs its own deposit loop into the same
     // accumulator and writes its own image.
@@ -374,11 +358,8 @@ __device__ __forceinline__ void refract_near_body(const RefractArgs &a) {
     constexpr int ITERS = (GR * GC + NTHREADS - 1) / NTHREADS;   // uniform trip count: the loop holds wave ballots
     // Interior tiles of a distance batch: the float64 phase differences of a thread's ITERS sources are formed ONCE (16 registers)
     // and every distance scales them -- the same products bit for bit, (xp - xm) * hscale, without the four LDS reads, their
-    // address and the two float64 subtractions per source and distance (PSX_NEAR_HOIST, tools/ab_src.sh)
-#ifndef PSX_NEAR_HOIST
-#define PSX_NEAR_HOIST 1
-#endif
-    constexpr bool HOIST = PSX_NEAR_HOIST && (GR * GC) % NTHREADS == 0;
+    // address and the two float64 subtractions per source and distance
+    constexpr bool HOIST = (GR * GC) % NTHREADS == 0;
     double hgx[HOIST ? ITERS : 1], hgy[HOIST ? ITERS : 1];
     const bool hoisted = HOIST && window_inside && a.ndist > 1;      // uniform
     if constexpr (HOIST) {
@@ -396,16 +377,13 @@ __device__ __forceinline__ void refract_near_body(const RefractArgs &a) {
     }
     // ... and with a wide halo such a tile takes its distances TWO at a time: once the differences sit in registers nobody reads the
     // staged phase again, and its 34 KiB hold a second accumulator -- one barrier and one write-out phase per PAIR of distances
-    // (PSX_NEAR_PAIR; not the split call, whose sides ride in the staged phase).  A/B on one box (gpurun_out/r6s42), tiles +
-    // replay per 4-distance launch: 16384^2 halo 12 7.79 / 7.85 -> 7.54 / 7.57 ms, halo 16 8.49 -> 7.83, halo 8 8.0 -> 7.9; the
-    // narrow halos LOSE (4096^2 halo 6: tiles 0.2775 -> 0.2812 ms; 16384^2 halo 4: 10.05 -> 10.20): compiled in for halo >= 8.
-#ifndef PSX_NEAR_PAIR
-#define PSX_NEAR_PAIR 1
-#endif
+    // (not the split call, whose sides ride in the staged phase).  A/B on one box (session r6s42), tiles + replay per 4-distance
+    // launch: 16384^2 halo 12 7.79 / 7.85 -> 7.54 / 7.57 ms, halo 16 8.49 -> 7.83, halo 8 8.0 -> 7.9; the narrow halos LOSE
+    // (4096^2 halo 6: tiles 0.2775 -> 0.2812 ms; 16384^2 halo 4: 10.05 -> 10.20): halo >= 8 only.
     static_assert(sizeof(double) * SR * SC >= sizeof(long long) * (ACC + G::TRASH), "the staged phase holds a second accumulator");
     long long *const sacc2 = (long long *)sphi;
     unsigned *const sfar2 = sfar + 3;                    // (sfar, smax[0], smax[1], sfar2: the 16 bytes behind the intensity window)
-    const bool pairs = PSX_NEAR_PAIR && H >= 8 && HOIST && !SPLITC && hoisted;      // uniform
+    const bool pairs = H >= 8 && HOIST && !SPLITC && hoisted;      // uniform
     if (pairs) {
         __syncthreads();                                 // every thread holds its differences
         for (int idx = tid; idx < ACC; idx += NTHREADS) sacc2[idx] = 0ll;
@@ -454,11 +432,7 @@ __device__ __forceinline__ void refract_near_body(const RefractArgs &a) {
             // table) the compiler makes of plain loads -- it leaves volatile ones alone.  0.271 -> 0.262 ms at 4096^2 (r4s21)
             const volatile __attribute__((address_space(3))) double *vphi =
                 (const volatile __attribute__((address_space(3))) double *)sphi;
-#if defined(PSX_NEAR_EXP) && (PSX_NEAR_EXP & 2)
-            const double xp = 1e-3 * sidx, xm = 0.0, yp = -2e-3 * sidx, ym = 0.0;
-#else
             const double xp = vphi[sidx + SC], xm = vphi[sidx - SC], yp = vphi[sidx + 1], ym = vphi[sidx - 1];
-#endif
             gx = (xp - xm) * hscale;
             gy = (yp - ym) * hscale;
         } else if (inside) {                                         // image border: np.gradient(edge_order=2)
@@ -537,27 +511,17 @@ __device__ __forceinline__ void refract_near_body(const RefractArgs &a) {
         {
             const float wx = dx - fx, wy = dy - fy;                  // exact in float32
             // base target in ring coordinates (+1): the four shares land inside the accumulator iff 0 <= ti <= TH, 0 <= tj <= TW
-#ifndef PSX_NEAR_EXP
-#define PSX_NEAR_EXP 0
-#endif
-            // PSX_NEAR_EXP (tools/ab_refract4.sh, wrong images, timing only): 1 -> every ray deposits at its own pixel (no two lanes of
-            // a wave share an address or a bank), 2 -> no stencil reads (a constant displacement), 3 -> both, 4 -> two of the four atomics
-            const int ti = gr - H + ((PSX_NEAR_EXP & 1) ? 0 : ifx) + 1, tj = gc - H + ((PSX_NEAR_EXP & 1) ? 0 : ify) + 1;
+            const int ti = gr - H + ifx + 1, tj = gc - H + ify + 1;
             // ANY ray of the window whose base pixel falls in the accumulator is deposited, however long it is: the
             // share of a ray at target pixel t is gathered exactly when the source lies in the window of t's tile, and
             // k_refract_far applies the same test to decide what is left for it
             const float Is_ = I * fscale_f;                          // 2^s scaling is exact
             const bool hit = (unsigned)ti <= (unsigned)TH && (unsigned)tj <= (unsigned)TW;
-            // a miss adds its shares to the trash area; 24-bit multiply + select, not a divergent branch
+            // a miss adds its shares to the bottom guard row at its lane's column (Geo); 24-bit multiply + select, not a
+            // divergent branch
             int aidx = (int)__umul24((unsigned)ti, (unsigned)AW) + tj;
             asm volatile("" : "+v"(aidx));               // computed for every lane, then selected
-            // a miss goes to the column its target WOULD have had: the lanes of a wave then keep their distinct banks whether
-            // they hit or miss (at column = lane, the eight halo-column lanes of every row collided with hits three or four
-            // lanes away -- a two-way conflict in nearly every deposit instruction)
-            long long *acc = (dd ? sacc2 : sacc) + (hit ? aidx
-                                         : G::MISS == 0 ? ACC + 2 * lane
-                                         : G::MISS == 1 ? (TH + 1) * AW + lane
-                                                        : (TH + 1) * AW + (tj & (AW - 1)));
+            long long *acc = (dd ? sacc2 : sacc) + (hit ? aidx : (TH + 1) * AW + lane);
             // float -> fixed point with one native conversion: the unit is 2^-30 of (the power of two above) the
             // largest staged intensity, so |v|*2^s <= 2^30 fits int32; the 64-bit sum has 2^33 of headroom
             auto dep = [&](int off, float v) __attribute__((always_inline)) {
@@ -566,18 +530,12 @@ __device__ __forceinline__ void refract_near_body(const RefractArgs &a) {
                 atomicAdd((unsigned long long *)(acc + off), (unsigned long long)(long long)qi);
             };
             // Wide halos: a wave is one row of the 64-wide window, and the rows deep in the halo often hold no ray that reaches the
-            // tile -- such a wave skips its four LDS atomics and their weights (a uniform branch; build-time A/B PSX_SKIP_MISS,
-            // tools/ab_skipmiss.sh, gpurun_out/r5s32, two rounds on one box at 16384^2: halo 8 5.17 -> 5.08 ms, halo 12 6.37 -> 6.20,
-            // halo 16 8.09 -> 7.76).  Not for the narrow halos, whose few halo rows sit next to the tile and nearly always hold a hit.
-#ifndef PSX_SKIP_MISS
-#define PSX_SKIP_MISS 1
-#endif
-            if (!(PSX_SKIP_MISS && H >= 8) || __any(hit)) {
-#ifndef PSX_PK_WEIGHTS
-#define PSX_PK_WEIGHTS 1
-#endif
-            if (PSX_PK_WEIGHTS) {
-                // the same eight products, two per instruction (v_pk_mul_f32): bit for bit the scalar form's
+            // tile -- such a wave skips its four LDS atomics and their weights (a uniform branch; session r5s32, two rounds on one
+            // box at 16384^2: halo 8 5.17 -> 5.08 ms, halo 12 6.37 -> 6.20, halo 16 8.09 -> 7.76).  Not for the narrow halos, whose
+            // few halo rows sit next to the tile and nearly always hold a hit.
+            if (H < 8 || __any(hit)) {
+                // the reference's products I * (wx-part * wy-part), RF2:241-262, two per instruction (v_pk_mul_f32); regrouping
+                // them as (I * wy-part) * wx-part would save two multiplies but round differently
                 typedef float v2f __attribute__((ext_vector_type(2)));
                 const v2f ax = {1.f - wx, wx};
                 const float omy = 1.f - wy;
@@ -585,19 +543,9 @@ __device__ __forceinline__ void refract_near_body(const RefractArgs &a) {
                 const v2f s1 = (ax * (v2f){wy, wy}) * (v2f){Is_, Is_};        // {(1-wx)wy, wx wy} * I
                 dep(0, s0.x);
                 dep(AW, s0.y);
-                if (!(PSX_NEAR_EXP & 4)) {           // timing experiment: two atomics per ray (what a packed pair of 32-bit fields would issue)
-                    dep(1, s1.x);
-                    dep(AW + 1, s1.y);
-                }
-            } else {
-            dep(0, Is_ * ((1.f - wx) * (1.f - wy)));
-            dep(AW, Is_ * (wx * (1.f - wy)));
-            dep(1, Is_ * ((1.f - wx) * wy));
-            dep(AW + 1, Is_ * (wx * wy));
+                dep(1, s1.x);
+                dep(AW + 1, s1.y);
             }
-            }
-            // (kept as the reference's products I * (wx-part * wy-part), RF2:241-262: regrouping them as (I * wy-part) * wx-part
-            // would save two multiplies but round differently)
         }
         // wave-aggregated append of far rays to this tile's own list: one LDS atomic per wave, no global atomics
         // (a single global counter saturates at ~90 returning atomics per microsecond on this chip)
@@ -721,7 +669,7 @@ __device__ __forceinline__ RefractArgs one_distance_block(const RefractTab &t, i
     a.Dx_out = nullptr; a.Dy_out = nullptr; a.I_mut = nullptr;
     a.Nx = s.Nx; a.Ny = s.Ny; a.margin = s.margin; a.clamp_xf = s.clamp_xf; a.clamp_yf = s.clamp_yf;
     a.status = s.status; a.far_count = s.far_count; a.far_list = s.far_list;
-    a.tiles_x = s.tiles_x; a.tiles_y = s.tiles_y; a.tile_cap = s.tile_cap; a.far_stride = s.far_stride; a.stamps = nullptr;
+    a.tiles_x = s.tiles_x; a.tiles_y = s.tiles_y; a.tile_cap = s.tile_cap; a.stamps = nullptr;
     a.det_gmax = s.det_gmax; a.det_scale_bits = s.det_scale_bits; a.det_fold_count = s.det_fold_count; a.det_acc = s.det_acc;
     return a;
 }
@@ -786,9 +734,8 @@ template <class G, int MODE = FAR_FLOAT, bool ONE = false>      // ONE: a single
 __device__ __forceinline__ void refract_far_body(const RefractArgs &a) {
     constexpr int TH = G::TH, TW = G::TW, H = G::H;
     const unsigned nlists = (unsigned)(a.tiles_x * a.tiles_y) * (unsigned)a.ndist;
-    unsigned lst = blockIdx.x * FAR_LISTS + threadIdx.x / FAR_SUB;
+    const unsigned lst = blockIdx.x * FAR_LISTS + threadIdx.x / FAR_SUB;
     if (lst >= nlists) return;
-    if (a.far_stride) lst = (unsigned)(((unsigned long long)lst * a.far_stride) % nlists);     // stride coprime to nlists (host)
     const unsigned lane = threadIdx.x % FAR_SUB;
     const unsigned dist = ONE ? 0u : lst / (unsigned)(a.tiles_x * a.tiles_y);
     float *const I_out = a.I_out[ONE ? 0 : dist];
@@ -985,16 +932,6 @@ struct DetScratch {
     }
 };
 
-// diagnostics: a stride for the replay's walk over the lists that is coprime to their number (0: the plain tile order)
-static unsigned far_stride_for(unsigned nlists) {
-    unsigned s = (unsigned)debug_switch(DBG_FAR_STRIDE);
-    if (s == 0 || nlists < 2) return 0;
-    auto gcd = [](unsigned x, unsigned y) { while (y) { const unsigned t = x % y; x = y; y = t; } return x; };
-    s %= nlists;
-    while (s < 2 || gcd(s, nlists) != 1) ++s;
-    return s;
-}
-
 // far-ray counters and lists of a call: [ndist][ntiles] counts, then [ndist][ntiles][TH*TW] records
 template <class G>
 size_t lists_bytes(int Nx, int Ny, int ndist) {
@@ -1035,7 +972,6 @@ int launch_refract(RefractArgs &a, const float *I_in, const double *phi_in, int 
     a.tiles_x = (int)cdiv(a.Nx, G::TH);
     a.tiles_y = (int)cdiv(a.Ny, G::TW);
     a.tile_cap = G::TH * G::TW;
-    a.far_stride = far_stride_for((unsigned)(a.tiles_x * a.tiles_y * a.ndist));
     a.far_count = (unsigned *)workspace;
     a.far_list = (FarRay *)((char *)workspace + 16 * ((sizeof(unsigned) * (size_t)a.tiles_x * a.tiles_y * a.ndist + 15) / 16));
     a.det_gmax = nullptr; a.det_fold_count = nullptr; a.det_acc = nullptr; a.det_scale_bits = 0u;
@@ -1064,11 +1000,9 @@ int launch_refract(RefractArgs &a, const float *I_in, const double *phi_in, int 
             static std::atomic<unsigned long long> attr_mask{0};
             if (first_on_device(attr_mask))
                 PSX_HIP(hipFuncSetAttribute((const void *)k_refract_near<G, NM, HI, HP>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            // diagnostics (psx_debug_switch "near_lds_pad"): more LDS than the tile needs, i.e. one workgroup per CU
-            const size_t lds = std::min<size_t>(160 * 1024, G::LDS + 1024 * (size_t)std::max(0, debug_switch(DBG_NEAR_LDS_PAD)));
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
             PSX_TIMED("k_refract_near", st,
-                      k_refract_near<G, NM, HI, HP><<<a.tiles_x * a.tiles_y, G::NT, lds, st>>>(a));
+                      k_refract_near<G, NM, HI, HP><<<a.tiles_x * a.tiles_y, G::NT, G::LDS, st>>>(a));
         }
         if (int rc = launch_check("k_refract_near")) return rc;
         const int nlists = a.tiles_x * a.tiles_y * a.ndist;
@@ -1098,7 +1032,7 @@ int launch_refract_batch(RefractTab &t, int n, bool has_I, int nmat, void *works
     const size_t nt = (size_t)tiles_x * tiles_y;
     for (int e = 0; e < REFRACT_TAB; ++e) {
         RefractArgs &a = t.e[e];
-        a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tile_cap = G::TH * G::TW; a.far_stride = far_stride_for((unsigned)nt);
+        a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tile_cap = G::TH * G::TW;
         const int k = e < n ? e : 0;
         a.far_count = (unsigned *)workspace + (size_t)k * nt;
         a.far_list = (FarRay *)((char *)workspace + 16 * ((sizeof(unsigned) * nt * REFRACT_TAB + 15) / 16)) + (size_t)k * nt * a.tile_cap;

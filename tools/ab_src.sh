@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds A/B variants of ONE source file of csrc/ (SRC, default refract) as whole libraries under tools/ab/ (git-ignored .so
-# files; they travel to the GPU box).     SRC=refract tools/ab_src.sh "tag1:-DPSX_X=1" "tag2:-DPSX_Y=1 -DPSX_Z=0" ...
+# files; they travel to the GPU box).  The source gives each macro of the experiment its default (#ifndef NAME / #define NAME v);
+# fold the winner back into plain code afterwards.     SRC=refract tools/ab_src.sh "tag1:-DNAME=1" "tag2:-DNAME=2 -DOTHER=0" ...
 # On the box: tools/ab_run.sh OUTDIR tag1 tag2 ...
 set -e
 SRC=${SRC:-refract}

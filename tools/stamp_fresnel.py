@@ -10,7 +10,7 @@ import _switches                      # PSX_SWITCHES="no_p2=1 ..." -> psx_debug_
 _switches.apply()
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-ND = int(sys.argv[2]) if len(sys.argv) > 2 else 1      # with PSX_STAMP_PASS1=1: distances sharing pass 1
+ND = int(sys.argv[2]) if len(sys.argv) > 2 else 1      # with PSX_SWITCHES=stamp_pass1=1: distances sharing pass 1
 lib = _lib.lib()
 plan = ops.FresnelPlan(N, N, max_dist=ND)
 w = (torch.randn(N, N, device="cuda") + 1j * torch.randn(N, N, device="cuda")).to(torch.complex64)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from paresis_amd import _lib, ops, synth
-import _switches                      # PSX_SWITCHES="near_lds_pad=8" -> psx_debug_switch
+import _switches                      # PSX_SWITCHES="detect_4pass=1" -> psx_debug_switch
 _switches.apply()
 
 def _opt(name, default=None):

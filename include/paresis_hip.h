@@ -71,6 +71,15 @@ int psx_transmit_wave_c64(const psx_c64 *wave_in, float amp, const float *const 
 int psx_transmit_rt_f32(const float *I_in, float I0, const float *const *T, const double *cphase, const double *catt,
                         int nmat, float *I_out, const double *phi_in, double *phi_out, int64_t n, void *stream);
 
+/* ---- material fold: a stack of more than PSX_MAX_MAT maps as three (Sample.py:279, 347-348 loop over any number) ----
+ * P = sum_m cphase[m]*T[m][p] in float64 (the fma order of every consumer), A = sum_m catt[m]*T[m][p];
+ * P_hi[p] = (float)P, P_lo[p] = (float)(P - P_hi[p]), A_out[p] = (float)A.  The stack [P_hi, P_lo, A] with cphase (1, 1, 0)
+ * and catt (0, 0, 1) gives every consumer the same exponents to ~1e-14 relative: the hi/lo pair carries a phase of
+ * hundreds of radians past float32.  T: HOST array of nmat <= PSX_MAX_FOLD device pointers; one launch reads each once. */
+#define PSX_MAX_FOLD 64
+int psx_fold_materials_f32(const float *const *T, const double *cphase, const double *catt, int nmat, float *P_hi,
+                           float *P_lo, float *A_out, int64_t n, void *stream);
+
 /* acc[p] (+)= scale * img[p] * exp(sum_m catt[m]*T[m][p])  -- plate attenuation + energy accumulation
  * (Experiment.py:351-358, 478-483).  accumulate: 0 store, 1 add.  nmat may be 0. */
 int psx_accumulate_f32(float *acc, const float *img, float scale, const float *const *T, const double *catt, int nmat,
@@ -320,6 +329,29 @@ int psx_membrane_layer_f32(psx_membrane_plan *plan, int offx, int offy, int dimX
 int psx_membrane_layers_f32(psx_membrane_plan *plan, int nlayers, const int *offx, const int *offy, int dimX, int dimY,
                             int margin, int margin2, double scale, int accumulate, float *out, float *support,
                             float support_value, void *stream);
+
+/* ---- contrast phantom (Samples/generateContrastPhantom.py): 12 tubes in a solid-water support -----------------------
+ * The host derives every scalar by the generator's own expressions (paresis_amd/Samples/generateContrastPhantom.py); the
+ * kernels do the per-pixel work.  Slice m (dimY x dimY, never stored) is the indicator of tube m < 12, or of the support
+ * (m = 12): window rows [row0, row1) x cols [col0, col1) with (i - ci)^2 + (j - cj)^2 < rad2 in float64, the support
+ * minus every tube pixel.  lines[m][c] = sum over rows r (in order) of the bilinear sample of slice m at column
+ * cos*c + sin*r + off_x, row -sin*c + cos*r + off_y, zero outside the slice (skimage radon(slice, [angle]), circle=True).
+ * geom [13][dimX][dimY] float32: (float)(lines[m][c] * pix_mm * 1e-3) on rows [tube_row0, tube_row1) for a tube,
+ * [support_row0, support_row1) for the support, 0 elsewhere.  lines: DEVICE [13][dimY] float64, written. */
+#define PSX_PHANTOM_TUBES 12
+typedef struct {
+    int dimX, dimY;
+    double ci[PSX_PHANTOM_TUBES + 1], cj[PSX_PHANTOM_TUBES + 1];   /* centres (pixels); index 12: the support */
+    int row0[PSX_PHANTOM_TUBES + 1], row1[PSX_PHANTOM_TUBES + 1];  /* half-open windows of each slice */
+    int col0[PSX_PHANTOM_TUBES + 1], col1[PSX_PHANTOM_TUBES + 1];
+    double rad2[PSX_PHANTOM_TUBES + 1];                            /* squared radius (pixels^2) */
+    double cos_a, sin_a, off_x, off_y;                             /* radon's inverse map */
+    double pix_mm;
+    int tube_row0, tube_row1, support_row0, support_row1;          /* output rows (Python slice semantics, resolved) */
+} psx_phantom_desc;
+int psx_contrast_phantom_f32(const psx_phantom_desc *desc, double *lines, float *geom, void *stream);
+/* Debug/test: the 13 slices as bytes (0/1), [13][dimY][dimY] device buffer.  Small grids only. */
+int psx_contrast_phantom_slices_u8(const psx_phantom_desc *desc, uint8_t *slices, void *stream);
 
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------------------------------------
  * psx_profile_enable(1) clears the log and makes every kernel launch of the library record a HIP event pair on the

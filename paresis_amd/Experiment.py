@@ -398,12 +398,26 @@ class Experiment:
     BATCH_ENERGIES_MAX_PIXELS = 1137 * 1137        # lines of up to 1137 samples take the 2304-point transform, 8 to a round: fewer
                                                    # line groups than CUs, the case the batched library calls serve in one launch
 
-    def _batch_energies(self, N, plan):
+    def _batch_energies(self, N, plan, sim):
+        """Whether this position's energies go through the chain together.  Never for a sample that folds (a stack of the
+        chain would hold more than PSX_MAX_MAT maps, ops.MaterialStack): its fold has maps of its own for each energy, which the
+        batched calls cannot share -- an explicit exp_dict['batchEnergies'] = True takes the per-energy loop then too."""
+        if self._folds(sim):
+            return False
         flag = self.exp_dict.get('batchEnergies')
         if flag is not None:
             return bool(flag) and len(self.mySource.mySpectrum) > 1
         return (len(self.mySource.mySpectrum) > 1 and N[0] * N[1] <= self.BATCH_ENERGIES_MAX_PIXELS and
                 (plan is None or plan.engine == _lib.ENGINE_LDS))
+
+    def _folds(self, sim):
+        """True when a material stack of this chain holds more than PSX_MAX_MAT maps: air + membrane, the sample alone and
+        air + sample in both chains, membrane phase + sample in the RT chain (Experiment.py:323-349, 463-474)."""
+        n = lambda o: len(o.myMaterials) if o is not None else 0
+        na = 0 if self.exp_dict['inVacuum'] else n(self.myAirVolume)
+        nm, ns = n(self.myMembrane), n(self.mySampleofInterest)
+        sizes = [na + nm, ns, na + ns] + ([nm + ns] if sim == "RT" else [])
+        return max(sizes) > _lib.PSX_MAX_MAT
 
     def _bins_of_spectrum(self):
         """EXP:378: the energies of each detector bin, in spectrum order (a bin closes at the first energy above its
@@ -528,7 +542,7 @@ class Experiment:
         plate, air = self.myPlate, (None if ed['inVacuum'] else self.myAirVolume)
         tmp = self._tmp[0]
         dSM, dMO, dOD, M = ed['distSourceToMembrane'], ed['distMembraneToObject'], ed['distObjectToDetector'], ed['magnification']
-        if self._batch_energies(N, plan):
+        if self._batch_energies(N, plan, "Fresnel"):
             nvisited = self._fresnel_bins_batched(pointNum, stacks, accs, plan, plate, air, N, sums)
             self._zero_unvisited_bins(stacks, nvisited, pointNum)
             self._finish_mean_energy(sums, N[0] * N[1])
@@ -748,7 +762,7 @@ class Experiment:
         dMO, dOD = ed['distMembraneToObject'], ed['distObjectToDetector']
         clamp = (N[0], N[1])                                                              # RF2:61-64
         self._set_halo(N, clamp, air)
-        if not scattering and self._batch_energies(N, None):
+        if not scattering and self._batch_energies(N, None, "RT"):
             nvisited = self._rt_bins_batched(pointNum, stacks, accs, plate, air, N, sums, clamp)
             self._zero_unvisited_bins(stacks, nvisited, pointNum)
             if not ed.get('deferStatus'):

@@ -107,6 +107,10 @@ class AnalyticalSample(Sample):
             if fn == "CreateSampleSpheresInParallelepiped":                     # SAM:207-209
                 self.myGeometry, self.geom_parameters = geometry.spheres_in_parallelepiped(dimX, dimY, studyPixelSize)
                 return
+            if fn == "generateContrastPhantom":                                 # SAM:220-221, on the GPU
+                from .Samples.generateContrastPhantom import generateContrastPhantom
+                self.myGeometry, self.geom_parameters = generateContrastPhantom(dimX, dimY, studyPixelSize, angle=30)
+                return
             if fn == "loadSampleGeometryFromImages":                            # SAM:222-225
                 geom, self.geom_parameters = geometry.load_sample_geometry_from_images(self.myGeometryFolder, dimX, dimY,
                                                                                        studyPixelSize)
@@ -141,7 +145,18 @@ class AnalyticalSample(Sample):
                 raise Exception("Sample Geometry has the wrong nb of dim [material, x, y]")   # SAM:263-264
             self._dev_geometry = to_dev(g, torch.float32)
             self._dev_src = self.myGeometry
+            self.fold_cache().clear()              # the folds of the previous stack are never asked for again
         return self._dev_geometry
+
+    FOLD_CACHE_BYTES = 16 << 30  # folds of a stack of more than PSX_MAX_MAT maps (ops.MaterialStack): 3 float32 maps per
+                                 # energy and coefficient set, least recently used out first
+
+    def fold_cache(self):
+        """The folds of this sample's thickness stack, kept across membrane positions: the geometry is static."""
+        c = self.__dict__.get("_fold_cache")
+        if c is None:
+            c = self._fold_cache = ops.FoldCache(self.FOLD_CACHE_BYTES)
+        return c
 
     # --------------------------------------------------------------------------------------- coefficients
     def _coeff(self, table, energy):
@@ -163,7 +178,8 @@ class AnalyticalSample(Sample):
         """MaterialStack for a complex wave: cphase = -k delta, catt = -k beta (Sample.py:279)."""
         k = k_sample(energy)
         d, b = self._coeff(self.delta, energy), self._coeff(self.beta, energy)
-        return ops.MaterialStack(self.geometry_dev(), cphase=(-k * d if phase else 0 * d), catt=(-k * b if att else 0 * b))
+        return ops.MaterialStack(self.geometry_dev(), cphase=(-k * d if phase else 0 * d), catt=(-k * b if att else 0 * b),
+                                 fold_cache=self.fold_cache())
 
     def _df_model(self, imat):
         """(alveoli radius um, sphere volume fraction) when material `imat` scatters (Sample.py:322-344), else None.
@@ -182,12 +198,12 @@ class AnalyticalSample(Sample):
     def stack_rt(self, energy, phase=True, att=True):
         """MaterialStack for intensity + phase: cphase = -k delta, catt = -2 k beta (Sample.py:347-348).  Scattering
         materials enter with their thickness scaled by the sphere volume fraction (Sample.py:332,343), which is the same
-        as scaling their two coefficients."""
+        as scaling their two coefficients -- and so they fold (ops.MaterialStack), while dark_field() reads the raw maps."""
         k = k_sample(energy)
         d, b = self._coeff(self.delta, energy), self._coeff(self.beta, energy)
         frac = np.array([1.0 if self._df_model(i) is None else self._df_model(i)[1] for i in range(len(self.myMaterials))])
         return ops.MaterialStack(self.geometry_dev(), cphase=(-k * d * frac if phase else 0 * d),
-                                 catt=(-2 * k * b * frac if att else 0 * b))
+                                 catt=(-2 * k * b * frac if att else 0 * b), fold_cache=self.fold_cache())
 
     DF_CACHE_BYTES = 16 << 30  # width maps kept per sample: one float64 map per energy of a spectrum, least recently used out first
 

@@ -11,6 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libparesis_hip.so")
 
 PSX_MAX_MAT = 8
+PSX_MAX_FOLD = 64
+PSX_PHANTOM_TUBES = 12
 PSX_MAX_DIST = 8
 PSX_MAX_POISSON = 8
 PSX_MAX_DETECT = 4
@@ -18,7 +20,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class PsxError(RuntimeError):
@@ -38,6 +40,7 @@ PROTOTYPES = {
     "psx_clock_probe": (c_int, [POINTER(c_float), c_void_p]),
     "psx_transmit_wave_c64": (c_int, [_vp, c_float, _vpp, _dp, _dp, c_int, _vp, c_int64, _vp]),
     "psx_transmit_rt_f32": (c_int, [_vp, c_float, _vpp, _dp, _dp, c_int, _vp, _vp, _vp, c_int64, _vp]),
+    "psx_fold_materials_f32": (c_int, [_vpp, _dp, _dp, c_int, _vp, _vp, _vp, c_int64, _vp]),
     "psx_accumulate_f32": (c_int, [_vp, _vp, c_float, _vpp, _dp, c_int, c_int, c_int64, _vp]),
     "psx_accumulate_sum_f32": (c_int, [_vp, _vp, c_float, _vpp, _dp, c_int, c_int, c_int64, _vp, c_double, _vp]),
     "psx_accumulate_many_f32": (c_int, [_vp, _vpp, _fp, c_int, _vpp, _dp, c_int, c_int, c_int64, _vp, _dp, _vp]),
@@ -91,6 +94,8 @@ PROTOTYPES = {
     "psx_membrane_layer_f32": (c_int, [_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, _vp, _vp]),
     "psx_membrane_layers_f32": (c_int, [_vp, c_int, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_double, c_int,
                                         _vp, _vp, c_float, _vp]),
+    "psx_contrast_phantom_f32": (c_int, [_vp, _vp, _vp, _vp]),
+    "psx_contrast_phantom_slices_u8": (c_int, [_vp, _vp, _vp]),
     "psx_debug_stamps": (c_int, [_vp]),
     "psx_debug_switch": (c_int, [c_char_p, c_int]),
     "psx_debug_switches_active": (c_int, [ctypes.c_char_p, c_size_t]),

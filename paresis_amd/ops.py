@@ -39,9 +39,14 @@ def _need(t, dtype, name, shape=None):
 
 
 class MaterialStack:
-    """Thickness maps [nmat, Nx, Ny] float32 in HBM + per-map coefficients (see include/paresis_hip.h, "Materials")."""
+    """Thickness maps [nmat, Nx, Ny] float32 in HBM + per-map coefficients (see include/paresis_hip.h, "Materials").
 
-    def __init__(self, T, cphase=None, catt=None):
+    Any number of maps: a kernel takes at most PSX_MAX_MAT, so a stack of more is handed to it FOLDED -- psx_fold_materials_f32
+    sums the phase in float64 into a float32 hi/lo pair and the log-attenuation into one float32 map, the stack [P_hi, P_lo, A]
+    with cphase (1, 1, 0) and catt (0, 0, 1), which gives every consumer the same exponents to ~1e-14 relative.  A stack of
+    PSX_MAX_MAT maps or fewer is passed as it is.  fold_cache (a FoldCache, e.g. the sample's) keeps folds across calls."""
+
+    def __init__(self, T, cphase=None, catt=None, fold_cache=None):
         if T is None:
             self.T, self.n = None, 0
         else:
@@ -49,27 +54,36 @@ class MaterialStack:
             if T.dim() != 3:
                 raise PsxError("Sample Geometry has the wrong nb of dim [material, x, y]")   # Sample.py:263-264
             self.T, self.n = T, T.shape[0]
-        if self.n > _lib.PSX_MAX_MAT:
-            raise PsxError("at most %d materials per call, got %d" % (_lib.PSX_MAX_MAT, self.n))
         self.cphase = [0.0] * self.n if cphase is None else [float(v) for v in cphase]
         self.catt = [0.0] * self.n if catt is None else [float(v) for v in catt]
         if len(self.cphase) != self.n or len(self.catt) != self.n:
             raise PsxError("coefficient lists must have one entry per material")
+        self.fold_cache = fold_cache
+        self.folded = False           # maps of its own per coefficient set (a fold, or a concat holding one)
 
     @staticmethod
     def concat(*stacks):
-        """Materials of several objects seen by one kernel (e.g. membrane phase + sample phase, Experiment.py:469)."""
+        """Materials of several objects seen by one kernel (e.g. membrane phase + sample phase, Experiment.py:469).  When
+        they hold more than PSX_MAX_MAT maps, the stack with the most maps (the sample) is replaced by its fold, then the
+        next, until they fit."""
         stacks = [s for s in stacks if s is not None and s.n > 0]
         if not stacks:
             return MaterialStack(None)
+        while sum(s.n for s in stacks) > _lib.PSX_MAX_MAT:
+            i = max(range(len(stacks)), key=lambda j: stacks[j].n)
+            if stacks[i].n <= _FOLD_MAPS:
+                raise PsxError("%d stacks of %d maps cannot be folded to %d" % (len(stacks), sum(s.n for s in stacks),
+                                                                                 _lib.PSX_MAX_MAT))
+            stacks[i] = stacks[i].fold()
         out = MaterialStack.__new__(MaterialStack)
         out.T = None
         out.n = sum(s.n for s in stacks)
-        if out.n > _lib.PSX_MAX_MAT:
-            raise PsxError("at most %d materials per call, got %d" % (_lib.PSX_MAX_MAT, out.n))
         out.cphase = [c for s in stacks for c in s.cphase]
         out.catt = [c for s in stacks for c in s.catt]
         out._maps = [s.map(i) for s in stacks for i in range(s.n)]
+        out.fold_cache = None
+        out.folded = any(s.folded for s in stacks)
+        out._parts = stacks           # keeps the folds alive as long as the stack
         return out
 
     def map(self, i):
@@ -78,22 +92,118 @@ class MaterialStack:
         return self._maps[i]
 
     def with_coeffs(self, cphase=None, catt=None):
+        """The same maps under other coefficients.  Not for a fold or a stack holding one: its maps are [P_hi, P_lo, A] of
+        ONE coefficient set (take the raw stack's with_coeffs, then fold or concat)."""
+        if self.folded:
+            raise PsxError("with_coeffs: this stack holds a fold, whose maps belong to one coefficient set")
         out = MaterialStack.__new__(MaterialStack)
         out.T, out.n = self.T, self.n
         if self.T is None and self.n:
             out._maps = self._maps
+            out._parts = getattr(self, "_parts", None)
         out.cphase = list(self.cphase) if cphase is None else [float(v) for v in cphase]
         out.catt = list(self.catt) if catt is None else [float(v) for v in catt]
+        out.fold_cache = self.fold_cache
+        out.folded = self.folded
+        return out
+
+    def fold(self):
+        """The equivalent 3-map stack [P_hi, P_lo, A] (cphase 1, 1, 0; catt 0, 0, 1) -- from fold_cache when it holds it."""
+        key = None
+        if self.T is not None and self.fold_cache is not None:
+            key = (self.T, tuple(self.cphase), tuple(self.catt))
+            hit = self.fold_cache.get(key)
+            if hit is not None:
+                return hit
+        out = fold_materials([self.map(i) for i in range(self.n)], self.cphase, self.catt)
+        if key is not None:
+            self.fold_cache.put(key, out)
         return out
 
     def cargs(self, shape=None):
-        """(T** host array, cphase*, catt*, nmat) for the C ABI; keeps the ctypes arrays alive on self."""
+        """(T** host array, cphase*, catt*, nmat) for the C ABI; keeps the ctypes arrays alive on self.  A stack of more than
+        PSX_MAX_MAT maps passes its fold (kept on self while it lives)."""
+        if self.n > _lib.PSX_MAX_MAT:
+            self._fold = self.fold()
+            return self._fold.cargs(shape)
         maps = [self.map(i) for i in range(self.n)]
         for i, m in enumerate(maps):
             _need(m, torch.float32, "thickness map %d" % i, shape)
         self._c = ((c_void_p * max(1, self.n))(*[m.data_ptr() for m in maps]),
                    (c_double * max(1, self.n))(*self.cphase), (c_double * max(1, self.n))(*self.catt))
         return self._c[0], self._c[1], self._c[2], self.n
+
+
+_FOLD_MAPS = 3
+
+
+def fold_materials(maps, cphase, catt):
+    """psx_fold_materials_f32 over any number of float32 maps of one shape: a MaterialStack [P_hi, P_lo, A] (float32 [3, Nx,
+    Ny] in HBM) with cphase (1, 1, 0) and catt (0, 0, 1).  More than PSX_MAX_FOLD maps fold in runs, each run's fold
+    carried into the next as its first three maps (the phase pair exactly; A rounds to float32 once per run)."""
+    n = len(maps)
+    if n == 0 or len(cphase) != n or len(catt) != n:
+        raise PsxError("fold_materials: %d maps, %d phase and %d attenuation coefficients" % (n, len(cphase), len(catt)))
+    shape = tuple(maps[0].shape)
+    for i, m in enumerate(maps):
+        _need(m, torch.float32, "thickness map %d" % i, shape)
+    out = torch.empty((_FOLD_MAPS,) + shape, dtype=torch.float32, device=maps[0].device)
+    ms, cp, ca = list(maps), [float(v) for v in cphase], [float(v) for v in catt]
+    while True:
+        k = min(len(ms), _lib.PSX_MAX_FOLD)
+        check(lib().psx_fold_materials_f32((c_void_p * k)(*[m.data_ptr() for m in ms[:k]]), (c_double * k)(*cp[:k]),
+                                           (c_double * k)(*ca[:k]), k, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                           out[0].numel(), _stream()), "psx_fold_materials_f32")
+        if k == len(ms):
+            break
+        # the next run reads this run's fold in place: its output is a new buffer
+        prev, out = out, torch.empty_like(out)
+        ms = [prev[0], prev[1], prev[2]] + ms[k:]
+        cp = [1.0, 1.0, 0.0] + cp[k:]
+        ca = [0.0, 0.0, 1.0] + ca[k:]
+    st = MaterialStack(out, cphase=[1.0, 1.0, 0.0], catt=[0.0, 0.0, 1.0])
+    st.folded = True
+    return st
+
+
+class FoldCache:
+    """Folds of an object's thickness stacks, keyed by (stack tensor, cphase, catt): the stack is matched by IDENTITY (an
+    id() alone can be reused by a new tensor), the coefficients by value.  Bounded by bytes, the least recently used out
+    first (the most recent fold always stays)."""
+
+    def __init__(self, max_bytes):
+        self.max_bytes = int(max_bytes)
+        self._entries = {}            # (id(T), cphase, catt) -> (T, stack, bytes), least recently used first
+        self.nbytes = 0
+
+    def _k(self, key):
+        return (id(key[0]),) + tuple(key[1:])
+
+    def get(self, key):
+        k = self._k(key)
+        hit = self._entries.get(k)
+        if hit is None or hit[0] is not key[0]:
+            return None
+        self._entries[k] = self._entries.pop(k)
+        return hit[1]
+
+    def put(self, key, stack):
+        k = self._k(key)
+        old = self._entries.pop(k, None)
+        if old is not None:
+            self.nbytes -= old[2]
+        nb = stack.T.numel() * stack.T.element_size()
+        while self._entries and self.nbytes + nb > self.max_bytes:
+            self.nbytes -= self._entries.pop(next(iter(self._entries)))[2]
+        self._entries[k] = (key[0], stack, nb)
+        self.nbytes += nb
+
+    def clear(self):
+        self._entries.clear()
+        self.nbytes = 0
+
+    def __len__(self):
+        return len(self._entries)
 
 
 _NO_MATS = None
@@ -114,7 +224,7 @@ class MaterialBatch:
     building them (and re-checking their maps) for every membrane position: the coefficients depend on the energy only."""
 
     def __init__(self, base, cphase, catt):
-        self.base = _mats(base)
+        self.base = _unfolded(_mats(base), "MaterialBatch")
         self.cphase = [[float(v) for v in r] for r in cphase]
         self.catt = [[float(v) for v in r] for r in catt]
         if any(len(r) != self.base.n for r in self.cphase) or any(len(r) != self.base.n for r in self.catt):
@@ -124,10 +234,19 @@ class MaterialBatch:
     def rebase(self, base):
         """The same coefficients over another position's maps."""
         out = MaterialBatch.__new__(MaterialBatch)
-        out.base, out.cphase, out.catt, out.n = _mats(base), self.cphase, self.catt, self.n
+        out.base, out.cphase, out.catt, out.n = _unfolded(_mats(base), "MaterialBatch.rebase"), self.cphase, self.catt, self.n
         if out.base.n != self.n:
             raise PsxError("MaterialBatch.rebase: %d maps for %d coefficients" % (out.base.n, self.n))
         return out
+
+
+def _unfolded(m, what):
+    """m, when its maps can serve other coefficients: a stack that folds (more than PSX_MAX_MAT maps) or holds a fold has
+    maps of its own for each coefficient set, so the sources of a batch cannot share them."""
+    if m.n > _lib.PSX_MAX_MAT or m.folded:
+        raise PsxError("%s: a stack of more than %d maps folds per coefficient set; its sources cannot share maps (take one "
+                       "call per source)" % (what, _lib.PSX_MAX_MAT))
+    return m
 
 
 def _batch_mats(mats, ns, shape, what):
@@ -136,7 +255,7 @@ def _batch_mats(mats, ns, shape, what):
         if len(mats.cphase) != ns:
             raise PsxError("%s: %d coefficient rows for %d sources" % (what, len(mats.cphase), ns))
         return mats.base.cargs(shape)[0], mats.n, mats.cphase, mats.catt
-    mats = [_mats(None)] * ns if mats is None else [_mats(m) for m in mats]
+    mats = [_mats(None)] * ns if mats is None else [_unfolded(_mats(m), what) for m in mats]
     nm = mats[0].n
     T = mats[0].cargs(shape)[0]
     for m in mats[1:]:

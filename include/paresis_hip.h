@@ -46,6 +46,7 @@ extern "C" {
 
 typedef struct psx_fresnel_plan psx_fresnel_plan;
 typedef struct psx_detector_plan psx_detector_plan;
+typedef struct psx_integrate_plan psx_integrate_plan;
 
 typedef struct { float re, im; } psx_c64;
 
@@ -352,6 +353,29 @@ typedef struct {
 int psx_contrast_phantom_f32(const psx_phantom_desc *desc, double *lines, float *geom, void *stream);
 /* Debug/test: the 13 slices as bytes (0/1), [13][dimY][dimY] device buffer.  Small grids only. */
 int psx_contrast_phantom_slices_u8(const psx_phantom_desc *desc, uint8_t *slices, void *stream);
+
+/* ---- phase retrieval of speckle image stacks (no counterpart in the reference: its images' consumer) -----------------
+ * LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021) over K positions of one energy bin: per pixel,
+ *   R_k ~ x0*S_k + x1*g0_k + x2*g1_k,  (g0, g1) = np.gradient(R_k) (unit spacing, edge_order=1, float32 differences),
+ *   M = sum_k a_k a_k^T and v = sum_k a_k R_k with a_k = (S_k, g0_k, g1_k) in float64, M x = v solved in float64;
+ *   x = (1, 0, 0) exactly when det M <= 1e-12*M00*M11*M22 or the solved x0 <= 0;
+ *   transmission = 1/x0, dx = x1 (axis 0), dy = x2 (axis 1), detector pixels, the sign of the chain's Dxreal / Dyreal;
+ *   max_shift > 0 clamps dx, dy into [-max_shift, max_shift] (0: no clamp).
+ * S, R: HOST arrays of K in [3, PSX_MAX_LCS] device pointers to n x m float32 images (n, m >= 3); one launch reads each
+ * image once.  transmission, dx, dy: n x m float32, written. */
+#define PSX_MAX_LCS 64
+int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
+                float *dx, float *dy, void *stream);
+/* Frankot-Chellappa integration (IEEE PAMI 10, 1988) of the gradient field scale*(gx, gy) (rad per pixel along axis 0 / 1)
+ * with mirror extension: on the 2n x 2m grid gx is odd in axis 0 and even in axis 1, gy even in axis 0 and odd in axis 1;
+ * P = (-i kx Gx^ - i ky Gy^)/(kx^2 + ky^2), P(0) = 0, kx = 2 pi fftfreq(2n), ky = 2 pi fftfreq(2m); phi = Re ifft2(P) on
+ * the n x m corner (zero mean over the extension).  Both gradients go through ONE complex transform pair (Z = Gx + i Gy,
+ * rocFFT single precision, in place).  A plan fixes n x m and owns the 2n x 2m complex64 buffer and rocFFT's work
+ * buffer; psx_integrate_plan_bytes reports them.  gx, gy, phi: n x m float32 device images. */
+int psx_integrate_plan_create(int n, int m, psx_integrate_plan **plan);
+int psx_integrate_plan_destroy(psx_integrate_plan *plan);
+size_t psx_integrate_plan_bytes(const psx_integrate_plan *plan);
+int psx_integrate_f32(psx_integrate_plan *plan, const float *gx, const float *gy, double scale, float *phi, void *stream);
 
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------------------------------------
  * psx_profile_enable(1) clears the log and makes every kernel launch of the library record a HIP event pair on the

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libparesis_hip.so")
 
 PSX_MAX_MAT = 8
 PSX_MAX_FOLD = 64
+PSX_MAX_LCS = 64
 PSX_PHANTOM_TUBES = 12
 PSX_MAX_DIST = 8
 PSX_MAX_POISSON = 8
@@ -20,7 +21,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class PsxError(RuntimeError):
@@ -96,6 +97,11 @@ PROTOTYPES = {
                                         _vp, _vp, c_float, _vp]),
     "psx_contrast_phantom_f32": (c_int, [_vp, _vp, _vp, _vp]),
     "psx_contrast_phantom_slices_u8": (c_int, [_vp, _vp, _vp]),
+    "psx_lcs_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp]),
+    "psx_integrate_plan_create": (c_int, [c_int, c_int, _vpp]),
+    "psx_integrate_plan_destroy": (c_int, [_vp]),
+    "psx_integrate_plan_bytes": (c_size_t, [_vp]),
+    "psx_integrate_f32": (c_int, [_vp, _vp, _vp, c_double, _vp, _vp]),
     "psx_debug_stamps": (c_int, [_vp]),
     "psx_debug_switch": (c_int, [c_char_p, c_int]),
     "psx_debug_switches_active": (c_int, [ctypes.c_char_p, c_size_t]),

@@ -1,0 +1,256 @@
+// retrieve.hip -- speckle-tracking phase retrieval of simulated image stacks: LCS (psx_lcs_f32) and Frankot-Chellappa
+// integration (psx_integrate_*).
+//
+// LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021), per detector pixel, over K positions:
+//   R_k ~ x0*S_k + x1*g0_k + x2*g1_k,   (g0, g1) = np.gradient(R_k) (unit spacing, edge_order=1),
+//   M = sum_k a_k a_k^T, v = sum_k a_k R_k with a_k = (S_k, g0_k, g1_k), in float64;  M x = v;
+//   transmission = 1/x0, (dx, dy) = (x1, x2);  x = (1, 0, 0) when det M <= 1e-12 M00 M11 M22 or x0 <= 0.
+// k_lcs: one thread per pixel, all K positions in one launch; the gradient's neighbours come from L1/L2 (the rows above
+// and below are the neighbouring wavefronts' own rows), so HBM sees every input image about once.
+//
+// Frankot-Chellappa (IEEE PAMI 10, 1988) with mirror extension, 2n x 2m complex64 grid:
+//   k_integ_pack    Z = s*(Gx + i*Gy), Gx odd in axis 0 / even in axis 1, Gy even / odd: both gradients, one transform
+//   rocFFT forward, in place
+//   k_integ_filter  Gx^(k) = (Z(k) + conj Z(-k))/2, Gy^(k) = (Z(k) - conj Z(-k))/(2i),
+//                   P = (-i kx Gx^ - i ky Gy^)/(kx^2 + ky^2), P(0) = 0; one thread owns the pair (k, -k)
+//   rocFFT inverse, in place
+//   k_integ_crop    phi = Re(.)/(4nm) on the n x m corner
+#include "fresnel_plan.hpp"
+
+using namespace psx;
+
+namespace {
+
+struct LcsPtrs {
+    const float *S[PSX_MAX_LCS];
+    const float *R[PSX_MAX_LCS];
+};
+
+constexpr int LCS_BX = 64, LCS_BY = 4;
+
+// one thread per pixel (i, j) of the n x m images; no barrier, so out-of-range threads leave at once
+__global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs(LcsPtrs p, int K, int n, int m, float max_shift,
+                                                         float *__restrict__ trans, float *__restrict__ dx,
+                                                         float *__restrict__ dy) {
+    const int j = blockIdx.x * LCS_BX + threadIdx.x;
+    const int i = blockIdx.y * LCS_BY + threadIdx.y;
+    if (i >= n || j >= m) return;
+    // np.gradient, edge_order=1: central differences inside, one-sided first differences on the border (n, m >= 3)
+    const int ip = i + 1 < n ? i + 1 : n - 1, im = i > 0 ? i - 1 : 0;
+    const int jp = j + 1 < m ? j + 1 : m - 1, jm = j > 0 ? j - 1 : 0;
+    const float h0 = ip - im == 2 ? 0.5f : 1.0f, h1 = jp - jm == 2 ? 0.5f : 1.0f;
+    const int64_t c = (int64_t)i * m + j;
+    const int64_t up = (int64_t)ip * m + j, dn = (int64_t)im * m + j;
+    const int64_t rt = (int64_t)i * m + jp, lt = (int64_t)i * m + jm;
+    double m00 = 0.0, m01 = 0.0, m02 = 0.0, m11 = 0.0, m12 = 0.0, m22 = 0.0, v0 = 0.0, v1 = 0.0, v2 = 0.0;
+#pragma unroll 2
+    for (int k = 0; k < K; ++k) {
+        const float *R = p.R[k];
+        const float s = p.S[k][c], r = R[c], ru = R[up], rd = R[dn], rr = R[rt], rl = R[lt];
+        const double a0 = s, a1 = (ru - rd) * h0, a2 = (rr - rl) * h1, b = r;   // float32 differences, as numpy forms them
+        m00 = fma(a0, a0, m00);
+        m01 = fma(a0, a1, m01);
+        m02 = fma(a0, a2, m02);
+        m11 = fma(a1, a1, m11);
+        m12 = fma(a1, a2, m12);
+        m22 = fma(a2, a2, m22);
+        v0 = fma(a0, b, v0);
+        v1 = fma(a1, b, v1);
+        v2 = fma(a2, b, v2);
+    }
+    // cofactors of the symmetric M; det by the first row
+    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const double det = m00 * c00 + m01 * c01 + m02 * c02;
+    float t = 1.0f, x = 0.0f, y = 0.0f;
+    if (!(det <= 1e-12 * m00 * m11 * m22)) {
+        const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+        const double inv = 1.0 / det;
+        const double x0 = (c00 * v0 + c01 * v1 + c02 * v2) * inv;
+        if (x0 > 0.0) {
+            t = (float)(1.0 / x0);
+            x = (float)((c01 * v0 + c11 * v1 + c12 * v2) * inv);
+            y = (float)((c02 * v0 + c12 * v1 + c22 * v2) * inv);
+        }
+    }
+    if (max_shift > 0.0f) {
+        x = fminf(fmaxf(x, -max_shift), max_shift);
+        y = fminf(fmaxf(y, -max_shift), max_shift);
+    }
+    trans[c] = t;
+    dx[c] = x;
+    dy[c] = y;
+}
+
+// Z[a][b] on the 2n x 2m extension: Gx = +-gx (minus on the mirrored rows), Gy = +-gy (minus on the mirrored columns)
+__global__ __launch_bounds__(256) void k_integ_pack(const float *__restrict__ gx, const float *__restrict__ gy, double scale,
+                                                    float2 *__restrict__ Z, int n, int m) {
+    const int64_t W = 2 * (int64_t)m, N = 2 * (int64_t)n * W;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < N; q += (int64_t)gridDim.x * blockDim.x) {
+        const int a = (int)(q / W), b = (int)(q - (int64_t)a * W);
+        const bool ra = a >= n, rb = b >= m;
+        const int64_t src = (int64_t)(ra ? 2 * n - 1 - a : a) * m + (rb ? 2 * m - 1 - b : b);
+        const double x = scale * (double)gx[src], y = scale * (double)gy[src];
+        Z[q] = make_float2((float)(ra ? -x : x), (float)(rb ? -y : y));
+    }
+}
+
+// P(k) from Z(k) and Z(-k) at the angular frequency (kx, ky)
+__device__ __forceinline__ float2 fc_filter(float2 zk, float2 zm, double kx, double ky) {
+    // Gx^ = (zk + conj zm)/2;  Gy^ = (zk - conj zm)/(2i) = (-i)(zk - conj zm)/2
+    const float gxr = 0.5f * (zk.x + zm.x), gxi = 0.5f * (zk.y - zm.y);
+    const float dr = zk.x - zm.x, di = zk.y + zm.y;
+    const float gyr = 0.5f * di, gyi = -0.5f * dr;
+    const double den = kx * kx + ky * ky;
+    const float fx = (float)(kx / den), fy = (float)(ky / den);
+    // -i*(fx*Gx^ + fy*Gy^)
+    const float sr = fx * gxr + fy * gyr, si = fx * gxi + fy * gyi;
+    return make_float2(si, -sr);
+}
+
+__global__ __launch_bounds__(256) void k_integ_filter(float2 *__restrict__ Z, int n, int m) {
+    const int H = 2 * n, W = 2 * m;
+    const int64_t N = (int64_t)H * W;
+    const double wx = PSX_TWO_PI / (double)H, wy = PSX_TWO_PI / (double)W;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < N; q += (int64_t)gridDim.x * blockDim.x) {
+        const int a = (int)(q / W), b = (int)(q - (int64_t)a * W);
+        const int a2 = a ? H - a : 0, b2 = b ? W - b : 0;
+        const int64_t q2 = (int64_t)a2 * W + b2;
+        if (q2 < q) continue;   // the pair belongs to the thread of its smaller index
+        // np.fft.fftfreq: index f < H/2 -> f, else f - H (the Nyquist row is -H/2)
+        const double kx = wx * (a < n ? a : a - H), ky = wy * (b < m ? b : b - W);
+        const double kx2 = wx * (a2 < n ? a2 : a2 - H), ky2 = wy * (b2 < m ? b2 : b2 - W);
+        const float2 z1 = Z[q], z2 = Z[q2];
+        const float2 p1 = q == 0 ? make_float2(0.f, 0.f) : fc_filter(z1, z2, kx, ky);
+        if (q2 != q) Z[q2] = fc_filter(z2, z1, kx2, ky2);
+        Z[q] = p1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_integ_crop(const float2 *__restrict__ Z, float *__restrict__ phi, int n, int m,
+                                                    float norm) {
+    const int64_t N = (int64_t)n * m;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (int64_t)gridDim.x * blockDim.x) {
+        const int i = (int)(p / m), j = (int)(p - (int64_t)i * m);
+        phi[p] = Z[(int64_t)i * 2 * m + j].x * norm;
+    }
+}
+
+}  // namespace
+
+struct psx_integrate_plan {
+    int n, m;
+    size_t bytes;
+    rocfft_plan fwd, inv;
+    rocfft_execution_info info;
+    void *work;
+    float2 *Z;   // [2n][2m]
+};
+
+namespace {
+
+void integrate_plan_free(psx_integrate_plan *p) {
+    if (p->fwd) rocfft_plan_destroy(p->fwd);
+    if (p->inv) rocfft_plan_destroy(p->inv);
+    if (p->info) rocfft_execution_info_destroy(p->info);
+    (void)hipFree(p->work);
+    (void)hipFree(p->Z);
+    delete p;
+}
+
+int integrate_plan_init(psx_integrate_plan *p) {
+    if (int rc = rocfft_ensure_setup()) return rc;
+    const size_t lengths[2] = {2 * (size_t)p->m, 2 * (size_t)p->n};   // fastest first
+    PSX_ROCFFT(rocfft_plan_create(&p->fwd, rocfft_placement_inplace, rocfft_transform_type_complex_forward,
+                                  rocfft_precision_single, 2, lengths, 1, nullptr));
+    PSX_ROCFFT(rocfft_plan_create(&p->inv, rocfft_placement_inplace, rocfft_transform_type_complex_inverse,
+                                  rocfft_precision_single, 2, lengths, 1, nullptr));
+    size_t wf = 0, wi = 0;
+    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(p->fwd, &wf));
+    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(p->inv, &wi));
+    const size_t work = wf > wi ? wf : wi;
+    PSX_ROCFFT(rocfft_execution_info_create(&p->info));
+    if (work) {
+        PSX_HIP(hipMalloc(&p->work, work));
+        PSX_ROCFFT(rocfft_execution_info_set_work_buffer(p->info, p->work, work));
+    }
+    const size_t img = sizeof(float2) * 4 * (size_t)p->n * (size_t)p->m;
+    PSX_HIP(hipMalloc((void **)&p->Z, img));
+    p->bytes = img + work;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
+                float *dx, float *dy, void *stream) {
+    PSX_REQUIRE(K >= 3 && K <= PSX_MAX_LCS, "psx_lcs_f32: K=%d positions outside [3,%d]", K, PSX_MAX_LCS);
+    PSX_REQUIRE(n >= 3 && m >= 3, "psx_lcs_f32: images %dx%d smaller than 3x3", n, m);
+    PSX_REQUIRE(S != nullptr && R != nullptr, "psx_lcs_f32: null pointer array");
+    PSX_REQUIRE(transmission && dx && dy, "psx_lcs_f32: null output map");
+    PSX_REQUIRE(max_shift >= 0.0f, "psx_lcs_f32: max_shift=%g < 0", (double)max_shift);
+    LcsPtrs p;
+    for (int k = 0; k < PSX_MAX_LCS; ++k) {
+        p.S[k] = nullptr;
+        p.R[k] = nullptr;
+    }
+    for (int k = 0; k < K; ++k) {
+        PSX_REQUIRE(S[k] != nullptr && R[k] != nullptr, "psx_lcs_f32: position %d has a null image", k);
+        p.S[k] = S[k];
+        p.R[k] = R[k];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)cdiv(m, LCS_BX), (unsigned)cdiv(n, LCS_BY)), block(LCS_BX, LCS_BY);
+    PSX_TIMED("k_lcs", st, k_lcs<<<grid, block, 0, st>>>(p, K, n, m, max_shift, transmission, dx, dy));
+    return launch_check("k_lcs");
+}
+
+int psx_integrate_plan_create(int n, int m, psx_integrate_plan **plan) {
+    PSX_REQUIRE(plan != nullptr, "psx_integrate_plan_create: null plan pointer");
+    *plan = nullptr;
+    PSX_REQUIRE(n >= 2 && m >= 2, "psx_integrate_plan_create: grid %dx%d too small", n, m);
+    PSX_REQUIRE((int64_t)n * m <= (int64_t)1 << 28, "psx_integrate_plan_create: grid %dx%d too large", n, m);
+    psx_integrate_plan *p = new psx_integrate_plan();
+    p->n = n; p->m = m; p->bytes = 0; p->fwd = nullptr; p->inv = nullptr; p->info = nullptr; p->work = nullptr; p->Z = nullptr;
+    if (int rc = integrate_plan_init(p)) {
+        integrate_plan_free(p);
+        return rc;
+    }
+    *plan = p;
+    return 0;
+}
+
+int psx_integrate_plan_destroy(psx_integrate_plan *plan) {
+    if (plan) integrate_plan_free(plan);
+    return 0;
+}
+
+size_t psx_integrate_plan_bytes(const psx_integrate_plan *plan) { return plan ? plan->bytes : 0; }
+
+int psx_integrate_f32(psx_integrate_plan *plan, const float *gx, const float *gy, double scale, float *phi, void *stream) {
+    PSX_REQUIRE(plan != nullptr, "psx_integrate_f32: null plan");
+    PSX_REQUIRE(gx && gy && phi, "psx_integrate_f32: null image");
+    hipStream_t st = (hipStream_t)stream;
+    const int n = plan->n, m = plan->m;
+    const int64_t N = 4 * (int64_t)n * m;
+    PSX_TIMED("k_integ_pack", st, k_integ_pack<<<ew_grid(N, 256), 256, 0, st>>>(gx, gy, scale, plan->Z, n, m));
+    if (int rc = launch_check("k_integ_pack")) return rc;
+    PSX_ROCFFT(rocfft_execution_info_set_stream(plan->info, st));
+    void *buf[1] = {plan->Z};
+    {
+        ProfScope ps("rocfft_integrate_forward", st);
+        PSX_ROCFFT(rocfft_execute(plan->fwd, buf, nullptr, plan->info));
+    }
+    PSX_TIMED("k_integ_filter", st, k_integ_filter<<<ew_grid(N, 256), 256, 0, st>>>(plan->Z, n, m));
+    if (int rc = launch_check("k_integ_filter")) return rc;
+    {
+        ProfScope ps("rocfft_integrate_inverse", st);
+        PSX_ROCFFT(rocfft_execute(plan->inv, buf, nullptr, plan->info));
+    }
+    const float norm = (float)(1.0 / (double)N);
+    PSX_TIMED("k_integ_crop", st, k_integ_crop<<<ew_grid((int64_t)n * m, 256), 256, 0, st>>>(plan->Z, phi, n, m, norm));
+    return launch_check("k_integ_crop");
+}
+
+}  // extern "C"

@@ -3,10 +3,13 @@
 
     python -m paresis_amd.main [--experiment NAME] [--type RayT|Fresnel] [--oversampling N] [--points N]
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
+                               [--retrieve [--max-shift S]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
-has its own seed.
+has its own seed.  --retrieve (needs 3 positions or more) runs the speckle-tracking phase retrieval of each bin on rank 0
+after the gather (paresis_amd/retrieval.py) and writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under the bin's
+directory.
 """
 import argparse
 import datetime
@@ -16,8 +19,14 @@ import time
 import numpy as np
 
 
-def run(exp_dict, save=True, saving_format=".tif", backend=None):
-    """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors."""
+def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None):
+    """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
+
+    retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
+    (retrieval.retrieve with the experiment's parameters, max_shift its clamp); with save, the maps go to
+    <bin dir>/retrieval/.  exp_dict['retrievalParams'] then holds the parameters it used."""
+    if retrieve and int(exp_dict['nbExpPoints']) < 3:
+        raise ValueError("--retrieve needs at least 3 membrane positions, got %d" % int(exp_dict['nbExpPoints']))
     from . import dist
     from .Experiment import Experiment
     from .InputOutput.pagailleIO import save_image
@@ -125,6 +134,14 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None):
                     save_image(gathered[0][2][ibin], paths[ibin] + 'propag/PropagImage_' + str(exp_dict['expID']) + '_' + saving_format)
                     save_image(gathered[0][3][ibin], paths[ibin] + 'White_' + str(exp_dict['expID']) + '_' + saving_format)
         experiment.saveAllParameters(time0, exp_dict)
+    if rank == 0 and retrieve:
+        from . import retrieval
+        params = retrieval.params_from_experiment(experiment)
+        retrieved = retrieval.retrieve(gathered, params, max_shift=max_shift)
+        exp_dict['retrievalParams'] = params
+        if save:
+            for ibin in sorted(retrieved):
+                retrieval.save_retrieval(retrieved[ibin], paths[ibin], exp_dict['expID'], saving_format)
     dist.finish()
     print("\nfini")
     return gathered
@@ -148,6 +165,10 @@ def main(argv=None):
     ap.add_argument("--backend", default=None, choices=[None, "nccl", "gloo"],
                     help="torch.distributed backend under torchrun (default: nccl = RCCL on a GPU node; gloo rehearses several "
                          "ranks on one GPU)")
+    ap.add_argument("--retrieve", action="store_true",
+                    help="speckle-tracking phase retrieval of every bin after the run (3 positions or more): "
+                         "retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory")
+    ap.add_argument("--max-shift", type=float, default=None, help="--retrieve: clamp of the displacements, in pixels")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -155,7 +176,9 @@ def main(argv=None):
     if a.xml:
         exp_dict['xmlDir'] = a.xml
     os.makedirs(exp_dict['filepath'], exist_ok=True)
-    run(exp_dict, save=True, saving_format=a.format, backend=a.backend)
+    if a.retrieve and a.points < 3:
+        ap.error("--retrieve needs --points 3 or more")
+    run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift)
 
 
 if __name__ == "__main__":

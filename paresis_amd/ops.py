@@ -945,3 +945,105 @@ def status_scan(img):
     _need(img, torch.float32, "img")
     check(lib().psx_status_scan_f32(_ptr(img), img.numel(), _ptr(status_word(img.device)), _stream()),
           "psx_status_scan_f32")
+
+
+def _positions(imgs, name):
+    """The K images of one side of an LCS call as a list of 2-D tensors: a [K, n, m] tensor, or a sequence of K 2-D tensors
+    (e.g. the bin slices S[ibin] of the chains' [nbins, n, m] stacks).  Counts and shapes only: devices come after both
+    sides are known, so that the message names the first thing that is wrong."""
+    if isinstance(imgs, torch.Tensor):
+        if imgs.dim() != 3:
+            raise PsxError("%s must be [K, n, m] or a sequence of K [n, m] images; got shape %s" % (name, tuple(imgs.shape)))
+        imgs = [imgs[k] for k in range(imgs.shape[0])]
+    imgs = list(imgs)
+    K = len(imgs)
+    if K < 3 or K > _lib.PSX_MAX_LCS:
+        raise PsxError("%s: K=%d positions outside [3, %d]" % (name, K, _lib.PSX_MAX_LCS))
+    for k, t in enumerate(imgs):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise PsxError("%s[%d] must be a 2-D tensor" % (name, k))
+        if tuple(t.shape) != tuple(imgs[0].shape):
+            raise PsxError("%s[%d] has shape %s, %s[0] %s" % (name, k, tuple(t.shape), name, tuple(imgs[0].shape)))
+    return imgs
+
+
+def lcs(sample, reference, max_shift=None, out=None):
+    """LCS speckle tracking of one energy bin (psx_lcs_f32): K in [3, PSX_MAX_LCS] sample / reference pairs of n x m float32
+    images in HBM -> (transmission, dx, dy), n x m float32.  dx is the displacement along axis 0, dy along axis 1, in pixels,
+    with the sign of the chain's Dxreal / Dyreal.  max_shift (pixels, > 0) clamps dx and dy; None: no clamp.  out: three
+    caller-owned n x m float32 tensors (transmission, dx, dy) to write into."""
+    S = _positions(sample, "sample")
+    R = _positions(reference, "reference")
+    if len(S) != len(R):
+        raise PsxError("sample has %d positions, reference %d" % (len(S), len(R)))
+    shape = tuple(S[0].shape)
+    if tuple(R[0].shape) != shape:
+        raise PsxError("reference images have shape %s, sample images %s" % (tuple(R[0].shape), shape))
+    if shape[0] < 3 or shape[1] < 3:
+        raise PsxError("images %dx%d smaller than 3x3" % shape)
+    dev = S[0].device
+    for nm, imgs in (("sample", S), ("reference", R)):
+        for k, t in enumerate(imgs):
+            _need(t, torch.float32, "%s[%d]" % (nm, k))
+            if t.device != dev:
+                raise PsxError("%s[%d] is on %s, sample[0] on %s" % (nm, k, t.device, dev))
+    ms = 0.0 if max_shift is None else float(max_shift)
+    if max_shift is not None and not ms > 0.0:
+        raise PsxError("max_shift must be > 0 pixels (None: no clamp), got %r" % (max_shift,))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3))
+    else:
+        out = tuple(out)
+        if len(out) != 3:
+            raise PsxError("out must hold three tensors (transmission, dx, dy)")
+        for nm, t in zip(("transmission", "dx", "dy"), out):
+            _need(t, torch.float32, "out " + nm, shape)
+            if t.device != dev:
+                raise PsxError("out %s is on %s, the images on %s" % (nm, t.device, dev))
+    K = len(S)
+    with torch.cuda.device(dev):
+        check(lib().psx_lcs_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K, shape[0], shape[1], c_float(ms),
+                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), "psx_lcs_f32")
+    return out
+
+
+class IntegratePlan:
+    """psx_integrate_plan for one n x m grid: Frankot-Chellappa integration of a gradient field with mirror extension
+    (rocFFT on the 2n x 2m complex64 grid the plan owns; `bytes` reports it with rocFFT's work buffer)."""
+
+    def __init__(self, n, m, device=None):
+        self.n, self.m = int(n), int(m)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = c_void_p(None)
+        with torch.cuda.device(self.device):
+            check(lib().psx_integrate_plan_create(self.n, self.m, ctypes.byref(self._h)), "psx_integrate_plan_create")
+        self.bytes = lib().psx_integrate_plan_bytes(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().psx_integrate_plan_destroy(self._h)
+            self._h = c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def integrate(self, gx, gy, scale=1.0, out=None):
+        """phi (n x m float32, radians, zero mean over the extension) whose gradient is scale*(gx, gy), in radians per pixel
+        along axis 0 / axis 1.  Calls on one plan are ordered on the current stream (they share its buffer)."""
+        shape = (self.n, self.m)
+        _need(gx, torch.float32, "gx", shape)
+        _need(gy, torch.float32, "gy", shape)
+        for nm, t in (("gx", gx), ("gy", gy)):
+            if t.device != self.device:
+                raise PsxError("%s is on %s, the plan on %s" % (nm, t.device, self.device))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            _need(out, torch.float32, "out", shape)
+        with torch.cuda.device(self.device):
+            check(lib().psx_integrate_f32(self._h, _ptr(gx), _ptr(gy), c_double(scale), _ptr(out), _stream()),
+                  "psx_integrate_f32")
+        return out

@@ -1,0 +1,223 @@
+"""Speckle-tracking phase retrieval of the simulated image stacks, on the GPU.
+
+A speckle-based run gives, per energy bin, K membrane positions of a sample image S_k and a reference image R_k.  This
+module turns them into the sample's transmission, its refraction (displacement) and its phase:
+
+    lcs(sample, reference)   LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021): per pixel, the float64
+                             least-squares solution of  R_k ~ x0*S_k + x1*dR_k/d0 + x2*dR_k/d1  over the K positions,
+                             the first-order form of S(r) = T*R(r - D): transmission = 1/x0, (dx, dy) = (x1, x2) in
+                             detector pixels, along axis 0 / axis 1, with the sign of the chain's Dxreal / Dyreal
+    phase_gradient(...)      displacement -> phase gradient in radians per detector pixel
+    integrate(gx, gy)        Frankot-Chellappa (IEEE PAMI 10, 1988) with mirror extension -> phase (zero mean)
+    retrieve(results, ...)   all of it for every bin of main.run's {position: (Sample, Reference, ...)}
+
+Both steps are HIP kernels (csrc/retrieve.hip; the integration's transforms are rocFFT); nothing runs on the host but
+argument checks.  Command line, for a run already on disk (main.py's layout):
+
+    python -m paresis_amd.retrieval RUN_DIR [--energy KEV --pixel-um P --distance Z --magnification M]
+                                            [--max-shift S] [--format .tif]
+
+writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory; without the four physical parameters
+only transmission, dx and dy.
+"""
+import argparse
+import os
+import re
+import sys
+
+import numpy as np
+
+from .getk import getk
+
+_plans = {}
+
+
+def lcs(sample, reference, max_shift=None):
+    """K >= 3 sample / reference images of one bin ([K, n, m] float32 CUDA tensors, or sequences of K n x m ones) ->
+    {'transmission', 'dx', 'dy'}, n x m float32 on the same device.  max_shift (pixels): clamp dx, dy; None: no clamp."""
+    from . import ops
+    t, dx, dy = ops.lcs(sample, reference, max_shift=max_shift)
+    return {'transmission': t, 'dx': dx, 'dy': dy}
+
+
+def _plan(device, n, m):
+    import torch
+    from . import ops
+    dev = torch.device(device)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(n), int(m))
+    p = _plans.get(key)
+    if p is None:
+        p = _plans[key] = ops.IntegratePlan(n, m, device=torch.device("cuda", key[0]))
+    return p
+
+
+def integrate(gx, gy, scale=1.0, out=None):
+    """Frankot-Chellappa integration of the gradient field scale*(gx, gy) (n x m float32 CUDA tensors, radians per pixel along
+    axis 0 / axis 1) with mirror extension -> phi, n x m float32, zero mean over the 2n x 2m extension.  One plan per
+    (device, shape) is kept for the process's lifetime."""
+    return _plan(gx.device, gx.shape[0], gx.shape[1]).integrate(gx, gy, scale=scale, out=out)
+
+
+def gradient_scale(energy_keV, pixel_um, distance_m, magnification):
+    """Radians per detector pixel of phase gradient per detector pixel of displacement: k*p^2/(M*z).
+
+    The ray-tracing chain displaces by D = dphi/di * z/(k*h^2*M) study pixels (refractionFileNumba2.py:54-56, gradient per
+    study pixel of size h = p/(ov*M), M the object->detector magnification the chain passes, EXP:473-474), and the detector
+    bins ov x ov study pixels into one.  A phase slope s per detector pixel is s/ov per study pixel, so
+    D = (s/ov)*z/(k*h^2*M) study pixels = (s/ov^2)*z/(k*h^2*M) detector pixels = s*z*M/(k*p^2), i.e. s = D*k*p^2/(M*z);
+    ov drops out.  k = getk(E), the chain's own constants."""
+    p = float(pixel_um) * 1e-6
+    return getk(float(energy_keV) * 1e3) * p * p / (float(magnification) * float(distance_m))
+
+
+def phase_gradient(dx, dy, energy_keV, pixel_um, distance_m, magnification):
+    """(gx, gy) = (dx, dy) * k*p^2/(M*z): displacements in detector pixels -> phase gradient in radians per detector pixel
+    (see gradient_scale).  energy_keV: the photon energy; pixel_um: the detector pixel; distance_m: distObjectToDetector;
+    magnification: exp_dict['magnification'].  Tensors or numpy arrays."""
+    c = gradient_scale(energy_keV, pixel_um, distance_m, magnification)
+    return dx * c, dy * c
+
+
+def params_from_experiment(experiment):
+    """The physical parameters of an Experiment's retrieval: {'energy_keV': exp_dict['meanEnergy'] (known after a run),
+    'pixel_um': the detector pixel, 'distance_m': distObjectToDetector, 'magnification': exp_dict['magnification']}."""
+    ed = experiment.exp_dict
+    return {'energy_keV': float(ed['meanEnergy']), 'pixel_um': float(experiment.myDetector.det_param['myPixelSize']),
+            'distance_m': float(ed['distObjectToDetector']), 'magnification': float(ed['magnification'])}
+
+
+def _stack(results, positions, slot, device):
+    import torch
+    imgs = [results[p][slot] for p in positions]
+    if all(isinstance(t, torch.Tensor) and t.is_cuda for t in imgs):
+        return [t.to(device=device, dtype=torch.float32).contiguous() for t in imgs]
+    host = np.stack([np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32) for t in imgs])
+    dev = torch.from_numpy(host).to(device)                         # one upload: [K, nbins, n, m]
+    return [dev[k] for k in range(dev.shape[0])]
+
+
+def retrieve(results, params=None, bins=None, energies=None, max_shift=None, device=None):
+    """Retrieve every bin of a run: results = main.run's {position: (Sample, Reference, ...)} with [nbins, n, m] stacks (host or
+    device; host stacks are uploaded once) -> {bin: {'transmission', 'dx', 'dy', 'phi'}}, device tensors.
+
+    params: {'energy_keV', 'pixel_um', 'distance_m', 'magnification'} (params_from_experiment); None: no phase ('phi' left
+    out).  bins: the bins to retrieve (default all).  energies: one energy (keV) per bin of `bins`; without it every bin uses
+    params['energy_keV'] -- the run's mean detected energy, which is right for one bin only: a multi-bin run should pass
+    each bin's own energy.  max_shift: clamp of dx, dy in pixels (None: no clamp)."""
+    import torch
+    positions = sorted(results)
+    if len(positions) < 3:
+        raise ValueError("phase retrieval needs at least 3 positions, got %d" % len(positions))
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    S = _stack(results, positions, 0, dev)
+    R = _stack(results, positions, 1, dev)
+    nbins = S[0].shape[0]
+    bins = list(range(nbins)) if bins is None else [int(b) for b in bins]
+    if energies is not None and len(energies) != len(bins):
+        raise ValueError("energies must hold one value per retrieved bin (%d), got %d" % (len(bins), len(energies)))
+    out = {}
+    for i, b in enumerate(bins):
+        r = lcs([s[b] for s in S], [s[b] for s in R], max_shift=max_shift)
+        if params is not None:
+            e = params['energy_keV'] if energies is None else energies[i]
+            r['phi'] = integrate(r['dx'], r['dy'],
+                                 scale=gradient_scale(e, params['pixel_um'], params['distance_m'], params['magnification']))
+        out[b] = r
+    return out
+
+
+def save_retrieval(r, directory, exp_id, fmt):
+    """Write one bin's maps as directory/retrieval/<name>_<exp_id><fmt> (name: transmission, dx, dy[, phi])."""
+    from .InputOutput.pagailleIO import save_image
+    d = os.path.join(directory, "retrieval")
+    os.makedirs(d, exist_ok=True)
+    paths = []
+    for name in ("transmission", "dx", "dy", "phi"):
+        if name in r:
+            paths.append(os.path.join(d, "%s_%s%s" % (name, exp_id, fmt)))
+            save_image(r[name].detach().cpu().numpy(), paths[-1])
+    return paths
+
+
+_SAMPLE = re.compile(r"^sampleImage_(.+)_(\d+)(\.[A-Za-z0-9]+)$")
+_REF = re.compile(r"^ReferenceImage_(.+)_(\d+)(\.[A-Za-z0-9]+)$")
+
+
+def discover(run_dir):
+    """main.run's layout under run_dir -> [(bin_dir, exp_id, fmt, [(position, sample_path, reference_path), ...])], one entry
+    per bin directory (run_dir itself for a one-bin run, run_dir/NN_NNkev/ otherwise), positions in increasing order.
+    Raises ValueError when a sample has no reference partner (or the reverse), when one directory holds several runs or
+    formats, or when fewer than 3 positions are found.  Needs no GPU."""
+    run_dir = os.path.abspath(run_dir)
+    cands = [run_dir] + sorted(os.path.join(run_dir, d) for d in os.listdir(run_dir)
+                               if re.match(r"^\d+_\d+kev$", d) and os.path.isdir(os.path.join(run_dir, d)))
+    found = []
+    for d in cands:
+        sd, rd = os.path.join(d, "sample"), os.path.join(d, "ref")
+        if not os.path.isdir(sd) and not os.path.isdir(rd):
+            continue
+        side = []
+        for sub, pat in ((sd, _SAMPLE), (rd, _REF)):
+            files = {}
+            for f in sorted(os.listdir(sub)) if os.path.isdir(sub) else []:
+                mt = pat.match(f)
+                if mt:
+                    files[(mt.group(1), int(mt.group(2)), mt.group(3))] = os.path.join(sub, f)
+            side.append(files)
+        s, r = side
+        for key in sorted(set(s) ^ set(r)):
+            raise ValueError("%s: %s image of run %s position %d (%s) has no %s partner"
+                             % (d, "sample" if key in s else "reference", key[0], key[1], key[2],
+                                "reference" if key in s else "sample"))
+        runs = sorted({(k[0], k[2]) for k in s})
+        if not runs:
+            continue
+        if len(runs) > 1:
+            raise ValueError("%s holds several runs or formats %s: give one run's directory" % (d, runs))
+        exp_id, fmt = runs[0]
+        pos = sorted(k[1] for k in s)
+        if len(pos) < 3:
+            raise ValueError("%s: phase retrieval needs at least 3 positions, found %d" % (d, len(pos)))
+        found.append((d, exp_id, fmt, [(p, s[(exp_id, p, fmt)], r[(exp_id, p, fmt)]) for p in pos]))
+    if not found:
+        raise ValueError("no sample/ and ref/ images of main.run's layout under %s" % run_dir)
+    return found
+
+
+def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None):
+    """discover() + lcs (+ integrate when params are given) + save_retrieval for every bin directory; returns the paths."""
+    import torch
+    from .InputOutput.pagailleIO import openImage
+    written = []
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for d, exp_id, in_fmt, pairs in discover(run_dir):
+        S = torch.from_numpy(np.stack([np.asarray(openImage(s), dtype=np.float32) for _, s, _ in pairs])).to(dev)
+        R = torch.from_numpy(np.stack([np.asarray(openImage(r), dtype=np.float32) for _, _, r in pairs])).to(dev)
+        res = retrieve({p: (S[i:i + 1], R[i:i + 1]) for i, (p, _, _) in enumerate(pairs)}, params, max_shift=max_shift)[0]
+        written += save_retrieval(res, d, exp_id, fmt or in_fmt)
+    return written
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m paresis_amd.retrieval", description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("run_dir")
+    ap.add_argument("--energy", type=float, default=None, help="photon energy, keV")
+    ap.add_argument("--pixel-um", type=float, default=None, help="detector pixel size, micrometres")
+    ap.add_argument("--distance", type=float, default=None, help="object-to-detector distance, metres")
+    ap.add_argument("--magnification", type=float, default=None, help="exp_dict['magnification']")
+    ap.add_argument("--max-shift", type=float, default=None, help="clamp of dx, dy in pixels")
+    ap.add_argument("--format", default=None, help="output format (.tif, .edf, .npy); default: the input's")
+    a = ap.parse_args(argv)
+    phys = (a.energy, a.pixel_um, a.distance, a.magnification)
+    if any(v is not None for v in phys) and any(v is None for v in phys):
+        ap.error("--energy, --pixel-um, --distance and --magnification go together")
+    params = None if phys[0] is None else {'energy_keV': a.energy, 'pixel_um': a.pixel_um, 'distance_m': a.distance,
+                                           'magnification': a.magnification}
+    for p in retrieve_run_dir(a.run_dir, params, max_shift=a.max_shift, fmt=a.format):
+        print(p)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

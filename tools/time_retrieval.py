@@ -1,0 +1,85 @@
+"""Time the phase retrieval's kernels against their byte price.
+
+    python tools/time_retrieval.py [--reps 20] [--host]
+
+k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; the integration's extended grid is 2n x 2m complex64.  Times are
+HIP-event pairs per launch (psx_profile_summary), after warm-up, on a GPU the process has to itself.  --host adds the float64
+numpy oracle's time at the same sizes -- HOST time, one run, for scale only.
+"""
+import argparse
+import ctypes
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from paresis_amd import ops, retrieval  # noqa: E402
+from paresis_amd._lib import lib  # noqa: E402
+
+PEAK = 8e12
+
+
+def summary():
+    buf = ctypes.create_string_buffer(1 << 16)
+    ops.check(lib().psx_profile_summary(buf, len(buf)), "psx_profile_summary")
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, count, ms = line.split()
+        out[name] = (int(count), float(ms))
+    return out
+
+
+def case(n, m, K, reps, host):
+    g = torch.Generator(device="cuda").manual_seed(n + K)
+    S = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
+    R = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
+    outs = tuple(torch.empty((n, m), device="cuda") for _ in range(3))
+    phi = torch.empty((n, m), device="cuda")
+    for _ in range(3):
+        ops.lcs(S, R, out=outs)
+        retrieval.integrate(outs[1], outs[2], out=phi)
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        ops.lcs(S, R, out=outs)
+        retrieval.integrate(outs[1], outs[2], out=phi)
+    torch.cuda.synchronize()
+    s = summary()
+    lib().psx_profile_enable(0)
+    per = {k: v[1] / v[0] * 1e3 for k, v in s.items()}       # us per call
+    price = 4.0 * n * m * (2 * K + 3)
+    t = per["k_lcs"]
+    print("%dx%d K=%d  k_lcs %.1f us  price %.1f MB (%.1f us at 8 TB/s)  achieved %.2f TB/s = %.2f of 8 TB/s"
+          % (n, m, K, t, price / 1e6, price / PEAK * 1e6, price / (t * 1e-6) / 1e12, price / (t * 1e-6) / PEAK))
+    kern = sum(v for k, v in per.items() if k.startswith("k_integ"))
+    fft = sum(v for k, v in per.items() if k.startswith("rocfft_integrate"))
+    grid = 4.0 * n * m * 8
+    print("    integrate %.1f us = kernels %.1f us (%s) + rocFFT %.1f us (%s); extended grid %.1f MiB per pass"
+          % (kern + fft, kern, ", ".join("%s %.1f" % (k, v) for k, v in per.items() if k.startswith("k_integ")), fft,
+             ", ".join("%s %.1f" % (k, v) for k, v in per.items() if k.startswith("rocfft")), grid / 2 ** 20))
+    if host:
+        from tests import _retrieval_oracle as orl
+        Sh, Rh = list(S.cpu().numpy()), list(R.cpu().numpy())
+        t0 = time.perf_counter()
+        r = orl.lcs(Sh, Rh)
+        t1 = time.perf_counter()
+        orl.integrate(r['dx'], r['dy'])
+        t2 = time.perf_counter()
+        print("    numpy oracle (HOST time): lcs %.2f s, integrate %.2f s" % (t1 - t0, t2 - t1))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--host", action="store_true")
+    a = ap.parse_args()
+    for n, m, K in ((2048, 2048, 16), (2048, 2048, 64), (200, 200, 12)):
+        case(n, m, K, a.reps, a.host)
+
+
+if __name__ == "__main__":
+    main()

@@ -366,6 +366,16 @@ int psx_contrast_phantom_slices_u8(const psx_phantom_desc *desc, uint8_t *slices
 #define PSX_MAX_LCS 64
 int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
                 float *dx, float *dy, void *stream);
+/* LCS-DF: psx_lcs_f32 with a dark-field column (the diffusion term of the X-ray Fokker-Planck model, Morgan & Paganin,
+ * Sci. Rep. 9, 17465, 2019): per pixel, R_k ~ x0*S_k + x1*g0_k + x2*g1_k + x3*L_k, L_k = R[i+1,j] + R[i-1,j] + R[i,j+1] +
+ *   R[i,j-1] - 4 R[i,j] with edge-replicated neighbours (the gradients' clamped indices), formed in float64;
+ *   M (4x4), v as above with a_k = (S_k, g0_k, g1_k, L_k), solved by LDL^T without pivoting in float64;
+ *   x = (1, 0, 0, 0) exactly when a pivot d_i <= 0, prod d_i <= 1e-12*M00*M11*M22*M33, or the solved x0 <= 0;
+ *   transmission = 1/x0, dx = x1, dy = x2 as psx_lcs_f32 (max_shift clamps these two only), df = -x3 in detector px^2
+ *   (S ~ T*(R - D.grad R + df*lap R); a Gaussian blur of per-axis variance s^2 gives df = s^2/2), not clamped.
+ * K in [4, PSX_MAX_LCS], n, m >= 3; argument errors as psx_lcs_f32.  Reads the same bytes as psx_lcs_f32, writes four maps. */
+int psx_lcs_df_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
+                   float *dx, float *dy, float *df, void *stream);
 /* Frankot-Chellappa integration (IEEE PAMI 10, 1988) of the gradient field scale*(gx, gy) (rad per pixel along axis 0 / 1)
  * with mirror extension: on the 2n x 2m grid gx is odd in axis 0 and even in axis 1, gy even in axis 0 and odd in axis 1;
  * P = (-i kx Gx^ - i ky Gy^)/(kx^2 + ky^2), P(0) = 0, kx = 2 pi fftfreq(2n), ky = 2 pi fftfreq(2m); phi = Re ifft2(P) on

@@ -5,7 +5,11 @@
 //   R_k ~ x0*S_k + x1*g0_k + x2*g1_k,   (g0, g1) = np.gradient(R_k) (unit spacing, edge_order=1),
 //   M = sum_k a_k a_k^T, v = sum_k a_k R_k with a_k = (S_k, g0_k, g1_k), in float64;  M x = v;
 //   transmission = 1/x0, (dx, dy) = (x1, x2);  x = (1, 0, 0) when det M <= 1e-12 M00 M11 M22 or x0 <= 0.
-// k_lcs: one thread per pixel, all K positions in one launch; the gradient's neighbours come from L1/L2 (the rows above
+// LCS-DF (psx_lcs_df_f32; the diffusion term of the X-ray Fokker-Planck model, Morgan & Paganin, Sci. Rep. 9, 17465, 2019):
+//   R_k ~ x0*S_k + x1*g0_k + x2*g1_k + x3*L_k, L_k the edge-replicated 5-point Laplacian of R_k in float64;
+//   4x4 LDL^T without pivoting; x = (1, 0, 0, 0) when a pivot <= 0, prod d_i <= 1e-12 M00 M11 M22 M33, or x0 <= 0;
+//   df = -x3 (detector px^2: a Gaussian blur of per-axis variance s^2 gives df = s^2/2).
+// k_lcs, k_lcs_df: one thread per pixel, all K positions in one launch; the gradient's neighbours come from L1/L2 (the rows above
 // and below are the neighbouring wavefronts' own rows), so HBM sees every input image about once.
 //
 // Frankot-Chellappa (IEEE PAMI 10, 1988) with mirror extension, 2n x 2m complex64 grid:
@@ -79,6 +83,91 @@ __global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs(LcsPtrs p, int K, int n
     trans[c] = t;
     dx[c] = x;
     dy[c] = y;
+}
+
+// LCS-DF: k_lcs with a fourth column, the 5-point Laplacian of R_k with edge-replicated neighbours (the same clamped indices
+// as the gradients, so the same six loads), formed in float64 from the float32 samples: exact for image data.  The 4x4
+// system is solved by LDL^T without pivoting; fallback x = (1, 0, 0, 0) when a pivot is <= 0, when prod d_i (= det M) <=
+// 1e-12*M00*M11*M22*M33, or when x0 <= 0.  df = -x3 is not clamped.
+__global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs_df(LcsPtrs p, int K, int n, int m, float max_shift,
+                                                            float *__restrict__ trans, float *__restrict__ dx,
+                                                            float *__restrict__ dy, float *__restrict__ df) {
+    const int j = blockIdx.x * LCS_BX + threadIdx.x;
+    const int i = blockIdx.y * LCS_BY + threadIdx.y;
+    if (i >= n || j >= m) return;
+    const int ip = i + 1 < n ? i + 1 : n - 1, im = i > 0 ? i - 1 : 0;
+    const int jp = j + 1 < m ? j + 1 : m - 1, jm = j > 0 ? j - 1 : 0;
+    const float h0 = ip - im == 2 ? 0.5f : 1.0f, h1 = jp - jm == 2 ? 0.5f : 1.0f;
+    const int64_t c = (int64_t)i * m + j;
+    const int64_t up = (int64_t)ip * m + j, dn = (int64_t)im * m + j;
+    const int64_t rt = (int64_t)i * m + jp, lt = (int64_t)i * m + jm;
+    double m00 = 0.0, m01 = 0.0, m02 = 0.0, m03 = 0.0, m11 = 0.0, m12 = 0.0, m13 = 0.0, m22 = 0.0, m23 = 0.0, m33 = 0.0;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
+#pragma unroll 2
+    for (int k = 0; k < K; ++k) {
+        const float *R = p.R[k];
+        const float s = p.S[k][c], r = R[c], ru = R[up], rd = R[dn], rr = R[rt], rl = R[lt];
+        const double b = r;
+        const double a0 = s, a1 = (ru - rd) * h0, a2 = (rr - rl) * h1;
+        const double a3 = (((double)ru + (double)rd) + ((double)rr + (double)rl)) - 4.0 * b;   // exact in float64
+        m00 = fma(a0, a0, m00);
+        m01 = fma(a0, a1, m01);
+        m02 = fma(a0, a2, m02);
+        m03 = fma(a0, a3, m03);
+        m11 = fma(a1, a1, m11);
+        m12 = fma(a1, a2, m12);
+        m13 = fma(a1, a3, m13);
+        m22 = fma(a2, a2, m22);
+        m23 = fma(a2, a3, m23);
+        m33 = fma(a3, a3, m33);
+        v0 = fma(a0, b, v0);
+        v1 = fma(a1, b, v1);
+        v2 = fma(a2, b, v2);
+        v3 = fma(a3, b, v3);
+    }
+    float t = 1.0f, x = 0.0f, y = 0.0f, w = 0.0f;
+    // M = L D L^T, column by column; e_ij = L_ij*d_j
+    const double d0 = m00;
+    if (d0 > 0.0) {
+        const double r0 = 1.0 / d0;
+        const double l10 = m01 * r0, l20 = m02 * r0, l30 = m03 * r0;
+        const double d1 = m11 - l10 * m01;
+        if (d1 > 0.0) {
+            const double r1 = 1.0 / d1;
+            const double e21 = m12 - l20 * m01, e31 = m13 - l30 * m01;
+            const double l21 = e21 * r1, l31 = e31 * r1;
+            const double d2 = m22 - l20 * m02 - l21 * e21;
+            if (d2 > 0.0) {
+                const double r2 = 1.0 / d2;
+                const double e32 = m23 - l30 * m02 - l31 * e21;
+                const double l32 = e32 * r2;
+                const double d3 = m33 - l30 * m03 - l31 * e31 - l32 * e32;
+                if (d3 > 0.0 && !(d0 * d1 * d2 * d3 <= 1e-12 * m00 * m11 * m22 * m33)) {
+                    const double y1 = v1 - l10 * v0;
+                    const double y2 = v2 - l20 * v0 - l21 * y1;
+                    const double y3 = v3 - l30 * v0 - l31 * y1 - l32 * y2;
+                    const double x3 = y3 / d3;
+                    const double x2 = y2 * r2 - l32 * x3;
+                    const double x1 = y1 * r1 - l21 * x2 - l31 * x3;
+                    const double x0 = v0 * r0 - l10 * x1 - l20 * x2 - l30 * x3;
+                    if (x0 > 0.0) {
+                        t = (float)(1.0 / x0);
+                        x = (float)x1;
+                        y = (float)x2;
+                        w = (float)(-x3);
+                    }
+                }
+            }
+        }
+    }
+    if (max_shift > 0.0f) {
+        x = fminf(fmaxf(x, -max_shift), max_shift);
+        y = fminf(fmaxf(y, -max_shift), max_shift);
+    }
+    trans[c] = t;
+    dx[c] = x;
+    dy[c] = y;
+    df[c] = w;
 }
 
 // Z[a][b] on the 2n x 2m extension: Gx = +-gx (minus on the mirrored rows), Gy = +-gy (minus on the mirrored columns)
@@ -204,6 +293,29 @@ int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int 
     const dim3 grid((unsigned)cdiv(m, LCS_BX), (unsigned)cdiv(n, LCS_BY)), block(LCS_BX, LCS_BY);
     PSX_TIMED("k_lcs", st, k_lcs<<<grid, block, 0, st>>>(p, K, n, m, max_shift, transmission, dx, dy));
     return launch_check("k_lcs");
+}
+
+int psx_lcs_df_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
+                   float *dx, float *dy, float *df, void *stream) {
+    PSX_REQUIRE(K >= 4 && K <= PSX_MAX_LCS, "psx_lcs_df_f32: K=%d positions outside [4,%d]", K, PSX_MAX_LCS);
+    PSX_REQUIRE(n >= 3 && m >= 3, "psx_lcs_df_f32: images %dx%d smaller than 3x3", n, m);
+    PSX_REQUIRE(S != nullptr && R != nullptr, "psx_lcs_df_f32: null pointer array");
+    PSX_REQUIRE(transmission && dx && dy && df, "psx_lcs_df_f32: null output map");
+    PSX_REQUIRE(max_shift >= 0.0f, "psx_lcs_df_f32: max_shift=%g < 0", (double)max_shift);
+    LcsPtrs p;
+    for (int k = 0; k < PSX_MAX_LCS; ++k) {
+        p.S[k] = nullptr;
+        p.R[k] = nullptr;
+    }
+    for (int k = 0; k < K; ++k) {
+        PSX_REQUIRE(S[k] != nullptr && R[k] != nullptr, "psx_lcs_df_f32: position %d has a null image", k);
+        p.S[k] = S[k];
+        p.R[k] = R[k];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)cdiv(m, LCS_BX), (unsigned)cdiv(n, LCS_BY)), block(LCS_BX, LCS_BY);
+    PSX_TIMED("k_lcs_df", st, k_lcs_df<<<grid, block, 0, st>>>(p, K, n, m, max_shift, transmission, dx, dy, df));
+    return launch_check("k_lcs_df");
 }
 
 int psx_integrate_plan_create(int n, int m, psx_integrate_plan **plan) {

@@ -3,13 +3,13 @@
 
     python -m paresis_amd.main [--experiment NAME] [--type RayT|Fresnel] [--oversampling N] [--points N]
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
-                               [--retrieve [--max-shift S]]
+                               [--retrieve [--max-shift S] [--dark-field]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
 has its own seed.  --retrieve (needs 3 positions or more) runs the speckle-tracking phase retrieval of each bin on rank 0
 after the gather (paresis_amd/retrieval.py) and writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under the bin's
-directory.
+directory.  --dark-field (needs 4 positions or more) retrieves with LCS-DF and adds df_ and scattering_<expID><fmt>.
 """
 import argparse
 import datetime
@@ -19,14 +19,19 @@ import time
 import numpy as np
 
 
-def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None):
+def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
     (retrieval.retrieve with the experiment's parameters, max_shift its clamp); with save, the maps go to
-    <bin dir>/retrieval/.  exp_dict['retrievalParams'] then holds the parameters it used."""
+    <bin dir>/retrieval/.  exp_dict['retrievalParams'] then holds the parameters it used.  dark_field (with retrieve, 4
+    positions or more): LCS-DF, the maps gain df and scattering (retrieval.retrieve(..., dark_field=True))."""
     if retrieve and int(exp_dict['nbExpPoints']) < 3:
         raise ValueError("--retrieve needs at least 3 membrane positions, got %d" % int(exp_dict['nbExpPoints']))
+    if dark_field and not retrieve:
+        raise ValueError("dark_field is an option of retrieve")
+    if dark_field and int(exp_dict['nbExpPoints']) < 4:
+        raise ValueError("dark-field retrieval needs at least 4 membrane positions, got %d" % int(exp_dict['nbExpPoints']))
     from . import dist
     from .Experiment import Experiment
     from .InputOutput.pagailleIO import save_image
@@ -137,7 +142,7 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     if rank == 0 and retrieve:
         from . import retrieval
         params = retrieval.params_from_experiment(experiment)
-        retrieved = retrieval.retrieve(gathered, params, max_shift=max_shift)
+        retrieved = retrieval.retrieve(gathered, params, max_shift=max_shift, dark_field=dark_field)
         exp_dict['retrievalParams'] = params
         if save:
             for ibin in sorted(retrieved):
@@ -169,6 +174,8 @@ def main(argv=None):
                     help="speckle-tracking phase retrieval of every bin after the run (3 positions or more): "
                          "retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory")
     ap.add_argument("--max-shift", type=float, default=None, help="--retrieve: clamp of the displacements, in pixels")
+    ap.add_argument("--dark-field", action="store_true",
+                    help="--retrieve with LCS-DF (4 positions or more): also retrieval/{df,scattering}_<expID><fmt>")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -178,7 +185,12 @@ def main(argv=None):
     os.makedirs(exp_dict['filepath'], exist_ok=True)
     if a.retrieve and a.points < 3:
         ap.error("--retrieve needs --points 3 or more")
-    run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift)
+    if a.dark_field and not a.retrieve:
+        ap.error("--dark-field is an option of --retrieve")
+    if a.dark_field and a.points < 4:
+        ap.error("--dark-field needs --points 4 or more")
+    run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
+        dark_field=a.dark_field)
 
 
 if __name__ == "__main__":

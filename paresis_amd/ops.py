@@ -967,13 +967,9 @@ def _positions(imgs, name):
     return imgs
 
 
-def lcs(sample, reference, max_shift=None, out=None):
-    """LCS speckle tracking of one energy bin (psx_lcs_f32): K in [3, PSX_MAX_LCS] sample / reference pairs of n x m float32
-    images in HBM -> (transmission, dx, dy), n x m float32.  dx is the displacement along axis 0, dy along axis 1, in pixels,
-    with the sign of the chain's Dxreal / Dyreal.  max_shift (pixels, > 0) clamps dx and dy; None: no clamp.  out: three
-    caller-owned n x m float32 tensors (transmission, dx, dy) to write into."""
-    S = _positions(sample, "sample")
-    R = _positions(reference, "reference")
+def _lcs_args(S, R, max_shift, out, names):
+    """The checks ops.lcs and ops.lcs_df share, after _positions: equal counts and shapes, float32 images in HBM on one device,
+    max_shift > 0 or None; out= tensors of the n x m shape (`names`, one per output map), or new ones.  -> (shape, dev, ms, out)"""
     if len(S) != len(R):
         raise PsxError("sample has %d positions, reference %d" % (len(S), len(R)))
     shape = tuple(S[0].shape)
@@ -991,19 +987,50 @@ def lcs(sample, reference, max_shift=None, out=None):
     if max_shift is not None and not ms > 0.0:
         raise PsxError("max_shift must be > 0 pixels (None: no clamp), got %r" % (max_shift,))
     if out is None:
-        out = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3))
+        out = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for _ in names)
     else:
         out = tuple(out)
-        if len(out) != 3:
-            raise PsxError("out must hold three tensors (transmission, dx, dy)")
-        for nm, t in zip(("transmission", "dx", "dy"), out):
+        if len(out) != len(names):
+            raise PsxError("out must hold %s tensors (%s)" % (("three", "four")[len(names) - 3], ", ".join(names)))
+        for nm, t in zip(names, out):
             _need(t, torch.float32, "out " + nm, shape)
             if t.device != dev:
                 raise PsxError("out %s is on %s, the images on %s" % (nm, t.device, dev))
+    return shape, dev, ms, out
+
+
+def lcs(sample, reference, max_shift=None, out=None):
+    """LCS speckle tracking of one energy bin (psx_lcs_f32): K in [3, PSX_MAX_LCS] sample / reference pairs of n x m float32
+    images in HBM -> (transmission, dx, dy), n x m float32.  dx is the displacement along axis 0, dy along axis 1, in pixels,
+    with the sign of the chain's Dxreal / Dyreal.  max_shift (pixels, > 0) clamps dx and dy; None: no clamp.  out: three
+    caller-owned n x m float32 tensors (transmission, dx, dy) to write into."""
+    S = _positions(sample, "sample")
+    R = _positions(reference, "reference")
+    shape, dev, ms, out = _lcs_args(S, R, max_shift, out, ("transmission", "dx", "dy"))
     K = len(S)
     with torch.cuda.device(dev):
         check(lib().psx_lcs_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K, shape[0], shape[1], c_float(ms),
                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), "psx_lcs_f32")
+    return out
+
+
+def lcs_df(sample, reference, max_shift=None, out=None):
+    """LCS-DF speckle tracking of one energy bin (psx_lcs_df_f32): ops.lcs with a dark-field column, the 5-point Laplacian of
+    each reference image (the diffusion term of the X-ray Fokker-Planck model).  K in [4, PSX_MAX_LCS] sample / reference
+    pairs in the forms ops.lcs takes -> (transmission, dx, dy, df), n x m float32.  dx, dy as ops.lcs (max_shift clamps these
+    two only); df is the diffusion coefficient in detector pixels^2 (a Gaussian blur of per-axis variance s^2 gives
+    df = s^2/2), not clamped.  out: four caller-owned n x m float32 tensors (transmission, dx, dy, df) to write into."""
+    S = _positions(sample, "sample")
+    R = _positions(reference, "reference")
+    for nm, imgs in (("sample", S), ("reference", R)):
+        if len(imgs) < 4:
+            raise PsxError("%s: K=%d positions outside [4, %d]: dark field has four unknowns" % (nm, len(imgs), _lib.PSX_MAX_LCS))
+    shape, dev, ms, out = _lcs_args(S, R, max_shift, out, ("transmission", "dx", "dy", "df"))
+    K = len(S)
+    with torch.cuda.device(dev):
+        check(lib().psx_lcs_df_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K,
+                                   shape[0], shape[1], c_float(ms), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                                   _stream()), "psx_lcs_df_f32")
     return out
 
 

@@ -6,7 +6,10 @@ module turns them into the sample's transmission, its refraction (displacement) 
     lcs(sample, reference)   LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021): per pixel, the float64
                              least-squares solution of  R_k ~ x0*S_k + x1*dR_k/d0 + x2*dR_k/d1  over the K positions,
                              the first-order form of S(r) = T*R(r - D): transmission = 1/x0, (dx, dy) = (x1, x2) in
-                             detector pixels, along axis 0 / axis 1, with the sign of the chain's Dxreal / Dyreal
+                             detector pixels, along axis 0 / axis 1, with the sign of the chain's Dxreal / Dyreal;
+                             dark_field=True (LCS-DF, K >= 4) adds the column x3*lap(R_k), the diffusion term of the X-ray
+                             Fokker-Planck model (Morgan & Paganin, Sci. Rep. 9, 17465, 2019): df = -x3 in detector px^2
+    scattering_angle(df, ...) df -> the chain's scattering angle theta in radians
     phase_gradient(...)      displacement -> phase gradient in radians per detector pixel
     integrate(gx, gy)        Frankot-Chellappa (IEEE PAMI 10, 1988) with mirror extension -> phase (zero mean)
     retrieve(results, ...)   all of it for every bin of main.run's {position: (Sample, Reference, ...)}
@@ -15,10 +18,10 @@ Both steps are HIP kernels (csrc/retrieve.hip; the integration's transforms are 
 argument checks.  Command line, for a run already on disk (main.py's layout):
 
     python -m paresis_amd.retrieval RUN_DIR [--energy KEV --pixel-um P --distance Z --magnification M]
-                                            [--max-shift S] [--format .tif]
+                                            [--max-shift S] [--format .tif] [--dark-field]
 
 writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory; without the four physical parameters
-only transmission, dx and dy.
+only transmission, dx and dy.  --dark-field (4 positions or more) adds df, and scattering with the physical parameters.
 """
 import argparse
 import os
@@ -32,10 +35,15 @@ from .getk import getk
 _plans = {}
 
 
-def lcs(sample, reference, max_shift=None):
+def lcs(sample, reference, max_shift=None, dark_field=False):
     """K >= 3 sample / reference images of one bin ([K, n, m] float32 CUDA tensors, or sequences of K n x m ones) ->
-    {'transmission', 'dx', 'dy'}, n x m float32 on the same device.  max_shift (pixels): clamp dx, dy; None: no clamp."""
+    {'transmission', 'dx', 'dy'}, n x m float32 on the same device.  max_shift (pixels): clamp dx, dy; None: no clamp.
+    dark_field: LCS-DF (K >= 4, ops.lcs_df) -- the four-unknown system, whose transmission and displacement are not biased
+    by the lost speckle visibility of a scattering sample, and 'df' (detector px^2, unclamped) in the dict."""
     from . import ops
+    if dark_field:
+        t, dx, dy, df = ops.lcs_df(sample, reference, max_shift=max_shift)
+        return {'transmission': t, 'dx': dx, 'dy': dy, 'df': df}
     t, dx, dy = ops.lcs(sample, reference, max_shift=max_shift)
     return {'transmission': t, 'dx': dx, 'dy': dy}
 
@@ -70,6 +78,22 @@ def gradient_scale(energy_keV, pixel_um, distance_m, magnification):
     return getk(float(energy_keV) * 1e3) * p * p / (float(magnification) * float(distance_m))
 
 
+def scattering_angle(df, pixel_um, distance_m):
+    """The chain's scattering angle theta (radians) from LCS-DF's df (detector px^2): theta = 2*p*sqrt(2*max(df, 0))/z.
+
+    The ray-tracing chain turns theta into a Gaussian re-splat of sigma = theta*z/(h*M)/2 study pixels
+    (refractionFileNumba2.py:114, gaussian_shape(DF/2)), h = p/(ov*M) the study pixel (Experiment.py:188), M the
+    object->detector magnification the chain passes, so sigma_study = theta*z*ov/(2*p).  The detector bins ov x ov study
+    pixels into one: sigma_det = sigma_study/ov = theta*z/(2*p) detector pixels.  A Gaussian blur of per-axis variance s^2 is
+    to first order f + (s^2/2)*lap f, so df = sigma_det^2/2, i.e. theta = 2*p*sqrt(2*df)/z; ov, M and the energy drop out.
+    Negative df (noise, model error) gives 0.  df: a tensor or a numpy array; pixel_um: the detector pixel; distance_m:
+    distObjectToDetector."""
+    c = 2.0 * float(pixel_um) * 1e-6 / float(distance_m)
+    if hasattr(df, "clamp"):
+        return c * (2.0 * df.clamp(min=0)).sqrt()
+    return c * np.sqrt(2.0 * np.maximum(df, 0))
+
+
 def phase_gradient(dx, dy, energy_keV, pixel_um, distance_m, magnification):
     """(gx, gy) = (dx, dy) * k*p^2/(M*z): displacements in detector pixels -> phase gradient in radians per detector pixel
     (see gradient_scale).  energy_keV: the photon energy; pixel_um: the detector pixel; distance_m: distObjectToDetector;
@@ -96,18 +120,22 @@ def _stack(results, positions, slot, device):
     return [dev[k] for k in range(dev.shape[0])]
 
 
-def retrieve(results, params=None, bins=None, energies=None, max_shift=None, device=None):
+def retrieve(results, params=None, bins=None, energies=None, max_shift=None, device=None, dark_field=False):
     """Retrieve every bin of a run: results = main.run's {position: (Sample, Reference, ...)} with [nbins, n, m] stacks (host or
     device; host stacks are uploaded once) -> {bin: {'transmission', 'dx', 'dy', 'phi'}}, device tensors.
 
     params: {'energy_keV', 'pixel_um', 'distance_m', 'magnification'} (params_from_experiment); None: no phase ('phi' left
     out).  bins: the bins to retrieve (default all).  energies: one energy (keV) per bin of `bins`; without it every bin uses
     params['energy_keV'] -- the run's mean detected energy, which is right for one bin only: a multi-bin run should pass
-    each bin's own energy.  max_shift: clamp of dx, dy in pixels (None: no clamp)."""
+    each bin's own energy.  max_shift: clamp of dx, dy in pixels (None: no clamp).  dark_field: LCS-DF (4 positions or
+    more): every bin also gets 'df' (detector px^2) and, with params, 'scattering' (theta, radians; scattering_angle);
+    'phi' then integrates the four-unknown system's dx, dy."""
     import torch
     positions = sorted(results)
     if len(positions) < 3:
         raise ValueError("phase retrieval needs at least 3 positions, got %d" % len(positions))
+    if dark_field and len(positions) < 4:
+        raise ValueError("dark-field retrieval needs at least 4 positions, got %d" % len(positions))
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     S = _stack(results, positions, 0, dev)
     R = _stack(results, positions, 1, dev)
@@ -117,22 +145,24 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
         raise ValueError("energies must hold one value per retrieved bin (%d), got %d" % (len(bins), len(energies)))
     out = {}
     for i, b in enumerate(bins):
-        r = lcs([s[b] for s in S], [s[b] for s in R], max_shift=max_shift)
+        r = lcs([s[b] for s in S], [s[b] for s in R], max_shift=max_shift, dark_field=dark_field)
         if params is not None:
             e = params['energy_keV'] if energies is None else energies[i]
             r['phi'] = integrate(r['dx'], r['dy'],
                                  scale=gradient_scale(e, params['pixel_um'], params['distance_m'], params['magnification']))
+            if dark_field:
+                r['scattering'] = scattering_angle(r['df'], params['pixel_um'], params['distance_m'])
         out[b] = r
     return out
 
 
 def save_retrieval(r, directory, exp_id, fmt):
-    """Write one bin's maps as directory/retrieval/<name>_<exp_id><fmt> (name: transmission, dx, dy[, phi])."""
+    """Write one bin's maps as directory/retrieval/<name>_<exp_id><fmt> (name: transmission, dx, dy[, phi][, df][, scattering])."""
     from .InputOutput.pagailleIO import save_image
     d = os.path.join(directory, "retrieval")
     os.makedirs(d, exist_ok=True)
     paths = []
-    for name in ("transmission", "dx", "dy", "phi"):
+    for name in ("transmission", "dx", "dy", "phi", "df", "scattering"):
         if name in r:
             paths.append(os.path.join(d, "%s_%s%s" % (name, exp_id, fmt)))
             save_image(r[name].detach().cpu().numpy(), paths[-1])
@@ -184,8 +214,9 @@ def discover(run_dir):
     return found
 
 
-def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None):
-    """discover() + lcs (+ integrate when params are given) + save_retrieval for every bin directory; returns the paths."""
+def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None, dark_field=False):
+    """discover() + lcs (+ integrate when params are given) + save_retrieval for every bin directory; returns the paths.
+    dark_field: LCS-DF (4 positions or more), df (+ scattering with params) written too."""
     import torch
     from .InputOutput.pagailleIO import openImage
     written = []
@@ -193,7 +224,8 @@ def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None):
     for d, exp_id, in_fmt, pairs in discover(run_dir):
         S = torch.from_numpy(np.stack([np.asarray(openImage(s), dtype=np.float32) for _, s, _ in pairs])).to(dev)
         R = torch.from_numpy(np.stack([np.asarray(openImage(r), dtype=np.float32) for _, _, r in pairs])).to(dev)
-        res = retrieve({p: (S[i:i + 1], R[i:i + 1]) for i, (p, _, _) in enumerate(pairs)}, params, max_shift=max_shift)[0]
+        res = retrieve({p: (S[i:i + 1], R[i:i + 1]) for i, (p, _, _) in enumerate(pairs)}, params, max_shift=max_shift,
+                       dark_field=dark_field)[0]
         written += save_retrieval(res, d, exp_id, fmt or in_fmt)
     return written
 
@@ -208,13 +240,20 @@ def main(argv=None):
     ap.add_argument("--magnification", type=float, default=None, help="exp_dict['magnification']")
     ap.add_argument("--max-shift", type=float, default=None, help="clamp of dx, dy in pixels")
     ap.add_argument("--format", default=None, help="output format (.tif, .edf, .npy); default: the input's")
+    ap.add_argument("--dark-field", action="store_true",
+                    help="LCS-DF (4 positions or more): also df (detector px^2) and, with the physical parameters, scattering "
+                         "(rad)")
     a = ap.parse_args(argv)
     phys = (a.energy, a.pixel_um, a.distance, a.magnification)
     if any(v is not None for v in phys) and any(v is None for v in phys):
         ap.error("--energy, --pixel-um, --distance and --magnification go together")
     params = None if phys[0] is None else {'energy_keV': a.energy, 'pixel_um': a.pixel_um, 'distance_m': a.distance,
                                            'magnification': a.magnification}
-    for p in retrieve_run_dir(a.run_dir, params, max_shift=a.max_shift, fmt=a.format):
+    if a.dark_field:
+        for d, _, _, pairs in discover(a.run_dir):
+            if len(pairs) < 4:
+                ap.error("--dark-field needs at least 4 positions; %s has %d" % (d, len(pairs)))
+    for p in retrieve_run_dir(a.run_dir, params, max_shift=a.max_shift, fmt=a.format, dark_field=a.dark_field):
         print(p)
     return 0
 

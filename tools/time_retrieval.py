@@ -2,8 +2,10 @@
 
     python tools/time_retrieval.py [--reps 20] [--host]
 
-k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; the integration's extended grid is 2n x 2m complex64.  Times are
-HIP-event pairs per launch (psx_profile_summary), after warm-up, on a GPU the process has to itself.  --host adds the float64
+k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
+4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
+integration's extended grid is 2n x 2m complex64.  Times are HIP-event pairs per launch (psx_profile_summary), after warm-up,
+on a GPU the process has to itself.  --host adds the float64
 numpy oracle's time at the same sizes -- HOST time, one run, for scale only.
 """
 import argparse
@@ -38,14 +40,17 @@ def case(n, m, K, reps, host):
     S = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
     R = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
     outs = tuple(torch.empty((n, m), device="cuda") for _ in range(3))
+    outs_df = tuple(torch.empty((n, m), device="cuda") for _ in range(4))
     phi = torch.empty((n, m), device="cuda")
     for _ in range(3):
         ops.lcs(S, R, out=outs)
+        ops.lcs_df(S, R, out=outs_df)
         retrieval.integrate(outs[1], outs[2], out=phi)
     torch.cuda.synchronize()
     lib().psx_profile_enable(1)
     for _ in range(reps):
         ops.lcs(S, R, out=outs)
+        ops.lcs_df(S, R, out=outs_df)
         retrieval.integrate(outs[1], outs[2], out=phi)
     torch.cuda.synchronize()
     s = summary()
@@ -55,6 +60,11 @@ def case(n, m, K, reps, host):
     t = per["k_lcs"]
     print("%dx%d K=%d  k_lcs %.1f us  price %.1f MB (%.1f us at 8 TB/s)  achieved %.2f TB/s = %.2f of 8 TB/s"
           % (n, m, K, t, price / 1e6, price / PEAK * 1e6, price / (t * 1e-6) / 1e12, price / (t * 1e-6) / PEAK))
+    price_df = 4.0 * n * m * (2 * K + 4)
+    tdf = per["k_lcs_df"]
+    print("%dx%d K=%d  k_lcs_df %.1f us = %.2f x k_lcs  price %.1f MB (%.1f us at 8 TB/s)  achieved %.2f TB/s = %.2f of 8 TB/s"
+          % (n, m, K, tdf, tdf / t, price_df / 1e6, price_df / PEAK * 1e6, price_df / (tdf * 1e-6) / 1e12,
+             price_df / (tdf * 1e-6) / PEAK))
     kern = sum(v for k, v in per.items() if k.startswith("k_integ"))
     fft = sum(v for k, v in per.items() if k.startswith("rocfft_integrate"))
     grid = 4.0 * n * m * 8
@@ -69,7 +79,10 @@ def case(n, m, K, reps, host):
         t1 = time.perf_counter()
         orl.integrate(r['dx'], r['dy'])
         t2 = time.perf_counter()
-        print("    numpy oracle (HOST time): lcs %.2f s, integrate %.2f s" % (t1 - t0, t2 - t1))
+        from tests import _retrieval_df_oracle as odf
+        odf.lcs_df(Sh, Rh)
+        t3 = time.perf_counter()
+        print("    numpy oracle (HOST time): lcs %.2f s, integrate %.2f s, lcs_df %.2f s" % (t1 - t0, t2 - t1, t3 - t2))
 
 
 def main():

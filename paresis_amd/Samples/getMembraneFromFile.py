@@ -21,6 +21,7 @@ import torch
 
 from .. import synth
 from .._lib import check, lib
+from ..ops import _Plan
 from .._tensors import device
 
 SPHERE_FILE = "Samples/Membranes/CuSn.txt"
@@ -92,22 +93,16 @@ def sphere_layers(sphere_list, dimX, dimY, pixSize, meanSphereRadius, nbOfLayers
     return margin, margin2, layers
 
 
-class _MembranePlan:
+class _MembranePlan(_Plan):
     """The stitched list of one (sphere list, grid, pixel size, mean radius) resident on one GPU (psx_membrane_plan)."""
+    _destroy = "psx_membrane_plan_destroy"
 
     def __init__(self, lst, dimX, dimY, pixSize, meanSphereRadius):
         self.margin, self.margin2, par, self.sizeX, self.sizeY = stitched_list(lst, dimX, dimY, pixSize, meanSphereRadius)
         x, y, r = (np.ascontiguousarray(v, dtype=np.float64) for v in (par[:, 1] / pixSize, par[:, 0] / pixSize, par[:, 2] / pixSize))
-        self.h = c_void_p(None)
+        self._h = c_void_p(None)
         check(lib().psx_membrane_plan_create(x.ctypes.data_as(_DP), y.ctypes.data_as(_DP), r.ctypes.data_as(_DP), len(r),
-                                             ctypes.byref(self.h)), "psx_membrane_plan_create")
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().psx_membrane_plan_destroy(self.h)
-        except Exception:
-            pass
+                                             ctypes.byref(self._h)), "psx_membrane_plan_create")
 
 
 _plans = {}
@@ -151,7 +146,7 @@ def getMembraneSegmentedFromFile(sample, dimX, dimY, pixSize, pointNum, supportT
     # every layer and the uniform support map in ONE launch of the library (the position loop launches no PyTorch kernel)
     ox = (ctypes.c_int * max(1, len(offs)))(*[int(o[0]) for o in offs])
     oy = (ctypes.c_int * max(1, len(offs)))(*[int(o[1]) for o in offs])
-    check(lib().psx_membrane_layers_f32(plan.h, len(offs), ox, oy, dimX, dimY, plan.margin, plan.margin2,
+    check(lib().psx_membrane_layers_f32(plan._h, len(offs), ox, oy, dimX, dimY, plan.margin, plan.margin2,
                                         c_double(pixSize * 1e-6), 0, c_void_p(membrane.data_ptr()), c_void_p(support.data_ptr()),
                                         ctypes.c_float(float(supportThickness) * 1e-6), st), "psx_membrane_layers_f32")
     parameters_dic = {'Average sphere radius': (sample.myMeanSphereRadius, 'um'),

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 
 #include "paresis_hip.h"
 
@@ -33,6 +34,67 @@ inline int launch_check(const char *what) {
     if (e != hipSuccess) return fail((int)e, "launch of %s failed: %s", what, hipGetErrorString(e));
     return 0;
 }
+
+// ---- the owner of a device allocation ------------------------------------------------------------------------------
+// Move-only; every hipMalloc / hipFree of the library is in here.  It allocates only where alloc / upload is called, and
+// never lives at namespace scope or in a static (its destructor must not run after the HIP runtime is gone): plans are
+// heap objects destroyed through the ABI, per-call temporaries are locals.  Kernel argument blocks take get().
+// Stream-ordered mode (the *_async calls, per-call temporaries): the memory comes from the stream's pool, and reset()
+// waits for the stream before it hands it back, so the host arrays of an upload_async may go once the buffer is gone.
+template <class T>
+class DevBuf {
+    T *p_ = nullptr;
+    size_t n_ = 0;
+    hipStream_t st_ = nullptr;
+    bool async_ = false;
+
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { *this = static_cast<DevBuf &&>(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_; n_ = o.n_; st_ = o.st_; async_ = o.async_;
+            o.p_ = nullptr; o.n_ = 0;
+        }
+        return *this;
+    }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+
+    int alloc(size_t n) {
+        reset();
+        PSX_HIP(hipMalloc((void **)&p_, sizeof(T) * n));
+        n_ = n; async_ = false;
+        return 0;
+    }
+    int upload(const T *host, size_t n) {
+        if (int rc = alloc(n)) return rc;
+        PSX_HIP(hipMemcpy(p_, host, sizeof(T) * n, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int upload_async(const T *host, size_t n, hipStream_t st) {
+        reset();
+        PSX_HIP(hipMallocAsync((void **)&p_, sizeof(T) * n, st));
+        n_ = n; st_ = st; async_ = true;
+        PSX_HIP(hipMemcpyAsync(p_, host, sizeof(T) * n, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    void reset() {
+        if (p_ && async_) {
+            (void)hipStreamSynchronize(st_);
+            (void)hipFreeAsync(p_, st_);
+        } else if (p_) {
+            (void)hipFree(p_);
+        }
+        p_ = nullptr; n_ = 0;
+    }
+    T *get() const { return p_; }
+    size_t elems() const { return n_; }
+    size_t bytes() const { return sizeof(T) * n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
 
 // ---- a stack of thickness maps with per-map coefficients, passed to kernels by value ---------------------------
 struct Mats {

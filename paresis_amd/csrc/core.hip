@@ -119,17 +119,16 @@ int psx_abi_version(void) { return 13; }   // 3: psx_debug_switch(es_active), ps
 const char *psx_last_error(void) { return psx::err_buf(); }
 
 int psx_device_ok(void) {
-    int *d = nullptr;
+    psx::DevBuf<int> d;
     int h = 0;
-    if (hipMalloc(&d, sizeof(int)) != hipSuccess) {
+    if (d.alloc(1)) {
         psx::fail(1, "hipMalloc failed: no usable HIP device");
         return 0;
     }
-    (void)hipMemset(d, 0, sizeof(int));
-    psx_probe_kernel<<<1, 1>>>(d);
+    (void)hipMemset(d.get(), 0, sizeof(int));
+    psx_probe_kernel<<<1, 1>>>(d.get());
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = hipMemcpy(&h, d.get(), sizeof(int), hipMemcpyDeviceToHost);
     if (e != hipSuccess || h != 950) {
         psx::fail((int)e, "gfx950 code object not runnable on this device: %s", hipGetErrorString(e));
         return 0;
@@ -140,13 +139,13 @@ int psx_device_ok(void) {
 int psx_clock_probe(float *mhz, void *stream) {
     if (!mhz) return psx::fail(PSX_E_ARG, "psx_clock_probe: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long *d = nullptr, h[2] = {0ull, 0ull};
-    PSX_HIP(hipMalloc((void **)&d, 3 * sizeof(unsigned long long)));
-    psx_clock_probe_kernel<<<psx::current_cu_count(), 256, 0, st>>>(d, 3000u, 1.0f);       // 30 us on every CU
+    psx::DevBuf<unsigned long long> d;
+    unsigned long long h[2] = {0ull, 0ull};
+    if (int rc = d.alloc(3)) return rc;
+    psx_clock_probe_kernel<<<psx::current_cu_count(), 256, 0, st>>>(d.get(), 3000u, 1.0f);       // 30 us on every CU
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d.get(), sizeof(h), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d);
     if (e != hipSuccess || h[1] == 0ull) return psx::fail((int)e, "psx_clock_probe: %s", hipGetErrorString(e));
     *mhz = (float)((double)h[0] / (double)h[1] * 100.0);
     return 0;

@@ -23,11 +23,11 @@ using namespace psx;
 struct BandOp {
     int n_out = 0, n_in = 0, W = 0;
     int span = 0;          // longest input span of 256 consecutive outputs (LDS staging of the contiguous pass)
-    int *start = nullptr;  // [n_out] device
-    int2 *blk = nullptr;   // [ceil(n_out/256)] device: input range [x, y) the outputs of a 256-block read (start[] is not
+    DevBuf<int> start;     // [n_out] device
+    DevBuf<int2> blk;      // [ceil(n_out/256)] device: input range [x, y) the outputs of a 256-block read (start[] is not
                            // monotonic where the reflect pad folds the axis back)
-    float *w = nullptr;    // [n_out][W] device (row-major: the axis-0 pass reads a row with scalar loads)
-    float *wT = nullptr;   // [W][n_out] device (transposed: the contiguous pass reads it coalesced)
+    DevBuf<float> w;       // [n_out][W] device (row-major: the axis-0 pass reads a row with scalar loads)
+    DevBuf<float> wT;      // [W][n_out] device (transposed: the contiguous pass reads it coalesced)
     std::vector<int> h_start;   // host copy of start[] (row tiles of the fused pair are laid out from it)
     bool stencil = false;       // every output reads start[0] + o .. with the SAME weights (a plain convolution: k_psf_tile)
     std::vector<float> h_w0;    // those weights
@@ -39,18 +39,18 @@ struct BandPair {
     bool ok = false;
     bool cheap = false;         // the tiles' halos re-read less than 30 % of the input rows (else two passes move fewer bytes)
     int RT = 0, n_rtiles = 0, mid_rows = 0, span_ld = 0;
-    int2 *r_tile = nullptr;     // [n_rtiles] device
+    DevBuf<int2> r_tile;        // [n_rtiles] device
     size_t lds = 0;
 };
 
 struct psx_detector_plan {
-    int Nx, Ny, ov, nx, ny, margin;
+    int Nx = 0, Ny = 0, ov = 0, nx = 0, ny = 0, margin = 0;
     BandOp fx, fy, bx, by;   // front / back operator of each axis; back.n_out == 0 when there is no PSF
-    float *t1 = nullptr;     // [Nx][fy.n_out]
-    float *t2 = nullptr;     // [fx.n_out][fy.n_out]   (only with a PSF)
-    float *t3 = nullptr;     // [fx.n_out][ny]         (only with a PSF)
+    DevBuf<float> t1;        // [Nx][fy.n_out]
+    DevBuf<float> t2;        // [fx.n_out][fy.n_out]   (only with a PSF)
+    DevBuf<float> t3;        // [fx.n_out][ny]         (only with a PSF)
     BandPair front, back;    // fused (contiguous axis, axis 0) pairs; front writes t2p, back reads it
-    float *t2p = nullptr;    // [PSX_MAX_DETECT][fx.n_out][pitch2], pitch2 = fy.n_out rounded up to 4 (16-byte rows for the back
+    DevBuf<float> t2p;       // [PSX_MAX_DETECT][fx.n_out][pitch2], pitch2 = fy.n_out rounded up to 4 (16-byte rows for the back
                              // pair's loads); one per image of a psx_detect_multi_f32 launch
     int pitch2 = 0;
     size_t bytes = 0;
@@ -895,14 +895,12 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
     // Detector.resize uses the axis-0 factor on both axes (DET:192); require the grids to agree with it
     PSX_REQUIRE((Nx + 2 * margin * ov) / (nx + 2 * margin) == (Ny + 2 * margin * ov) / (ny + 2 * margin),
                 "psx_detector_plan_create: different resampling factors on the two axes");
-    psx_detector_plan *p = new psx_detector_plan();
+    std::unique_ptr<psx_detector_plan> p(new psx_detector_plan());
     p->Nx = Nx; p->Ny = Ny; p->ov = ov; p->nx = nx; p->ny = ny; p->margin = margin;
     int rc = 0;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        PSX_HIP(hipMalloc(dst, bytes));
-        PSX_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        p->bytes += bytes;
-        return 0;
+    auto up = [&](auto &dst, const auto &src) -> int {      // a host vector into its device buffer
+        p->bytes += sizeof(src[0]) * src.size();
+        return dst.upload(src.data(), src.size());
     };
     auto build = [&](BandOp &op, int N, int n, int stage) -> int {
         std::vector<int> st;
@@ -931,25 +929,23 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
             blk.push_back(make_int2(lo, hi + op.W));
             op.span = std::max(op.span, hi + op.W - lo);
         }
-        if (int e = up((void **)&op.blk, blk.data(), sizeof(int2) * blk.size())) return e;
-        if (int e = up((void **)&op.start, st.data(), sizeof(int) * st.size())) return e;
-        if (int e = up((void **)&op.w, w.data(), sizeof(float) * w.size())) return e;
-        return up((void **)&op.wT, wT.data(), sizeof(float) * wT.size());
+        if (int e = up(op.blk, blk)) return e;
+        if (int e = up(op.start, st)) return e;
+        if (int e = up(op.w, w)) return e;
+        return up(op.wT, wT);
     };
     const bool psf = sigma_psf != 0.0;
     if (!rc) rc = build(p->fx, Nx, nx, psf ? STAGE_FRONT : STAGE_ALL);
     if (!rc) rc = build(p->fy, Ny, ny, psf ? STAGE_FRONT : STAGE_ALL);
     if (!rc && psf) rc = build(p->bx, Nx, nx, STAGE_BACK);
     if (!rc && psf) rc = build(p->by, Ny, ny, STAGE_BACK);
-    auto scratch = [&](float **dst, size_t elems) -> int {
-        hipError_t e = hipMalloc((void **)dst, sizeof(float) * elems);
-        if (e != hipSuccess) return fail((int)e, "psx_detector_plan_create: hipMalloc(scratch) failed: %s", hipGetErrorString(e));
+    auto scratch = [&](DevBuf<float> &dst, size_t elems) -> int {
         p->bytes += sizeof(float) * elems;
-        return 0;
+        return dst.alloc(elems);
     };
-    if (!rc) rc = scratch(&p->t1, (size_t)Nx * (size_t)p->fy.n_out);
-    if (!rc && psf) rc = scratch(&p->t2, (size_t)p->fx.n_out * (size_t)p->fy.n_out);
-    if (!rc && psf) rc = scratch(&p->t3, (size_t)p->fx.n_out * (size_t)ny);
+    if (!rc) rc = scratch(p->t1, (size_t)Nx * (size_t)p->fy.n_out);
+    if (!rc && psf) rc = scratch(p->t2, (size_t)p->fx.n_out * (size_t)p->fy.n_out);
+    if (!rc && psf) rc = scratch(p->t3, (size_t)p->fx.n_out * (size_t)ny);
     // the fused (contiguous axis, axis 0) pairs: tiles of RT output rows, the largest RT whose LDS footprint leaves four
     // workgroups per CU; a geometry that does not fit (very wide bands) keeps the four-pass form
     auto pair = [&](BandPair &pr, const BandOp &C, const BandOp &R) -> int {
@@ -976,7 +972,7 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
             if (lds > 64 * 1024) return 0;
             pr.RT = RT; pr.n_rtiles = (int)tiles.size(); pr.mid_rows = mid; pr.lds = lds;
             pr.cheap = (double)rows_read <= 1.3 * (double)R.n_in;
-            if (int e = up((void **)&pr.r_tile, tiles.data(), sizeof(int2) * tiles.size())) return e;
+            if (int e = up(pr.r_tile, tiles)) return e;
             pr.ok = true;
             return 0;
         }
@@ -985,12 +981,9 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
     if (!rc) rc = pair(p->front, p->fy, p->fx);
     if (!rc && psf) rc = pair(p->back, p->by, p->bx);
     p->pitch2 = (p->fy.n_out + 3) / 4 * 4;
-    if (!rc && psf && p->back.ok) rc = scratch(&p->t2p, (size_t)PSX_MAX_DETECT * (size_t)p->fx.n_out * (size_t)p->pitch2);
-    if (rc) {
-        psx_detector_plan_destroy(p);
-        return rc;
-    }
-    *plan = p;
+    if (!rc && psf && p->back.ok) rc = scratch(p->t2p, (size_t)PSX_MAX_DETECT * (size_t)p->fx.n_out * (size_t)p->pitch2);
+    if (rc) return rc;
+    *plan = p.release();
     return 0;
 }
 
@@ -1011,19 +1004,6 @@ int psx_detector_operator_host(int N, int ov, int n, int margin, double sigma_sr
 }
 
 int psx_detector_plan_destroy(psx_detector_plan *p) {
-    if (!p) return 0;
-    for (BandOp *op : {&p->fx, &p->fy, &p->bx, &p->by}) {
-        (void)hipFree(op->start);
-        (void)hipFree(op->blk);
-        (void)hipFree(op->w);
-        (void)hipFree(op->wT);
-    }
-    (void)hipFree(p->t1);
-    (void)hipFree(p->t2);
-    (void)hipFree(p->t3);
-    (void)hipFree(p->t2p);
-    (void)hipFree(p->front.r_tile);
-    (void)hipFree(p->back.r_tile);
     delete p;
     return 0;
 }
@@ -1049,7 +1029,7 @@ int band_cols(const BandOp &op, const float *in, float *out, int R, hipStream_t 
         const int span_ld = (op.span + 3 + 3 + 4) / 4 * 4;      // + alignment slack of the block's first input, whole float4s
         const size_t lds = sizeof(float) * RG8 * (size_t)span_ld;
 #define PSX_BAND_COLS_V4(WMAX)                                                                                          \
-    PSX_TIMED("k_band_cols", st, k_band_cols_v4<WMAX, MIT><<<grid, 256, lds, st>>>(in, out, op.start, op.blk, op.wT, R, \
+    PSX_TIMED("k_band_cols", st, k_band_cols_v4<WMAX, MIT><<<grid, 256, lds, st>>>(in, out, op.start.get(), op.blk.get(), op.wT.get(), R, \
                                                                                      op.n_in, op.n_out, op.W, span_ld, per))
         if (op.W <= 8) PSX_BAND_COLS_V4(8);
         else if (op.W <= 16) PSX_BAND_COLS_V4(16);
@@ -1066,7 +1046,7 @@ int band_cols(const BandOp &op, const float *in, float *out, int R, hipStream_t 
     const size_t lds = sizeof(float) * RG * (size_t)span_ld;
     PSX_REQUIRE(lds <= 64 * 1024, "detector: oversampling %d needs %zu bytes of LDS per row strip", op.span / 256, lds);
 #define PSX_BAND_COLS(WMAX)                                                                                            \
-    PSX_TIMED("k_band_cols", st, k_band_cols<WMAX, RG><<<grid, 256, lds, st>>>(in, out, op.start, op.blk, op.wT, R, op.n_in, \
+    PSX_TIMED("k_band_cols", st, k_band_cols<WMAX, RG><<<grid, 256, lds, st>>>(in, out, op.start.get(), op.blk.get(), op.wT.get(), R, op.n_in, \
                                                                                  op.n_out, op.W, span_ld, per))
     if (op.W <= 8) PSX_BAND_COLS(8);
     else if (op.W <= 16) PSX_BAND_COLS(16);
@@ -1083,7 +1063,7 @@ int band_rows(const BandOp &op, const float *in, float *out, int C, hipStream_t 
     const int per = strip_rows(op.n_out, cb);
     const dim3 grid(cb, (op.n_out + per - 1) / per);
 #define PSX_BAND_ROWS(WMAX, RB)                                                                                          \
-    PSX_TIMED("k_band_rows", st, k_band_rows<WMAX, RB><<<grid, 256, 0, st>>>(in, out, op.start, op.w, op.n_in, op.n_out, \
+    PSX_TIMED("k_band_rows", st, k_band_rows<WMAX, RB><<<grid, 256, 0, st>>>(in, out, op.start.get(), op.w.get(), op.n_in, op.n_out, \
                                                                              C, op.W, per))
     if (op.W <= 4) PSX_BAND_ROWS(4, 8);
     else if (op.W <= 8) PSX_BAND_ROWS(8, 4);
@@ -1105,9 +1085,9 @@ int band_pair(const BandPair &pr, const BandOp &C, const BandOp &R, const float 
         a.out[k] = out[std::min(k, nimg - 1)];
     }
     a.in_pitch = in_pitch; a.out_pitch = out_pitch;
-    a.c_start = C.start; a.c_blk = C.blk; a.c_wT = C.wT; a.c_W = C.W; a.Cin = C.n_in; a.Cout = C.n_out;
-    a.r_start = R.start; a.r_w = R.w; a.r_W = R.W; a.Rin = R.n_in; a.Rout = R.n_out;
-    a.r_tile = pr.r_tile; a.RT = pr.RT; a.n_rtiles = pr.n_rtiles; a.span_ld = pr.span_ld; a.mid_rows = pr.mid_rows;
+    a.c_start = C.start.get(); a.c_blk = C.blk.get(); a.c_wT = C.wT.get(); a.c_W = C.W; a.Cin = C.n_in; a.Cout = C.n_out;
+    a.r_start = R.start.get(); a.r_w = R.w.get(); a.r_W = R.W; a.Rin = R.n_in; a.Rout = R.n_out;
+    a.r_tile = pr.r_tile.get(); a.RT = pr.RT; a.n_rtiles = pr.n_rtiles; a.span_ld = pr.span_ld; a.mid_rows = pr.mid_rows;
     // column blocks x row strips x images; a workgroup walks the row tiles of its strip (its column set-up is done once), and
     // the launch as a whole fills the chip once whatever the number of images
     const int cb = (C.n_out + 255) / 256;
@@ -1165,7 +1145,7 @@ static int detect_impl(psx_detector_plan *p, const float *const *imgs, float *co
     const bool back_f = allowed && psf && p->back.ok && p->t2p && (front_f || p->pitch2 == p->fy.n_out);
     if (nimg > 1 && front_f && (back_f || !psf)) {
         float *mids[PSX_MAX_DETECT];
-        for (int k = 0; k < nimg; ++k) mids[k] = p->t2p + (size_t)k * p->fx.n_out * p->pitch2;
+        for (int k = 0; k < nimg; ++k) mids[k] = p->t2p.get() + (size_t)k * p->fx.n_out * p->pitch2;
         if (!psf) return band_pair(p->front, p->fy, p->fx, imgs, p->Ny, outs, p->fy.n_out, nimg, st);
         if (int rc = band_pair(p->front, p->fy, p->fx, imgs, p->Ny, mids, p->pitch2, nimg, st)) return rc;
         if (psf_stencil_ok(p->by, p->bx)) return psf_tile(p->by, p->bx, mids, p->pitch2, outs, p->ny, nimg, st);
@@ -1174,15 +1154,15 @@ static int detect_impl(psx_detector_plan *p, const float *const *imgs, float *co
     for (int k = 0; k < nimg; ++k) {
         const float *img = imgs[k];
         float *out = outs[k];
-        float *mid_img = back_f ? p->t2p : p->t2;
+        float *mid_img = back_f ? p->t2p.get() : p->t2.get();
         const int mid_pitch = back_f ? p->pitch2 : p->fy.n_out;
         float *front_out = psf ? mid_img : out;
         if (front_f) {
             if (int rc = band_pair(p->front, p->fy, p->fx, &img, p->Ny, &front_out, psf ? mid_pitch : p->fy.n_out, 1, st)) return rc;
         } else {
             // contiguous axis first (the only pass over the full-resolution image), then axis 0
-            if (int rc = band_cols(p->fy, img, p->t1, p->Nx, st)) return rc;
-            if (int rc = band_rows(p->fx, p->t1, front_out, p->fy.n_out, st)) return rc;
+            if (int rc = band_cols(p->fy, img, p->t1.get(), p->Nx, st)) return rc;
+            if (int rc = band_rows(p->fx, p->t1.get(), front_out, p->fy.n_out, st)) return rc;
         }
         if (!psf) continue;
         // back operator (PSF + crop) at detector resolution
@@ -1194,8 +1174,8 @@ static int detect_impl(psx_detector_plan *p, const float *const *imgs, float *co
             }
             continue;
         }
-        if (int rc = band_cols(p->by, p->t2, p->t3, p->fx.n_out, st)) return rc;
-        if (int rc = band_rows(p->bx, p->t3, out, p->ny, st)) return rc;
+        if (int rc = band_cols(p->by, p->t2.get(), p->t3.get(), p->fx.n_out, st)) return rc;
+        if (int rc = band_rows(p->bx, p->t3.get(), out, p->ny, st)) return rc;
     }
     return 0;
 }

@@ -84,58 +84,31 @@ int rocfft_ensure_setup() {
 }
 
 int rocfft_engine_create(psx_fresnel_plan *p) {
-    if (int rc = rocfft_ensure_setup()) return rc;
-    RocfftEngine *e = new RocfftEngine();
-    p->rf = e;
+    p->rf = std::make_unique<RocfftEngine>();
+    RocfftEngine *e = p->rf.get();
     const size_t lengths[2] = {(size_t)p->Py, (size_t)p->Px};   // rocFFT lengths are fastest-first
-    PSX_ROCFFT(rocfft_plan_create(&e->fwd, rocfft_placement_inplace, rocfft_transform_type_complex_forward,
-                                  rocfft_precision_single, 2, lengths, 1, nullptr));
-    PSX_ROCFFT(rocfft_plan_create(&e->inv, rocfft_placement_inplace, rocfft_transform_type_complex_inverse,
-                                  rocfft_precision_single, 2, lengths, 1, nullptr));
-    size_t wf = 0, wi = 0;
-    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(e->fwd, &wf));
-    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(e->inv, &wi));
-    e->work_bytes = wf > wi ? wf : wi;
-    PSX_ROCFFT(rocfft_execution_info_create(&e->info));
-    if (e->work_bytes) {
-        PSX_HIP(hipMalloc(&e->work, e->work_bytes));
-        PSX_ROCFFT(rocfft_execution_info_set_work_buffer(e->info, e->work, e->work_bytes));
-    }
-    const size_t img = sizeof(float2) * (size_t)p->Px * (size_t)p->Py;
-    PSX_HIP(hipMalloc((void **)&e->spec, img));
-    PSX_HIP(hipMalloc((void **)&e->prod, img));
-    PSX_HIP(hipMalloc((void **)&e->cx, sizeof(float2) * (size_t)p->Px));
-    PSX_HIP(hipMalloc((void **)&e->cy, sizeof(float2) * (size_t)p->Py));
-    p->bytes += 2 * img + e->work_bytes + sizeof(float2) * (size_t)(p->Px + p->Py);
+    if (int rc = e->fft.create(FftPlan::BOTH, rocfft_precision_single, 2, lengths)) return rc;
+    const size_t npad = (size_t)p->Px * (size_t)p->Py;
+    if (int rc = e->spec.alloc(npad)) return rc;
+    if (int rc = e->prod.alloc(npad)) return rc;
+    if (int rc = e->cx.alloc((size_t)p->Px)) return rc;
+    if (int rc = e->cy.alloc((size_t)p->Py)) return rc;
+    p->bytes += e->spec.bytes() + e->prod.bytes() + e->fft.work_bytes() + e->cx.bytes() + e->cy.bytes();
     return 0;
 }
 
-void rocfft_engine_destroy(psx_fresnel_plan *p) {
-    RocfftEngine *e = p->rf;
-    if (!e) return;
-    if (e->fwd) rocfft_plan_destroy(e->fwd);
-    if (e->inv) rocfft_plan_destroy(e->inv);
-    if (e->info) rocfft_execution_info_destroy(e->info);
-    (void)hipFree(e->work);
-    (void)hipFree(e->spec);
-    (void)hipFree(e->prod);
-    (void)hipFree(e->cx);
-    (void)hipFree(e->cy);
-    delete e;
-    p->rf = nullptr;
-}
-
 int rocfft_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
-    RocfftEngine *e = p->rf;
+    RocfftEngine *e = p->rf.get();
     hipStream_t st = a.stream;
+    float2 *const spec = e->spec.get(), *const prod = e->prod.get(), *const cx = e->cx.get(), *const cy = e->cy.get();
     const int64_t npad = (int64_t)p->Px * p->Py, n = (int64_t)p->Nx * p->Ny;
-    PSX_DISPATCH_NMAT(a.m.n, PSX_TIMED("k_pad_transmit", st, k_pad_transmit<NM><<<ew_grid(npad, 256), 256, 0, st>>>(a.wave_in, a.amp, a.m, e->spec, p->Nx, p->Ny, p->margin, p->Px,
+    PSX_DISPATCH_NMAT(a.m.n, PSX_TIMED("k_pad_transmit", st, k_pad_transmit<NM><<<ew_grid(npad, 256), 256, 0, st>>>(a.wave_in, a.amp, a.m, spec, p->Nx, p->Ny, p->margin, p->Px,
                                                       p->Py)));
     if (int rc = launch_check("k_pad_transmit")) return rc;
     bool need_fft = false;
     for (int d = 0; d < a.n_dist; ++d) {
         if (a.a[d] == 0.0) {   // z == 0: the reference returns its input untouched (EXP:233-234)
-            PSX_TIMED("k_crop_out", st, k_crop_out<<<ew_grid(n, 256), 256, 0, st>>>(e->spec, a.wave_out ? a.wave_out[d] : nullptr,
+            PSX_TIMED("k_crop_out", st, k_crop_out<<<ew_grid(n, 256), 256, 0, st>>>(spec, a.wave_out ? a.wave_out[d] : nullptr,
                                                         a.inten_out ? a.inten_out[d] : nullptr,
                                                         a.inten_scale ? a.inten_scale[d] : 1.f, a.accumulate, p->Nx,
                                                         p->Ny, p->margin, p->Py));
@@ -145,29 +118,20 @@ int rocfft_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
         }
     }
     if (!need_fft) return 0;
-    PSX_ROCFFT(rocfft_execution_info_set_stream(e->info, st));
-    void *buf[1] = {e->spec};
-    {
-        ProfScope ps("rocfft_forward", st);
-        PSX_ROCFFT(rocfft_execute(e->fwd, buf, nullptr, e->info));
-    }
+    if (int rc = e->fft.execute(FftPlan::FWD, spec, st, "rocfft_forward")) return rc;
     const double norm = 1.0 / ((double)p->Px * (double)p->Py);
     for (int d = 0; d < a.n_dist; ++d) {
         if (a.a[d] == 0.0) continue;
         const double g = a.gphase ? a.gphase[d] : 0.0;
         // k*z/M is ~1e11 rad: libm's cos/sin reduce the float64 argument exactly (as numpy does for EXP:250);
         // a remainder by a rounded 2*pi would already be off by 1e-5 rad
-        PSX_TIMED("k_chirp_table", st, k_chirp_table<<<(int)cdiv(p->Px, 256), 256, 0, st>>>(e->cx, p->Px, a.a[d], a.du_x, norm * std::cos(g),
+        PSX_TIMED("k_chirp_table", st, k_chirp_table<<<(int)cdiv(p->Px, 256), 256, 0, st>>>(cx, p->Px, a.a[d], a.du_x, norm * std::cos(g),
                                                              norm * std::sin(g)));
-        PSX_TIMED("k_chirp_table", st, k_chirp_table<<<(int)cdiv(p->Py, 256), 256, 0, st>>>(e->cy, p->Py, a.a[d], a.du_y, 1.0, 0.0));
-        PSX_TIMED("k_chirp_mul", st, k_chirp_mul<<<ew_grid(npad, 256), 256, 0, st>>>(e->spec, e->cx, e->cy, e->prod, p->Px, p->Py));
+        PSX_TIMED("k_chirp_table", st, k_chirp_table<<<(int)cdiv(p->Py, 256), 256, 0, st>>>(cy, p->Py, a.a[d], a.du_y, 1.0, 0.0));
+        PSX_TIMED("k_chirp_mul", st, k_chirp_mul<<<ew_grid(npad, 256), 256, 0, st>>>(spec, cx, cy, prod, p->Px, p->Py));
         if (int rc = launch_check("k_chirp_mul")) return rc;
-        void *pb[1] = {e->prod};
-        {
-            ProfScope ps("rocfft_inverse", st);
-            PSX_ROCFFT(rocfft_execute(e->inv, pb, nullptr, e->info));
-        }
-        PSX_TIMED("k_crop_out", st, k_crop_out<<<ew_grid(n, 256), 256, 0, st>>>(e->prod, a.wave_out ? a.wave_out[d] : nullptr,
+        if (int rc = e->fft.execute(FftPlan::INV, prod, st, "rocfft_inverse")) return rc;
+        PSX_TIMED("k_crop_out", st, k_crop_out<<<ew_grid(n, 256), 256, 0, st>>>(prod, a.wave_out ? a.wave_out[d] : nullptr,
                                                     a.inten_out ? a.inten_out[d] : nullptr,
                                                     a.inten_scale ? a.inten_scale[d] : 1.f, a.accumulate, p->Nx, p->Ny,
                                                     p->margin, p->Py));
@@ -193,22 +157,15 @@ int psx_fresnel_plan_create(int Nx, int Ny, int margin, int max_dist, int engine
     if (engine == PSX_ENGINE_AUTO) engine = lds_engine_supported(Nx, Ny, margin) ? PSX_ENGINE_LDS : PSX_ENGINE_ROCFFT;
     if (engine == PSX_ENGINE_LDS && !lds_engine_supported(Nx, Ny, margin))
         return fail(PSX_E_UNSUPPORTED, "psx_fresnel_plan_create: LDS engine cannot hold a %dx%d grid row in LDS", Nx, Ny);
-    psx_fresnel_plan *p = new psx_fresnel_plan();
+    std::unique_ptr<psx_fresnel_plan> p(new psx_fresnel_plan());
     p->Nx = Nx; p->Ny = Ny; p->margin = margin; p->Px = Nx + 2 * margin; p->Py = Ny + 2 * margin;
-    p->max_dist = max_dist; p->engine = engine; p->bytes = 0; p->rf = nullptr; p->lds = nullptr;
-    int rc = engine == PSX_ENGINE_LDS ? lds_engine_create(p) : rocfft_engine_create(p);
-    if (rc) {
-        psx_fresnel_plan_destroy(p);
-        return rc;
-    }
-    *plan = p;
+    p->max_dist = max_dist; p->engine = engine;
+    if (int rc = engine == PSX_ENGINE_LDS ? lds_engine_create(p.get()) : rocfft_engine_create(p.get())) return rc;
+    *plan = p.release();
     return 0;
 }
 
 int psx_fresnel_plan_destroy(psx_fresnel_plan *p) {
-    if (!p) return 0;
-    rocfft_engine_destroy(p);
-    lds_engine_destroy(p);
     delete p;
     return 0;
 }
@@ -267,19 +224,8 @@ int psx_fresnel_propagate_sources(psx_fresnel_plan *plan, int n_src, int n_dist,
     sa.wave_out = (float2 *const *)wave_out; sa.inten_out = inten_out; sa.inten_scale = inten_scale;
     sa.stream = (hipStream_t)stream;
     if (plan->engine == PSX_ENGINE_LDS) return lds_engine_propagate_sources(plan, sa);
-    for (int s = 0; s < n_src; ++s) {                    // rocFFT engine: one source at a time
-        PropArgs pa;
-        if (int rc = pack_mats(pa.m, T, cphase ? cphase + (size_t)s * nmat : nullptr, catt ? catt + (size_t)s * nmat : nullptr, nmat))
-            return rc;
-        pa.wave_in = wave_in ? (const float2 *)wave_in[s] : nullptr; pa.amp = amp[s]; pa.n_dist = n_dist;
-        pa.a = a + (size_t)s * n_dist; pa.gphase = gphase ? gphase + (size_t)s * n_dist : nullptr;
-        pa.du_x = du_x; pa.du_y = du_y;
-        pa.wave_out = wave_out ? (float2 *const *)wave_out + (size_t)s * n_dist : nullptr;
-        pa.inten_out = inten_out ? inten_out + (size_t)s * n_dist : nullptr;
-        pa.inten_scale = inten_scale ? inten_scale + (size_t)s * n_dist : nullptr;
-        pa.accumulate = 0; pa.stream = (hipStream_t)stream;
-        if (int rc = rocfft_engine_propagate(plan, pa)) return rc;
-    }
+    for (int s = 0; s < n_src; ++s)                      // rocFFT engine: one source at a time
+        if (int rc = rocfft_engine_propagate(plan, slice_source(sa, s))) return rc;
     return 0;
 }
 

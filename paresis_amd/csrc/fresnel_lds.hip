@@ -1523,20 +1523,17 @@ namespace psx {
 
 struct AxisTables : AxisKind {
     int N = 0;
-    float2 *w2 = nullptr;                           // DIF, PAIR, P2X: slab twiddles
-    float2 *w4 = nullptr;                           // DIF, P2X: thread factors of the radix-2 split
-    float2 *twA = nullptr, *twB = nullptr;
+    DevBuf<float2> w2;                              // DIF, PAIR, P2X: slab twiddles
+    DevBuf<float2> w4;                              // DIF, P2X: thread factors of the radix-2 split
+    DevBuf<float2> twA, twB;
     // float64 transforms of the kernel-spectrum build: taps = IDFT_P(chirp), spectrum = FFT_M(zero-padded taps) x S segments
-    rocfft_plan planP = nullptr, planM = nullptr;
-    rocfft_execution_info infoP = nullptr, infoM = nullptr;
-    void *workP = nullptr, *workM = nullptr;
-    double2 *bufP = nullptr, *bufM = nullptr;       // [P] chirp / taps, [S][M] padded taps / spectra
+    FftPlan planP, planM;                           // each with its own execution info and work buffer
+    DevBuf<double2> bufP, bufM;                     // [P] chirp / taps, [S][M] padded taps / spectra
 };
 
 struct KernEntry {
-    float2 *H;          // S spectra of M points (power-of-two lines: M points + the first taps, p2::spectrum_elems)
+    DevBuf<float2> H;   // S spectra of M points (power-of-two lines: M points + the first taps, p2::spectrum_elems)
     int M, S;
-    size_t elems;       // float2 elements allocated
     unsigned long long stamp;
 };
 
@@ -1545,16 +1542,16 @@ typedef std::tuple<double, double, int, int> KernKey;   // (a, du, N, M)
 
 struct LdsEngine {
     AxisTables ax[2];            // [0]: lines along axis 0 (length Nx), [1]: along axis 1 (length Ny)
-    float2 *inter = nullptr;     // [max_dist][Nx/IB][Ny][IB] intermediates (pass-1 line y, sample x)
+    DevBuf<float2> inter;        // [max_dist][Nx/IB][Ny][IB] intermediates (pass-1 line y, sample x)
     size_t inter_elems = 0;
-    float2 *pre = nullptr;       // [Ny][Nx] transmitted source wave, transposed (pass 0)
-    float2 *part = nullptr;      // [max_dist][Nx][Ny] partial sums of pass 2 of the partitioned convolution when only |.|^2 is wanted
-    float2 *wgpart = nullptr;    // [CUs][Mconv]: DIF rounds park the even half's result of a line here (one buffer per workgroup)
+    DevBuf<float2> pre;          // [Ny][Nx] transmitted source wave, transposed (pass 0)
+    DevBuf<float2> part;         // [max_dist][Nx][Ny] partial sums of pass 2 of the partitioned convolution when only |.|^2 is wanted
+    DevBuf<float2> wgpart;       // [CUs][Mconv]: DIF rounds park the even half's result of a line here (one buffer per workgroup)
     int wgpart_groups = 0;
-    unsigned *queue = nullptr;   // [2][QUEUE_WORDS]: work queues of pass 1 and pass 2 (zero between launches: the kernels re-arm them)
+    DevBuf<unsigned> queue;      // [2][QUEUE_WORDS]: work queues of pass 1 and pass 2 (zero between launches: the kernels re-arm them)
     bool use_queue = false;      // psx_fresnel_plan_work_queue
-    float2 *pre_b = nullptr;     // [PSX_MAX_SRC][Ny][Nx], [MAX_LINE][inter_elems]: the same two for a batch of source waves,
-    float2 *inter_b = nullptr;   // allocated by the first batched call (psx_fresnel_propagate_sources)
+    DevBuf<float2> pre_b;        // [PSX_MAX_SRC][Ny][Nx], [MAX_LINE][inter_elems]: the same two for a batch of source waves,
+    DevBuf<float2> inter_b;      // allocated together by the first batched call (psx_fresnel_propagate_sources)
     // Kernel spectra, keyed by (a, du, N, M).  72 KiB each at 4096^2: the cache is sized for a polychromatic position
     // (energies x hops x axes: 25 x 3 x 2 = 150 keys visited cyclically -- an LRU smaller than that misses on EVERY lookup),
     // i.e. effectively unbounded; CACHE_CAP only bounds the memory of a plan fed with ever-changing scalars.
@@ -1563,6 +1560,13 @@ struct LdsEngine {
     unsigned long long clock = 0;
 };
 constexpr size_t CACHE_CAP_BYTES = (size_t)1 << 30;
+
+}  // namespace psx
+
+psx_fresnel_plan::psx_fresnel_plan() = default;
+psx_fresnel_plan::~psx_fresnel_plan() = default;
+
+namespace psx {
 
 void lds_engine_work_queue(psx_fresnel_plan *p, int on) {
     if (p->lds) p->lds->use_queue = on != 0;
@@ -1592,81 +1596,64 @@ bool lds_engine_supported(int Nx, int Ny, int margin) {
 static int make_axis(AxisTables &t, int N, int margin, size_t &bytes) {
     t.N = N;
     static_cast<AxisKind &>(t) = choose(N, margin, debug_switch(DBG_NO_P2) != 0);
-    auto table = [&](float2 *&buf, size_t n) {
+    auto table = [&](DevBuf<float2> &buf, size_t n) {
         bytes += sizeof(float2) * n;
-        return hipMalloc((void **)&buf, sizeof(float2) * n);
+        return buf.alloc(n);
     };
     const int S1 = t.M / RAD;
     switch (t.kind) {
         case Kind::P2X:
-            PSX_HIP(table(t.w2, 512));
-            PSX_HIP(table(t.w4, 512));
-            if (int rc = p2::x_build_twiddles(t.w2, t.w4, nullptr)) return rc;
+            if (int rc = table(t.w2, 512)) return rc;
+            if (int rc = table(t.w4, 512)) return rc;
+            if (int rc = p2::x_build_twiddles(t.w2.get(), t.w4.get(), nullptr)) return rc;
             [[fallthrough]];
         case Kind::P2:
-            PSX_HIP(table(t.twA, p2::twA_elems(t.radix)));
-            PSX_HIP(table(t.twB, p2::twB_elems()));
-            if (int rc = p2::build_tables(t.twA, t.twB, t.radix, nullptr)) return rc;
+            if (int rc = table(t.twA, p2::twA_elems(t.radix))) return rc;
+            if (int rc = table(t.twB, p2::twB_elems())) return rc;
+            if (int rc = p2::build_tables(t.twA.get(), t.twB.get(), t.radix, nullptr)) return rc;
             break;
         case Kind::DIF:
-            PSX_HIP(table(t.w4, 2 * S1));
-            k_dif_twiddles<<<(int)cdiv(2 * S1, 256), 256>>>(t.w4, t.M);
+            if (int rc = table(t.w4, 2 * S1)) return rc;
+            k_dif_twiddles<<<(int)cdiv(2 * S1, 256), 256>>>(t.w4.get(), t.M);
             if (int rc = launch_check("k_dif_twiddles")) return rc;
             [[fallthrough]];
         case Kind::PAIR:
-            PSX_HIP(table(t.w2, t.M / t.radix));
-            k_pair_twiddles<<<(int)cdiv(t.M / t.radix, 256), 256>>>(t.w2, t.M, t.radix);
+            if (int rc = table(t.w2, t.M / t.radix)) return rc;
+            k_pair_twiddles<<<(int)cdiv(t.M / t.radix, 256), 256>>>(t.w2.get(), t.M, t.radix);
             if (int rc = launch_check("k_pair_twiddles")) return rc;
             [[fallthrough]];
         case Kind::R3:
-            PSX_HIP(table(t.twA, RAD * S1));
-            PSX_HIP(table(t.twB, RAD * t.radix));
-            k_stage_twiddles<<<(int)cdiv(RAD * S1, 256), 256>>>(t.twA, t.twB, t.M, t.radix);
+            if (int rc = table(t.twA, RAD * S1)) return rc;
+            if (int rc = table(t.twB, RAD * t.radix)) return rc;
+            k_stage_twiddles<<<(int)cdiv(RAD * S1, 256), 256>>>(t.twA.get(), t.twB.get(), t.M, t.radix);
             if (int rc = launch_check("k_stage_twiddles")) return rc;
             break;
     }
     // float64 transforms of the kernel-spectrum build
-    if (int rc = rocfft_ensure_setup()) return rc;
     const size_t P = (size_t)(N + 2 * margin), M = (size_t)t.Mconv;
-    PSX_ROCFFT(rocfft_plan_create(&t.planP, rocfft_placement_inplace, rocfft_transform_type_complex_inverse,
-                                  rocfft_precision_double, 1, &P, 1, nullptr));
-    PSX_ROCFFT(rocfft_plan_create(&t.planM, rocfft_placement_inplace, rocfft_transform_type_complex_forward,
-                                  rocfft_precision_double, 1, &M, (size_t)t.S, nullptr));
-    size_t wP = 0, wM = 0;
-    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(t.planP, &wP));
-    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(t.planM, &wM));
-    PSX_ROCFFT(rocfft_execution_info_create(&t.infoP));
-    PSX_ROCFFT(rocfft_execution_info_create(&t.infoM));
-    if (wP) {
-        PSX_HIP(hipMalloc(&t.workP, wP));
-        PSX_ROCFFT(rocfft_execution_info_set_work_buffer(t.infoP, t.workP, wP));
-    }
-    if (wM) {
-        PSX_HIP(hipMalloc(&t.workM, wM));
-        PSX_ROCFFT(rocfft_execution_info_set_work_buffer(t.infoM, t.workM, wM));
-    }
-    PSX_HIP(hipMalloc((void **)&t.bufP, sizeof(double2) * P));
-    PSX_HIP(hipMalloc((void **)&t.bufM, sizeof(double2) * M * t.S));
-    bytes += wP + wM + sizeof(double2) * (P + M * t.S);
+    if (int rc = t.planP.create(FftPlan::INV, rocfft_precision_double, 1, &P)) return rc;
+    if (int rc = t.planM.create(FftPlan::FWD, rocfft_precision_double, 1, &M, (size_t)t.S)) return rc;
+    if (int rc = t.bufP.alloc(P)) return rc;
+    if (int rc = t.bufM.alloc(M * t.S)) return rc;
+    bytes += t.planP.work_bytes() + t.planM.work_bytes() + t.bufP.bytes() + t.bufM.bytes();
     return 0;
 }
 
 int lds_engine_create(psx_fresnel_plan *p) {
-    LdsEngine *e = new LdsEngine();
-    p->lds = e;
+    p->lds = std::make_unique<LdsEngine>();
+    LdsEngine *e = p->lds.get();
     if (int rc = make_axis(e->ax[0], p->Nx, p->margin, p->bytes)) return rc;
     if (int rc = make_axis(e->ax[1], p->Ny, p->margin, p->bytes)) return rc;
     e->inter_elems = (size_t)cdiv(p->Nx, IB) * IB * (size_t)p->Ny;   // blocked layout [Nx/IB][Ny][IB]
-    const size_t img = sizeof(float2) * e->inter_elems;
-    PSX_HIP(hipMalloc((void **)&e->inter, img * p->max_dist));
-    p->bytes += img * p->max_dist;
+    if (int rc = e->inter.alloc(e->inter_elems * p->max_dist)) return rc;
+    p->bytes += e->inter.bytes();
     // every buffer a propagate call needs exists from here on: the call itself allocates nothing but kernel spectra it
     // has not seen yet (and refuses to do that while its stream is being captured into a graph)
     const size_t npix = (size_t)p->Nx * p->Ny;
-    PSX_HIP(hipMalloc((void **)&e->pre, sizeof(float2) * npix));
-    p->bytes += sizeof(float2) * npix;
-    PSX_HIP(hipMalloc((void **)&e->queue, sizeof(unsigned) * 2 * QUEUE_WORDS));
-    PSX_HIP(hipMemset(e->queue, 0, sizeof(unsigned) * 2 * QUEUE_WORDS));
+    if (int rc = e->pre.alloc(npix)) return rc;
+    p->bytes += e->pre.bytes();
+    if (int rc = e->queue.alloc(2 * QUEUE_WORDS)) return rc;
+    PSX_HIP(hipMemset(e->queue.get(), 0, e->queue.bytes()));
     // the two-round kinds park a line's first round per workgroup: DIF 2 * PART_M points, P2X 2 * 16384 (ye and round O's
     // input); one buffer serves both axes.  PAIR with several segments in pass 2: complex partial sums when only |.|^2 leaves
     size_t per_wg = 0;
@@ -1675,44 +1662,15 @@ int lds_engine_create(psx_fresnel_plan *p) {
             per_wg = std::max({per_wg, (size_t)2 * PART_M, t.kind == Kind::P2X ? p2::x_line_buffer_elems() : (size_t)0});
     if (per_wg) {
         e->wgpart_groups = current_cu_count();
-        PSX_HIP(hipMalloc((void **)&e->wgpart, sizeof(float2) * per_wg * (size_t)e->wgpart_groups));
-        p->bytes += sizeof(float2) * per_wg * (size_t)e->wgpart_groups;
+        if (int rc = e->wgpart.alloc(per_wg * (size_t)e->wgpart_groups)) return rc;
+        p->bytes += e->wgpart.bytes();
     }
     if (e->ax[1].kind == Kind::PAIR && e->ax[1].S > 1) {
-        PSX_HIP(hipMalloc((void **)&e->part, sizeof(float2) * npix * p->max_dist));
-        p->bytes += sizeof(float2) * npix * p->max_dist;
+        if (int rc = e->part.alloc(npix * p->max_dist)) return rc;
+        p->bytes += e->part.bytes();
     }
     PSX_HIP(hipDeviceSynchronize());
     return 0;
-}
-
-void lds_engine_destroy(psx_fresnel_plan *p) {
-    LdsEngine *e = p->lds;
-    if (!e) return;
-    for (auto &t : e->ax) {
-        (void)hipFree(t.twA);
-        (void)hipFree(t.twB);
-        (void)hipFree(t.w2);
-        (void)hipFree(t.w4);
-        if (t.planP) rocfft_plan_destroy(t.planP);
-        if (t.planM) rocfft_plan_destroy(t.planM);
-        if (t.infoP) rocfft_execution_info_destroy(t.infoP);
-        if (t.infoM) rocfft_execution_info_destroy(t.infoM);
-        (void)hipFree(t.workP);
-        (void)hipFree(t.workM);
-        (void)hipFree(t.bufP);
-        (void)hipFree(t.bufM);
-    }
-    for (auto &k : e->cache) (void)hipFree(k.second.H);
-    (void)hipFree(e->inter);
-    (void)hipFree(e->pre);
-    (void)hipFree(e->part);
-    (void)hipFree(e->wgpart);
-    (void)hipFree(e->pre_b);
-    (void)hipFree(e->inter_b);
-    (void)hipFree(e->queue);
-    delete e;
-    p->lds = nullptr;
 }
 
 // Kernel spectrum of one (distance, axis): cached, because it depends on scalars only (the reference rebuilds its
@@ -1720,12 +1678,12 @@ void lds_engine_destroy(psx_fresnel_plan *p) {
 // intermediates -- serves ONE stream at a time (include/paresis_hip.h, thread model): stream order is then enough to keep a
 // table alive until its readers are done; the one exception, evicting a table to reuse its memory, synchronises the stream.
 static int kernel_spectrum(psx_fresnel_plan *p, AxisTables &t, double a, double du, hipStream_t st, const float2 **out) {
-    LdsEngine *e = p->lds;
+    LdsEngine *e = p->lds.get();
     const KernKey key(a, du, t.N, t.Mconv);
     auto it = e->cache.find(key);
     if (it != e->cache.end()) {
         it->second.stamp = ++e->clock;
-        *out = it->second.H;
+        *out = it->second.H.get();
         return 0;
     }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1733,69 +1691,53 @@ static int kernel_spectrum(psx_fresnel_plan *p, AxisTables &t, double a, double 
         return fail(PSX_E_STATE, "psx_fresnel_propagate: kernel spectrum (a=%g, du=%g) is not cached and cannot be built while "
                                  "the stream is being captured: run the call once outside the capture first", a, du);
     const size_t elems = t.kind == Kind::P2X ? p2::x_spectrum_elems() : (t.kind == Kind::P2 ? p2::spectrum_elems(t.radix) : (size_t)t.Mconv * t.S);
-    KernEntry k{nullptr, t.Mconv, t.S, elems, ++e->clock};
+    // The table belongs to this call until the emplace at the end: every return before it releases it, and the two byte
+    // counts cover exactly the tables in the cache.
+    DevBuf<float2> H;
     const size_t bytes = sizeof(float2) * elems;
     if (e->cache_bytes + bytes > CACHE_CAP_BYTES && !e->cache.empty()) {   // evict the least recently used table
         auto lru = e->cache.begin();
         for (auto jt = e->cache.begin(); jt != e->cache.end(); ++jt)
             if (jt->second.stamp < lru->second.stamp) lru = jt;
         PSX_HIP(hipStreamSynchronize(st));       // its last readers are done
-        if (lru->second.elems == elems) {
-            k.H = lru->second.H;
-        } else {
-            (void)hipFree(lru->second.H);
-            e->cache_bytes -= sizeof(float2) * lru->second.elems;
-        }
+        e->cache_bytes -= lru->second.H.bytes();
+        p->bytes -= lru->second.H.bytes();
+        if (lru->second.H.elems() == elems) H = std::move(lru->second.H);      // reuse its memory
         e->cache.erase(lru);
     }
-    if (!k.H) {
-        PSX_HIP(hipMalloc((void **)&k.H, bytes));
-        e->cache_bytes += bytes;
-        p->bytes += bytes;
-    }
+    if (!H)
+        if (int rc = H.alloc(elems)) return rc;
     const int P = t.N + 2 * p->margin;
-    PSX_ROCFFT(rocfft_execution_info_set_stream(t.infoP, st));
-    PSX_ROCFFT(rocfft_execution_info_set_stream(t.infoM, st));
-    PSX_TIMED("k_kern_H", st, k_kern_H<<<(int)cdiv(P, 256), 256, 0, st>>>(t.bufP, P, a, du));
-    {
-        ProfScope ps("kern_ifft_P", st);
-        void *buf = t.bufP;
-        PSX_ROCFFT(rocfft_execute(t.planP, &buf, nullptr, t.infoP));
-    }
-    auto give_back = [&](int rc) {               // not cached: give the table back
-        (void)hipFree(k.H);
-        e->cache_bytes -= bytes;
-        return rc;
-    };
+    double2 *const bufP = t.bufP.get(), *const bufM = t.bufM.get();
+    PSX_TIMED("k_kern_H", st, k_kern_H<<<(int)cdiv(P, 256), 256, 0, st>>>(bufP, P, a, du));
+    if (int rc = t.planP.execute(FftPlan::INV, bufP, st, "kern_ifft_P")) return rc;
     // taps -> the zero-padded sequences of the forward transform
     if (t.kind == Kind::P2X) {
-        if (int rc = p2::x_pad_taps(t.bufP, t.bufM, P, st)) return give_back(rc);
+        if (int rc = p2::x_pad_taps(bufP, bufM, P, st)) return rc;
     } else {
         const int mode = t.kind == Kind::DIF ? 2 : (t.kind == Kind::PAIR ? 1 : 0);     // k_kern_pad's `part`
-        PSX_TIMED("k_kern_pad", st, k_kern_pad<<<(int)cdiv((int64_t)t.Mconv * t.S, 256), 256, 0, st>>>(t.bufP, t.bufM, P, t.Mconv, t.Lh, t.S, mode));
+        PSX_TIMED("k_kern_pad", st, k_kern_pad<<<(int)cdiv((int64_t)t.Mconv * t.S, 256), 256, 0, st>>>(bufP, bufM, P, t.Mconv, t.Lh, t.S, mode));
     }
-    {
-        ProfScope ps("kern_fft_M", st);
-        void *buf = t.bufM;
-        PSX_ROCFFT(rocfft_execute(t.planM, &buf, nullptr, t.infoM));
-    }
+    if (int rc = t.planM.execute(FftPlan::FWD, bufM, st, "kern_fft_M")) return rc;
     // spectra -> the point order of the kind's LDS transform
     const int grid = (int)cdiv((int64_t)t.M * t.S, 256);
     int rc = 0;
     switch (t.kind) {
-        case Kind::P2X: rc = p2::x_perm_spectrum(t.bufM, t.bufP, k.H, P, st); break;
-        case Kind::P2: rc = p2::perm_spectrum(t.bufM, t.bufP, k.H, t.radix, P, st); break;
+        case Kind::P2X: rc = p2::x_perm_spectrum(bufM, bufP, H.get(), P, st); break;
+        case Kind::P2: rc = p2::perm_spectrum(bufM, bufP, H.get(), t.radix, P, st); break;
         case Kind::DIF:
         case Kind::PAIR:
-            PSX_TIMED("k_kern_perm", st, k_kern_perm_pair<<<grid, 256, 0, st>>>(t.bufM, reinterpret_cast<float4 *>(k.H), t.M, t.radix, t.S,
+            PSX_TIMED("k_kern_perm", st, k_kern_perm_pair<<<grid, 256, 0, st>>>(bufM, reinterpret_cast<float4 *>(H.get()), t.M, t.radix, t.S,
                                                                                t.kind == Kind::DIF ? 0.5 : 1.0));
             break;
-        case Kind::R3: PSX_TIMED("k_kern_perm", st, k_kern_perm<<<grid, 256, 0, st>>>(t.bufM, k.H, t.M, t.radix, t.S)); break;
+        case Kind::R3: PSX_TIMED("k_kern_perm", st, k_kern_perm<<<grid, 256, 0, st>>>(bufM, H.get(), t.M, t.radix, t.S)); break;
     }
     if (!rc) rc = launch_check("kernel spectrum");
-    if (rc) return give_back(rc);
-    e->cache.emplace(key, k);
-    *out = k.H;
+    if (rc) return rc;
+    *out = H.get();
+    e->cache.emplace(key, KernEntry{std::move(H), t.Mconv, t.S, ++e->clock});
+    e->cache_bytes += bytes;
+    p->bytes += bytes;
     return 0;
 }
 
@@ -1899,7 +1841,7 @@ static int line_groups(const AxisTables &t, int nlines, bool dual) {
 // transpose, into rows of the result) for n_dist distances; the caller sets the per-distance pointers, the work order and
 // the diagnostics.
 static LineArgs pass_args(const psx_fresnel_plan *p, int pass, int n_dist) {
-    const LdsEngine *e = p->lds;
+    const LdsEngine *e = p->lds.get();
     const AxisTables &t = e->ax[pass];
     LineArgs la;
     if (pass == 0) {
@@ -1910,18 +1852,18 @@ static LineArgs pass_args(const psx_fresnel_plan *p, int pass, int n_dist) {
         la.in_si = 0; la.in_sl = 0; la.in_blocked = 1; la.out_ld = p->Ny; la.out_blocked = 0;
     }
     la.margin = p->margin; la.L = la.N + la.P - 1;
-    la.twA = t.twA; la.twB = t.twB;
+    la.twA = t.twA.get(); la.twB = t.twB.get();
     la.B = t.B; la.Lh = t.Lh; la.S = t.S; la.NB = t.NB;
-    la.w2 = t.w2; la.w4 = t.w4; la.wgpart = e->wgpart; la.wg_groups = e->wgpart_groups;
+    la.w2 = t.w2.get(); la.w4 = t.w4.get(); la.wgpart = e->wgpart.get(); la.wg_groups = e->wgpart_groups;
     la.dsh = 2 * PART_M - la.P; la.thr = la.L - 2 * PART_M;
-    la.queue = e->use_queue ? e->queue + (size_t)pass * QUEUE_WORDS : nullptr;
+    la.queue = e->use_queue ? e->queue.get() + (size_t)pass * QUEUE_WORDS : nullptr;
     la.n_dist = n_dist; la.dist_inner = 0; la.accumulate = 0;
     la.stamps = nullptr; la.stamp_j = 1;
     return la;
 }
 
 int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
-    LdsEngine *e = p->lds;
+    LdsEngine *e = p->lds.get();
     hipStream_t st = a.stream;
     const int64_t npix = (int64_t)p->Nx * p->Ny;
     // z == 0 distances return the input field (EXP:233-234)
@@ -1945,7 +1887,7 @@ int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
         int vec_ok = p->Ny % 4 == 0 && (uintptr_t)a.wave_in % 16 == 0;
         for (int i = 0; i < a.m.n && i < PSX_MAX_MAT; ++i) vec_ok = vec_ok && ((uintptr_t)a.m.T[i] % 16 == 0);
         PSX_DISPATCH_NMAT(a.m.n, PSX_TIMED("k_source_transposed", st, k_source_transposed<NM><<<ntiles, 256, 0, st>>>(
-                                                                           a.wave_in, a.amp, a.m, e->pre, p->Nx, p->Ny, vec_ok)));
+                                                                           a.wave_in, a.amp, a.m, e->pre.get(), p->Nx, p->Ny, vec_ok)));
         if (int rc = launch_check("k_source_transposed")) return rc;
     }
 
@@ -1961,13 +1903,13 @@ int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
         la.stamps = stamp_pass1 ? g_stamps : nullptr; la.stamp_j = stamp_round;
         for (int i = 0; i < PSX_MAX_DIST; ++i) {
             const int k = i < nnz ? i : 0;
-            la.src[i] = e->pre;
+            la.src[i] = e->pre.get();
             if (i < nnz) {
                 if (int rc = kernel_spectrum(p, e->ax[0], a.a[nz[i]], a.du_x, st, &la.H[i])) return rc;
             } else {
                 la.H[i] = la.H[0];
             }
-            la.wave_out[i] = e->inter + (size_t)k * e->inter_elems;
+            la.wave_out[i] = e->inter.get() + (size_t)k * e->inter_elems;
             la.part[i] = la.wave_out[i];            // partial sums of a partitioned pass build up in the intermediate itself
             la.inten_out[i] = nullptr;
             la.scale[i] = 1.f;
@@ -1999,14 +1941,14 @@ int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
     lb.accumulate = a.accumulate; lb.stamps = stamp_pass1 ? nullptr : g_stamps; lb.stamp_j = stamp_round;
     for (int i = 0; i < PSX_MAX_DIST; ++i) {
         const int k = i < nnz ? i : 0, d = nz[k];
-        lb.src[i] = e->inter + (size_t)k * e->inter_elems;
+        lb.src[i] = e->inter.get() + (size_t)k * e->inter_elems;
         if (i < nnz) {
             if (int rc = kernel_spectrum(p, e->ax[1], a.a[d], a.du_y, st, &lb.H[i])) return rc;
         } else {
             lb.H[i] = lb.H[0];
         }
         lb.wave_out[i] = a.wave_out ? a.wave_out[d] : nullptr;
-        lb.part[i] = lb.wave_out[i] ? lb.wave_out[i] : (e->part ? e->part + (size_t)k * npix : nullptr);
+        lb.part[i] = lb.wave_out[i] ? lb.wave_out[i] : (e->part ? e->part.get() + (size_t)k * npix : nullptr);
         lb.inten_out[i] = a.inten_out ? a.inten_out[d] : nullptr;
         lb.scale[i] = a.inten_scale ? a.inten_scale[d] : 1.f;
         const double g = a.gphase ? a.gphase[d] : 0.0;
@@ -2024,7 +1966,7 @@ int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
 // as a grid axis: three launches for up to PSX_MAX_SRC sources.  Results are exactly those of one propagate call per source
 // (same kernels, same arithmetic); nothing is accumulated here -- every pair has its own output.
 int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
-    LdsEngine *e = p->lds;
+    LdsEngine *e = p->lds.get();
     hipStream_t st = a.stream;
     const int V = a.n_src * a.n_dist;
     const size_t npix = (size_t)p->Nx * p->Ny;
@@ -2036,23 +1978,8 @@ int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
     batched = batched && line_groups(e->ax[0], p->Ny, false) < current_cu_count();
     for (int v = 0; v < V && batched; ++v) batched = a.a[v] != 0.0;         // z == 0 pairs take the one-source path
     if (!batched) {
-        for (int s = 0; s < a.n_src; ++s) {
-            PropArgs pa;
-            pa.wave_in = a.wave_in ? a.wave_in[s] : nullptr;
-            pa.amp = a.amp[s];
-            pa.m = a.maps;
-            for (int i = 0; i < a.maps.n; ++i) {
-                pa.m.cphase[i] = a.cphase ? a.cphase[(size_t)s * a.maps.n + i] : 0.0;
-                pa.m.catt[i] = a.catt ? a.catt[(size_t)s * a.maps.n + i] : 0.0;
-            }
-            pa.n_dist = a.n_dist; pa.a = a.a + (size_t)s * a.n_dist; pa.gphase = a.gphase ? a.gphase + (size_t)s * a.n_dist : nullptr;
-            pa.du_x = a.du_x; pa.du_y = a.du_y;
-            pa.wave_out = a.wave_out ? a.wave_out + (size_t)s * a.n_dist : nullptr;
-            pa.inten_out = a.inten_out ? a.inten_out + (size_t)s * a.n_dist : nullptr;
-            pa.inten_scale = a.inten_scale ? a.inten_scale + (size_t)s * a.n_dist : nullptr;
-            pa.accumulate = 0; pa.stream = st;
-            if (int rc = lds_engine_propagate(p, pa)) return rc;
-        }
+        for (int s = 0; s < a.n_src; ++s)
+            if (int rc = lds_engine_propagate(p, slice_source(a, s))) return rc;
         return 0;
     }
     if (!e->pre_b) {
@@ -2060,9 +1987,12 @@ int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
         (void)hipStreamIsCapturing(st, &cs);
         if (cs != hipStreamCaptureStatusNone)
             return fail(PSX_E_STATE, "psx_fresnel_propagate_sources: the batch buffers are allocated by the first call; make it before capturing");
-        PSX_HIP(hipMalloc((void **)&e->pre_b, sizeof(float2) * npix * PSX_MAX_SRC));
-        PSX_HIP(hipMalloc((void **)&e->inter_b, sizeof(float2) * e->inter_elems * MAX_LINE));
-        p->bytes += sizeof(float2) * (npix * PSX_MAX_SRC + e->inter_elems * MAX_LINE);
+        DevBuf<float2> pre_b, inter_b;           // both or neither: a call that fails here leaves the engine as it was
+        if (int rc = pre_b.alloc(npix * PSX_MAX_SRC)) return rc;
+        if (int rc = inter_b.alloc(e->inter_elems * MAX_LINE)) return rc;
+        e->pre_b = std::move(pre_b);
+        e->inter_b = std::move(inter_b);
+        p->bytes += e->pre_b.bytes() + e->inter_b.bytes();
     }
     // ---- pass 0: the transmitted source wave of every source, transposed
     {
@@ -2084,15 +2014,15 @@ int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
         }
         const dim3 grid((unsigned)(cdiv(p->Nx, 64) * cdiv(p->Ny, 64)), (unsigned)a.n_src);
         PSX_DISPATCH_NMAT(a.maps.n, PSX_TIMED("k_source_transposed", st, k_source_transposed_batch<NM><<<grid, 256, 0, st>>>(
-                                                                              b, mp, e->pre_b, npix, p->Nx, p->Ny, vec_ok)));
+                                                                              b, mp, e->pre_b.get(), npix, p->Nx, p->Ny, vec_ok)));
         if (int rc = launch_check("k_source_transposed")) return rc;
     }
     // ---- pass 1 and pass 2: pair v = (source v / n_dist, distance v % n_dist) is "distance" v of the line kernels
     LineArgs la = pass_args(p, 0, V), lb = pass_args(p, 1, V);
     for (int i = 0; i < MAX_LINE; ++i) {
         const int v = i < V ? i : 0;
-        la.src[i] = e->pre_b + (size_t)(v / a.n_dist) * npix;
-        la.wave_out[i] = e->inter_b + (size_t)v * e->inter_elems;
+        la.src[i] = e->pre_b.get() + (size_t)(v / a.n_dist) * npix;
+        la.wave_out[i] = e->inter_b.get() + (size_t)v * e->inter_elems;
         la.part[i] = la.wave_out[i];
         la.inten_out[i] = nullptr;
         la.scale[i] = 1.f;

@@ -238,8 +238,8 @@ __global__ __launch_bounds__(MLT) void k_membrane_layers(const CellSphere *__res
 }  // namespace
 
 struct psx_membrane_plan {
-    CellSphere *spheres = nullptr;   // sorted by cell (row-major cells), list order inside a cell
-    int *cell_off = nullptr;         // [ncx*ncy + 1]
+    DevBuf<CellSphere> spheres;      // sorted by cell (row-major cells), list order inside a cell
+    DevBuf<int> cell_off;            // [ncx*ncy + 1]
     int ncx = 0, ncy = 0, rmax_int = 1;
     double x0 = 0.0, y0 = 0.0;
     int64_t n = 0;
@@ -251,7 +251,7 @@ int psx_membrane_plan_create(const double *x, const double *y, const double *r, 
     PSX_REQUIRE(plan != nullptr, "psx_membrane_plan_create: null plan pointer");
     *plan = nullptr;
     PSX_REQUIRE(n >= 0 && (n == 0 || (x && y && r)), "psx_membrane_plan_create: null sphere arrays");
-    psx_membrane_plan *p = new psx_membrane_plan();
+    std::unique_ptr<psx_membrane_plan> p(new psx_membrane_plan());
     double xmin = 0, xmax = 0, ymin = 0, ymax = 0, rmax = 0;
     bool any = false;
     for (int64_t s = 0; s < n; ++s) {
@@ -263,10 +263,8 @@ int psx_membrane_plan_create(const double *x, const double *y, const double *r, 
     }
     p->x0 = std::floor(xmin); p->y0 = std::floor(ymin);
     const double ex = xmax - p->x0, ey = ymax - p->y0;
-    if (!(ex / MC < 60000.0 && ey / MC < 60000.0 && (ex / MC + 1) * (ey / MC + 1) < 4.0e8 && rmax < 1.0e6)) {
-        delete p;
+    if (!(ex / MC < 60000.0 && ey / MC < 60000.0 && (ex / MC + 1) * (ey / MC + 1) < 4.0e8 && rmax < 1.0e6))
         return fail(PSX_E_ARG, "psx_membrane_plan_create: sphere list spans %.3g x %.3g pixels (radius up to %.3g)", ex, ey, rmax);
-    }
     p->ncx = (int)(ex / MC) + 1; p->ncy = (int)(ey / MC) + 1;
     p->rmax_int = (int)std::floor(rmax) + 1;
     const size_t nc = (size_t)p->ncx * p->ncy;
@@ -284,22 +282,13 @@ int psx_membrane_plan_create(const double *x, const double *y, const double *r, 
     for (int64_t s = 0; s < n; ++s)
         if (cell[s] >= 0) sorted[cursor[cell[s]]++] = CellSphere{x[s], y[s], r[s]};
     p->n = off[nc];
-    hipError_t e = hipMalloc((void **)&p->spheres, sizeof(CellSphere) * sorted.size());
-    if (e == hipSuccess) e = hipMalloc((void **)&p->cell_off, sizeof(int) * off.size());
-    if (e == hipSuccess) e = hipMemcpy(p->spheres, sorted.data(), sizeof(CellSphere) * sorted.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->cell_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        psx_membrane_plan_destroy(p);
-        return fail((int)e, "psx_membrane_plan_create: %s", hipGetErrorString(e));
-    }
-    *plan = p;
+    if (int rc = p->spheres.upload(sorted.data(), sorted.size())) return rc;
+    if (int rc = p->cell_off.upload(off.data(), off.size())) return rc;
+    *plan = p.release();
     return 0;
 }
 
 int psx_membrane_plan_destroy(psx_membrane_plan *p) {
-    if (!p) return 0;
-    (void)hipFree(p->spheres);
-    (void)hipFree(p->cell_off);
     delete p;
     return 0;
 }
@@ -321,7 +310,7 @@ int psx_membrane_layers_f32(psx_membrane_plan *p, int nlayers, const int *offx, 
             la.offy[l] = offy[l0 + l];
         }
         PSX_TIMED("k_membrane", st, k_membrane_layers<<<tiles_x * tiles_y, MLT, 0, st>>>(
-                      p->spheres, p->cell_off, p->ncx, p->ncy, p->x0, p->y0, p->rmax_int, la, out, l0 == 0 ? support : nullptr,
+                      p->spheres.get(), p->cell_off.get(), p->ncx, p->ncy, p->x0, p->y0, p->rmax_int, la, out, l0 == 0 ? support : nullptr,
                       support_value, dimX, dimY, margin, margin2, tiles_y, scale, (accumulate || l0 > 0) ? 1 : 0));
         if (int rc = launch_check("k_membrane")) return rc;
     }
@@ -364,21 +353,17 @@ int psx_membrane_f32(const double *xf, const double *yf, const double *rad, int6
     std::vector<int> ids(pairs.size() ? pairs.size() : 1), cursor(counts.begin(), counts.end() - 1);
     for (auto &pr : pairs) ids[cursor[pr.first]++] = pr.second;      // sphere order inside a tile = list order
     if (sph.empty()) sph.push_back(Sphere{0, 0, 0, 0, 0, 0, 0});
-    Sphere *d_sph = nullptr;
-    int *d_off = nullptr, *d_ids = nullptr;
-    PSX_HIP(hipMallocAsync((void **)&d_sph, sizeof(Sphere) * sph.size(), st));
-    PSX_HIP(hipMallocAsync((void **)&d_off, sizeof(int) * counts.size(), st));
-    PSX_HIP(hipMallocAsync((void **)&d_ids, sizeof(int) * ids.size(), st));
-    PSX_HIP(hipMemcpyAsync(d_sph, sph.data(), sizeof(Sphere) * sph.size(), hipMemcpyHostToDevice, st));
-    PSX_HIP(hipMemcpyAsync(d_off, counts.data(), sizeof(int) * counts.size(), hipMemcpyHostToDevice, st));
-    PSX_HIP(hipMemcpyAsync(d_ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, st));
-    PSX_TIMED("k_membrane", st, k_membrane<<<nt, 256, 0, st>>>(d_sph, d_off, d_ids, out, dimX, dimY, margin, tiles_y,
+    // stream-ordered temporaries, declared after the host vectors they are filled from: on every way out they wait for the
+    // stream and go back to its pool before those vectors do
+    DevBuf<Sphere> d_sph;
+    DevBuf<int> d_off, d_ids;
+    if (int rc = d_sph.upload_async(sph.data(), sph.size(), st)) return rc;
+    if (int rc = d_off.upload_async(counts.data(), counts.size(), st)) return rc;
+    if (int rc = d_ids.upload_async(ids.data(), ids.size(), st)) return rc;
+    PSX_TIMED("k_membrane", st, k_membrane<<<nt, 256, 0, st>>>(d_sph.get(), d_off.get(), d_ids.get(), out, dimX, dimY, margin, tiles_y,
                                                                 scale, accumulate));
     const int rc = launch_check("k_membrane");
-    PSX_HIP(hipStreamSynchronize(st));       // the host staging vectors go out of scope below
-    (void)hipFreeAsync(d_sph, st);
-    (void)hipFreeAsync(d_off, st);
-    (void)hipFreeAsync(d_ids, st);
+    PSX_HIP(hipStreamSynchronize(st));       // its error is the call's; the temporaries are freed either way
     return rc;
 }
 

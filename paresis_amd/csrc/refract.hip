@@ -913,21 +913,17 @@ static unsigned det_scale_bits() {         // the scale with 2^6 of room for sha
 }
 
 // scratch of psx_fastloop_f32's deterministic mode (that entry point has no workspace argument): accumulators + the max
-// word, owned for the duration of one call -- a plain hipMalloc / synchronise / hipFree per call, a debugging aid.  The
+// word, owned for the duration of one call -- a plain allocation / synchronise / free per call, a debugging aid.  The
 // refraction entry points take theirs from the caller's workspace and allocate nothing (refract_far_body).
 struct DetScratch {
+    DevBuf<long long> buf;         // [npix] accumulators + 16 bytes for the max word; freed when the call returns, whichever way
     long long *acc = nullptr;
     unsigned *mx = nullptr;
     int alloc(size_t npix, hipStream_t st) {
-        PSX_HIP(hipMalloc((void **)&acc, sizeof(long long) * npix + 16));
+        if (int rc = buf.alloc(npix + 2)) return rc;
+        acc = buf.get();
         mx = reinterpret_cast<unsigned *>(acc + npix);
-        PSX_HIP(hipMemsetAsync(acc, 0, sizeof(long long) * npix + 16, st));
-        return 0;
-    }
-    int release(hipStream_t st) {
-        PSX_HIP(hipStreamSynchronize(st));
-        PSX_HIP(hipFree(acc));
-        acc = nullptr;
+        PSX_HIP(hipMemsetAsync(acc, 0, buf.bytes(), st));
         return 0;
     }
 };
@@ -1168,8 +1164,8 @@ int psx_fastloop_f32(const float *I, const float *Dx, const float *Dy, float *I2
         PSX_TIMED("k_fastloop", st, k_fastloop<true><<<ew_grid(n, 256), 256, 0, st>>>(I, Dx, Dy, I2, Nx, Ny, DetAcc{ds.acc, ds.mx}));
         PSX_TIMED("k_det_apply", st, k_det_apply<<<ew_grid(n, 256), 256, 0, st>>>(I2, ds.acc, ds.mx, n));
         const int rc_det = launch_check("k_fastloop (deterministic)");
-        const int rc_rel = ds.release(st);
-        return rc_det ? rc_det : rc_rel;
+        PSX_HIP(hipStreamSynchronize(st));   // the scratch goes with ds
+        return rc_det;
     }
     PSX_TIMED("k_fastloop", st, k_fastloop<false><<<ew_grid(n, 256), 256, 0, st>>>(I, Dx, Dy, I2, Nx, Ny, DetAcc{nullptr, nullptr}));
     return launch_check("k_fastloop");

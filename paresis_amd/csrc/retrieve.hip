@@ -227,44 +227,33 @@ __global__ __launch_bounds__(256) void k_integ_crop(const float2 *__restrict__ Z
 }  // namespace
 
 struct psx_integrate_plan {
-    int n, m;
-    size_t bytes;
-    rocfft_plan fwd, inv;
-    rocfft_execution_info info;
-    void *work;
-    float2 *Z;   // [2n][2m]
+    int n = 0, m = 0;
+    size_t bytes = 0;
+    FftPlan fft;         // forward + inverse, [2n][2m]
+    DevBuf<float2> Z;    // [2n][2m]
 };
 
 namespace {
 
-void integrate_plan_free(psx_integrate_plan *p) {
-    if (p->fwd) rocfft_plan_destroy(p->fwd);
-    if (p->inv) rocfft_plan_destroy(p->inv);
-    if (p->info) rocfft_execution_info_destroy(p->info);
-    (void)hipFree(p->work);
-    (void)hipFree(p->Z);
-    delete p;
-}
-
-int integrate_plan_init(psx_integrate_plan *p) {
-    if (int rc = rocfft_ensure_setup()) return rc;
-    const size_t lengths[2] = {2 * (size_t)p->m, 2 * (size_t)p->n};   // fastest first
-    PSX_ROCFFT(rocfft_plan_create(&p->fwd, rocfft_placement_inplace, rocfft_transform_type_complex_forward,
-                                  rocfft_precision_single, 2, lengths, 1, nullptr));
-    PSX_ROCFFT(rocfft_plan_create(&p->inv, rocfft_placement_inplace, rocfft_transform_type_complex_inverse,
-                                  rocfft_precision_single, 2, lengths, 1, nullptr));
-    size_t wf = 0, wi = 0;
-    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(p->fwd, &wf));
-    PSX_ROCFFT(rocfft_plan_get_work_buffer_size(p->inv, &wi));
-    const size_t work = wf > wi ? wf : wi;
-    PSX_ROCFFT(rocfft_execution_info_create(&p->info));
-    if (work) {
-        PSX_HIP(hipMalloc(&p->work, work));
-        PSX_ROCFFT(rocfft_execution_info_set_work_buffer(p->info, p->work, work));
+// The argument checks, pointer packing and grid shared by psx_lcs_f32 and psx_lcs_df_f32.  fn: the entry point's name in the
+// error texts; Kmin: its smallest K; outputs_ok: all its output maps are there.
+int lcs_prepare(const char *fn, int Kmin, const float *const *S, const float *const *R, int K, int n, int m, float max_shift,
+                bool outputs_ok, LcsPtrs &p, dim3 &grid) {
+    PSX_REQUIRE(K >= Kmin && K <= PSX_MAX_LCS, "%s: K=%d positions outside [%d,%d]", fn, K, Kmin, PSX_MAX_LCS);
+    PSX_REQUIRE(n >= 3 && m >= 3, "%s: images %dx%d smaller than 3x3", fn, n, m);
+    PSX_REQUIRE(S != nullptr && R != nullptr, "%s: null pointer array", fn);
+    PSX_REQUIRE(outputs_ok, "%s: null output map", fn);
+    PSX_REQUIRE(max_shift >= 0.0f, "%s: max_shift=%g < 0", fn, (double)max_shift);
+    for (int k = 0; k < PSX_MAX_LCS; ++k) {
+        p.S[k] = nullptr;
+        p.R[k] = nullptr;
     }
-    const size_t img = sizeof(float2) * 4 * (size_t)p->n * (size_t)p->m;
-    PSX_HIP(hipMalloc((void **)&p->Z, img));
-    p->bytes = img + work;
+    for (int k = 0; k < K; ++k) {
+        PSX_REQUIRE(S[k] != nullptr && R[k] != nullptr, "%s: position %d has a null image", fn, k);
+        p.S[k] = S[k];
+        p.R[k] = R[k];
+    }
+    grid = dim3((unsigned)cdiv(m, LCS_BX), (unsigned)cdiv(n, LCS_BY));
     return 0;
 }
 
@@ -274,47 +263,21 @@ extern "C" {
 
 int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
                 float *dx, float *dy, void *stream) {
-    PSX_REQUIRE(K >= 3 && K <= PSX_MAX_LCS, "psx_lcs_f32: K=%d positions outside [3,%d]", K, PSX_MAX_LCS);
-    PSX_REQUIRE(n >= 3 && m >= 3, "psx_lcs_f32: images %dx%d smaller than 3x3", n, m);
-    PSX_REQUIRE(S != nullptr && R != nullptr, "psx_lcs_f32: null pointer array");
-    PSX_REQUIRE(transmission && dx && dy, "psx_lcs_f32: null output map");
-    PSX_REQUIRE(max_shift >= 0.0f, "psx_lcs_f32: max_shift=%g < 0", (double)max_shift);
     LcsPtrs p;
-    for (int k = 0; k < PSX_MAX_LCS; ++k) {
-        p.S[k] = nullptr;
-        p.R[k] = nullptr;
-    }
-    for (int k = 0; k < K; ++k) {
-        PSX_REQUIRE(S[k] != nullptr && R[k] != nullptr, "psx_lcs_f32: position %d has a null image", k);
-        p.S[k] = S[k];
-        p.R[k] = R[k];
-    }
+    dim3 grid;
+    if (int rc = lcs_prepare("psx_lcs_f32", 3, S, R, K, n, m, max_shift, transmission && dx && dy, p, grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)cdiv(m, LCS_BX), (unsigned)cdiv(n, LCS_BY)), block(LCS_BX, LCS_BY);
-    PSX_TIMED("k_lcs", st, k_lcs<<<grid, block, 0, st>>>(p, K, n, m, max_shift, transmission, dx, dy));
+    PSX_TIMED("k_lcs", st, k_lcs<<<grid, dim3(LCS_BX, LCS_BY), 0, st>>>(p, K, n, m, max_shift, transmission, dx, dy));
     return launch_check("k_lcs");
 }
 
 int psx_lcs_df_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
                    float *dx, float *dy, float *df, void *stream) {
-    PSX_REQUIRE(K >= 4 && K <= PSX_MAX_LCS, "psx_lcs_df_f32: K=%d positions outside [4,%d]", K, PSX_MAX_LCS);
-    PSX_REQUIRE(n >= 3 && m >= 3, "psx_lcs_df_f32: images %dx%d smaller than 3x3", n, m);
-    PSX_REQUIRE(S != nullptr && R != nullptr, "psx_lcs_df_f32: null pointer array");
-    PSX_REQUIRE(transmission && dx && dy && df, "psx_lcs_df_f32: null output map");
-    PSX_REQUIRE(max_shift >= 0.0f, "psx_lcs_df_f32: max_shift=%g < 0", (double)max_shift);
     LcsPtrs p;
-    for (int k = 0; k < PSX_MAX_LCS; ++k) {
-        p.S[k] = nullptr;
-        p.R[k] = nullptr;
-    }
-    for (int k = 0; k < K; ++k) {
-        PSX_REQUIRE(S[k] != nullptr && R[k] != nullptr, "psx_lcs_df_f32: position %d has a null image", k);
-        p.S[k] = S[k];
-        p.R[k] = R[k];
-    }
+    dim3 grid;
+    if (int rc = lcs_prepare("psx_lcs_df_f32", 4, S, R, K, n, m, max_shift, transmission && dx && dy && df, p, grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)cdiv(m, LCS_BX), (unsigned)cdiv(n, LCS_BY)), block(LCS_BX, LCS_BY);
-    PSX_TIMED("k_lcs_df", st, k_lcs_df<<<grid, block, 0, st>>>(p, K, n, m, max_shift, transmission, dx, dy, df));
+    PSX_TIMED("k_lcs_df", st, k_lcs_df<<<grid, dim3(LCS_BX, LCS_BY), 0, st>>>(p, K, n, m, max_shift, transmission, dx, dy, df));
     return launch_check("k_lcs_df");
 }
 
@@ -323,18 +286,18 @@ int psx_integrate_plan_create(int n, int m, psx_integrate_plan **plan) {
     *plan = nullptr;
     PSX_REQUIRE(n >= 2 && m >= 2, "psx_integrate_plan_create: grid %dx%d too small", n, m);
     PSX_REQUIRE((int64_t)n * m <= (int64_t)1 << 28, "psx_integrate_plan_create: grid %dx%d too large", n, m);
-    psx_integrate_plan *p = new psx_integrate_plan();
-    p->n = n; p->m = m; p->bytes = 0; p->fwd = nullptr; p->inv = nullptr; p->info = nullptr; p->work = nullptr; p->Z = nullptr;
-    if (int rc = integrate_plan_init(p)) {
-        integrate_plan_free(p);
-        return rc;
-    }
-    *plan = p;
+    std::unique_ptr<psx_integrate_plan> p(new psx_integrate_plan());
+    p->n = n; p->m = m;
+    const size_t lengths[2] = {2 * (size_t)m, 2 * (size_t)n};   // fastest first
+    if (int rc = p->fft.create(FftPlan::BOTH, rocfft_precision_single, 2, lengths)) return rc;
+    if (int rc = p->Z.alloc(4 * (size_t)n * (size_t)m)) return rc;
+    p->bytes = p->Z.bytes() + p->fft.work_bytes();
+    *plan = p.release();
     return 0;
 }
 
 int psx_integrate_plan_destroy(psx_integrate_plan *plan) {
-    if (plan) integrate_plan_free(plan);
+    delete plan;
     return 0;
 }
 
@@ -346,22 +309,15 @@ int psx_integrate_f32(psx_integrate_plan *plan, const float *gx, const float *gy
     hipStream_t st = (hipStream_t)stream;
     const int n = plan->n, m = plan->m;
     const int64_t N = 4 * (int64_t)n * m;
-    PSX_TIMED("k_integ_pack", st, k_integ_pack<<<ew_grid(N, 256), 256, 0, st>>>(gx, gy, scale, plan->Z, n, m));
+    float2 *const Z = plan->Z.get();
+    PSX_TIMED("k_integ_pack", st, k_integ_pack<<<ew_grid(N, 256), 256, 0, st>>>(gx, gy, scale, Z, n, m));
     if (int rc = launch_check("k_integ_pack")) return rc;
-    PSX_ROCFFT(rocfft_execution_info_set_stream(plan->info, st));
-    void *buf[1] = {plan->Z};
-    {
-        ProfScope ps("rocfft_integrate_forward", st);
-        PSX_ROCFFT(rocfft_execute(plan->fwd, buf, nullptr, plan->info));
-    }
-    PSX_TIMED("k_integ_filter", st, k_integ_filter<<<ew_grid(N, 256), 256, 0, st>>>(plan->Z, n, m));
+    if (int rc = plan->fft.execute(FftPlan::FWD, Z, st, "rocfft_integrate_forward")) return rc;
+    PSX_TIMED("k_integ_filter", st, k_integ_filter<<<ew_grid(N, 256), 256, 0, st>>>(Z, n, m));
     if (int rc = launch_check("k_integ_filter")) return rc;
-    {
-        ProfScope ps("rocfft_integrate_inverse", st);
-        PSX_ROCFFT(rocfft_execute(plan->inv, buf, nullptr, plan->info));
-    }
+    if (int rc = plan->fft.execute(FftPlan::INV, Z, st, "rocfft_integrate_inverse")) return rc;
     const float norm = (float)(1.0 / (double)N);
-    PSX_TIMED("k_integ_crop", st, k_integ_crop<<<ew_grid((int64_t)n * m, 256), 256, 0, st>>>(plan->Z, phi, n, m, norm));
+    PSX_TIMED("k_integ_crop", st, k_integ_crop<<<ew_grid((int64_t)n * m, 256), 256, 0, st>>>(Z, phi, n, m, norm));
     return launch_check("k_integ_crop");
 }
 

@@ -704,9 +704,28 @@ def fastloop(I, Dx, Dy, I2):
     return I2
 
 
+# ---------------------------------------------------------------------------------------------- plan handles
+class _Plan:
+    """A plan of the library: the handle `_h` (set by the subclass's __init__) and `_destroy`, the name of the symbol that
+    frees it.  close() may be called any number of times; a plan that is dropped closes itself."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # -------------------------------------------------------------------------------------------------- Fresnel
-class FresnelPlan:
+class FresnelPlan(_Plan):
     """psx_fresnel_plan for one study grid (Experiment.wavePropagation, Experiment.py:219-252)."""
+    _destroy = "psx_fresnel_plan_destroy"
 
     def __init__(self, Nx, Ny, margin=MARGIN_FRESNEL, max_dist=4, engine=_lib.ENGINE_AUTO, device=None):
         self.Nx, self.Ny, self.margin, self.max_dist = int(Nx), int(Ny), int(margin), int(max_dist)
@@ -722,17 +741,6 @@ class FresnelPlan:
         """Line groups through a queue instead of static shares (psx_fresnel_plan_work_queue): for runs whose transfers or
         other streams share the GPU with the propagations."""
         check(lib().psx_fresnel_plan_work_queue(self._h, 1 if on else 0), "psx_fresnel_plan_work_queue")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().psx_fresnel_plan_destroy(self._h)
-            self._h = c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def propagate(self, a, gphase, du, wave_in=None, amp=1.0, mats=None, want_wave=None, inten_out=None,
                   inten_scale=None, add=False):
@@ -803,8 +811,9 @@ class FresnelPlan:
 
 
 # ------------------------------------------------------------------------------------------------- detector
-class DetectorPlan:
+class DetectorPlan(_Plan):
     """psx_detector_plan: the composed blur/bin/PSF operator of Detector.detection (Detector.py:79-119)."""
+    _destroy = "psx_detector_plan_destroy"
 
     def __init__(self, Nx, Ny, ov, nx, ny, sigma_src, sigma_psf, margin=MARGIN_DETECTOR, device=None):
         self.Nx, self.Ny, self.nx, self.ny = int(Nx), int(Ny), int(nx), int(ny)
@@ -814,17 +823,6 @@ class DetectorPlan:
             check(lib().psx_detector_plan_create(self.Nx, self.Ny, int(ov), self.nx, self.ny, int(margin),
                                                  c_double(sigma_src), c_double(sigma_psf), ctypes.byref(self._h)),
                   "psx_detector_plan_create")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().psx_detector_plan_destroy(self._h)
-            self._h = c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def detect(self, img, out=None):
         _need(img, torch.float32, "img", (self.Nx, self.Ny))
@@ -1034,9 +1032,10 @@ def lcs_df(sample, reference, max_shift=None, out=None):
     return out
 
 
-class IntegratePlan:
+class IntegratePlan(_Plan):
     """psx_integrate_plan for one n x m grid: Frankot-Chellappa integration of a gradient field with mirror extension
     (rocFFT on the 2n x 2m complex64 grid the plan owns; `bytes` reports it with rocFFT's work buffer)."""
+    _destroy = "psx_integrate_plan_destroy"
 
     def __init__(self, n, m, device=None):
         self.n, self.m = int(n), int(m)
@@ -1045,17 +1044,6 @@ class IntegratePlan:
         with torch.cuda.device(self.device):
             check(lib().psx_integrate_plan_create(self.n, self.m, ctypes.byref(self._h)), "psx_integrate_plan_create")
         self.bytes = lib().psx_integrate_plan_bytes(self._h)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().psx_integrate_plan_destroy(self._h)
-            self._h = c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def integrate(self, gx, gy, scale=1.0, out=None):
         """phi (n x m float32, radians, zero mean over the extension) whose gradient is scale*(gx, gy), in radians per pixel

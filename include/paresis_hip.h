@@ -261,7 +261,13 @@ int psx_detector_operator_host(int N, int ov, int n, int margin, double sigma_sr
 /* out[x][y] = sum of the s x s block of img, s = Nx/sx (Detector.resize, Detector.py:185-198) */
 int psx_resize_f32(const float *img, int Nx, int Ny, float *out, int sx, int sy, void *stream);
 /* out[p] = Poisson(lam[p]) drawn from a counter-based generator keyed by (seed, p)  (Detector.py:113-115;
- * the reference seeds from the wall clock, so only the distribution is reproducible) */
+ * the reference seeds from the wall clock, so only the distribution is reproducible).
+ * Supported means: 0 <= lam <= 2^23, so that every count the sampler can reach stays below 2^24 and is an exact float32
+ * integer (tests/test_gpu_poisson.py holds the distribution to the exact one from 1e-6 to 1e6).  lam <= 0 (-0.0 and -inf
+ * included) and NaN give 0; a denormal lam gives 0 (its exp(-lam) is 1.0f).  Beyond the range nothing is reported -- no error,
+ * no status bit -- and the value is not a Poisson draw: for a finite lam > 2^24 a float32 near lam + sqrt(lam) N(0,1), rounded
+ * to the float32 grid there (spacing >= 2); for +inf a non-finite float32 (inf - inf in the candidate).  Both paths of the
+ * kernel (16-byte and scalar) give the same bits there too. */
 int psx_poisson_f32(const float *lam, float *out, int64_t n, uint64_t seed, void *stream);
 /* The same IN PLACE on nimg <= PSX_MAX_POISSON images of n pixels in ONE launch, image i under key seeds[i] (imgs, seeds:
  * host arrays) -- the three or four detector images of an energy bin (Experiment.py:388-394).  Image i comes out exactly as

@@ -686,7 +686,11 @@ struct Philox {
             k[0] += 0x9E3779B9u;
             k[1] += 0xBB67AE85u;
         }
-        for (int i = 0; i < 4; ++i) u[i] = ((float)(c[i] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0,1)
+        // (0, 1]: never 0, but from c >> 8 = 2^23 on the + 0.5f is rounded away (ties to even) and c >> 8 = 2^24 - 1 gives 1.0
+        // exactly.  As a PTRS U that is +0.5: us = 0, rcp(0) = inf, the candidate fails the squeeze and is skipped by the
+        // us < 0.013 && V > us test before any logarithm; as V, or in the product of uniforms, 1.0 is an ordinary value
+        // (test_unit_uniform_first_candidate runs both)
+        for (int i = 0; i < 4; ++i) u[i] = ((float)(c[i] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     }
 };
 

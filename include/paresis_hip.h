@@ -382,6 +382,29 @@ int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int 
  * K in [4, PSX_MAX_LCS], n, m >= 3; argument errors as psx_lcs_f32.  Reads the same bytes as psx_lcs_f32, writes four maps. */
 int psx_lcs_df_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
                    float *dx, float *dy, float *df, void *stream);
+/* UMPA ("Unified Modulated Pattern Analysis", Zdora et al., PRL 118, 203903, 2017; separable form: De Marco et al., Opt.
+ * Express 31, 635, 2023): windowed speckle tracking for displacements beyond the one pixel LCS is valid for, from K >= 1
+ * positions.  Model S_k(q) ~ T*R_k(q - u), LCS's sign: dx along axis 0, dy along axis 1, as the chain's Dxreal / Dyreal.
+ *   window = w in [1, PSX_MAX_UMPA_WINDOW]: a UNIFORM (2w+1)^2 window (no Hamming taper, unlike the UMPA package: the window
+ *   sums are then box filters); search = s in [1, PSX_MAX_UMPA_SEARCH]: integer candidates u = (a, b), |a|, |b| <= s;
+ *   K in [1, PSX_MAX_LCS]; n, m >= 2(w+s)+1.
+ *   Border band: a pixel closer than w+s to any border gets exactly transmission = 1, dx = dy = 0, residual = 0; no index is
+ *   ever clamped or mirrored.
+ *   Interior pixel r, sums over k and over q in the window around r, all in float64 (any order):
+ *     E = sum S_k(q)^2,  B(u) = sum S_k(q) R_k(q-u),  C(u) = sum R_k(q-u)^2;  a candidate with C(u) == 0 is skipped;
+ *     L(u) = E - B*B/C,  T(u) = B/C;  u* = (a*, b*) = the first strict minimum of L, a outer, b inner, both ascending;
+ *     per axis: if |a*| < s and both L(a*-1, b*) = Lm and L(a*+1, b*) = Lp exist (not skipped), den = Lm - 2 L(u*) + Lp and,
+ *     if den > 0, da = clip(0.5 (Lm - Lp)/den, -0.5, 0.5); otherwise da = 0 (a minimum on the search boundary gives
+ *     exactly +-s); db likewise;
+ *     dx = a* + da, dy = b* + db, transmission = T(u*), residual = max(L(u*), 0)/E, as float32;
+ *     (1, 0, 0, residual 0) exactly when every candidate is skipped or T(u*) <= 0.
+ *   Where two candidates' costs agree to rounding the choice between them is unspecified.
+ * S, R: HOST arrays of K device pointers to n x m float32 images, n*m <= 2^30.  One launch, no scratch memory: the images
+ * are read (2s+1)*ceil((2s+1)/7) times from L2 at most.  Argument errors as psx_lcs_f32. */
+#define PSX_MAX_UMPA_WINDOW 8
+#define PSX_MAX_UMPA_SEARCH 8
+int psx_umpa_f32(const float *const *S, const float *const *R, int K, int n, int m, int window, int search,
+                 float *transmission, float *dx, float *dy, float *residual, void *stream);
 /* Frankot-Chellappa integration (IEEE PAMI 10, 1988) of the gradient field scale*(gx, gy) (rad per pixel along axis 0 / 1)
  * with mirror extension: on the 2n x 2m grid gx is odd in axis 0 and even in axis 1, gy even in axis 0 and odd in axis 1;
  * P = (-i kx Gx^ - i ky Gy^)/(kx^2 + ky^2), P(0) = 0, kx = 2 pi fftfreq(2n), ky = 2 pi fftfreq(2m); phi = Re ifft2(P) on

@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(_HERE, "libparesis_hip.so")
 PSX_MAX_MAT = 8
 PSX_MAX_FOLD = 64
 PSX_MAX_LCS = 64
+PSX_MAX_UMPA_WINDOW = 8
+PSX_MAX_UMPA_SEARCH = 8
 PSX_PHANTOM_TUBES = 12
 PSX_MAX_DIST = 8
 PSX_MAX_POISSON = 8
@@ -21,7 +23,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class PsxError(RuntimeError):
@@ -99,6 +101,7 @@ PROTOTYPES = {
     "psx_contrast_phantom_slices_u8": (c_int, [_vp, _vp, _vp]),
     "psx_lcs_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp]),
     "psx_lcs_df_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp, _vp]),
+    "psx_umpa_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, _vp]),
     "psx_integrate_plan_create": (c_int, [c_int, c_int, _vpp]),
     "psx_integrate_plan_destroy": (c_int, [_vp]),
     "psx_integrate_plan_bytes": (c_size_t, [_vp]),

@@ -3,13 +3,15 @@
 
     python -m paresis_amd.main [--experiment NAME] [--type RayT|Fresnel] [--oversampling N] [--points N]
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
-                               [--retrieve [--max-shift S] [--dark-field]]
+                               [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa --window W --search M]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
 has its own seed.  --retrieve (needs 3 positions or more) runs the speckle-tracking phase retrieval of each bin on rank 0
 after the gather (paresis_amd/retrieval.py) and writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under the bin's
 directory.  --dark-field (needs 4 positions or more) retrieves with LCS-DF and adds df_ and scattering_<expID><fmt>.
+--method umpa (1 position or more) retrieves with UMPA, for displacements of up to --search pixels, and adds
+residual_<expID><fmt>; it takes neither --dark-field nor --max-shift.
 """
 import argparse
 import datetime
@@ -19,14 +21,19 @@ import time
 import numpy as np
 
 
-def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False):
+def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
+        method='lcs', window=2, search=3):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
     (retrieval.retrieve with the experiment's parameters, max_shift its clamp); with save, the maps go to
     <bin dir>/retrieval/.  exp_dict['retrievalParams'] then holds the parameters it used.  dark_field (with retrieve, 4
-    positions or more): LCS-DF, the maps gain df and scattering (retrieval.retrieve(..., dark_field=True))."""
-    if retrieve and int(exp_dict['nbExpPoints']) < 3:
+    positions or more): LCS-DF, the maps gain df and scattering (retrieval.retrieve(..., dark_field=True)).  method='umpa'
+    (with retrieve, 1 position or more; window, search as retrieval.umpa): UMPA instead of LCS, the maps gain residual."""
+    if retrieve and method != "lcs":
+        from .retrieval import check_method
+        check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
+    elif retrieve and int(exp_dict['nbExpPoints']) < 3:
         raise ValueError("--retrieve needs at least 3 membrane positions, got %d" % int(exp_dict['nbExpPoints']))
     if dark_field and not retrieve:
         raise ValueError("dark_field is an option of retrieve")
@@ -142,7 +149,8 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     if rank == 0 and retrieve:
         from . import retrieval
         params = retrieval.params_from_experiment(experiment)
-        retrieved = retrieval.retrieve(gathered, params, max_shift=max_shift, dark_field=dark_field)
+        retrieved = retrieval.retrieve(gathered, params, max_shift=max_shift, dark_field=dark_field, method=method,
+                                       window=window, search=search)
         exp_dict['retrievalParams'] = params
         if save:
             for ibin in sorted(retrieved):
@@ -176,6 +184,11 @@ def main(argv=None):
     ap.add_argument("--max-shift", type=float, default=None, help="--retrieve: clamp of the displacements, in pixels")
     ap.add_argument("--dark-field", action="store_true",
                     help="--retrieve with LCS-DF (4 positions or more): also retrieval/{df,scattering}_<expID><fmt>")
+    ap.add_argument("--method", default="lcs", choices=["lcs", "umpa"],
+                    help="--retrieve with LCS (3 positions or more, |D| < 1 px) or UMPA (1 position or more, |D| up to --search "
+                         "px; also retrieval/residual_<expID><fmt>)")
+    ap.add_argument("--window", type=int, default=2, help="--method umpa: half-width w of the (2w+1)^2 window, 1..8")
+    ap.add_argument("--search", type=int, default=3, help="--method umpa: largest integer shift searched, 1..8")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -183,14 +196,21 @@ def main(argv=None):
     if a.xml:
         exp_dict['xmlDir'] = a.xml
     os.makedirs(exp_dict['filepath'], exist_ok=True)
-    if a.retrieve and a.points < 3:
+    if a.method == "umpa":
+        if not a.retrieve:
+            ap.error("--method is an option of --retrieve")
+        if a.dark_field or a.max_shift is not None:
+            ap.error("--dark-field and --max-shift are options of --method lcs")
+        if not 1 <= a.window <= 8 or not 1 <= a.search <= 8:
+            ap.error("--window and --search must be in 1..8")
+    if a.retrieve and a.method == "lcs" and a.points < 3:
         ap.error("--retrieve needs --points 3 or more")
     if a.dark_field and not a.retrieve:
         ap.error("--dark-field is an option of --retrieve")
     if a.dark_field and a.points < 4:
         ap.error("--dark-field needs --points 4 or more")
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
-        dark_field=a.dark_field)
+        dark_field=a.dark_field, method=a.method, window=a.window, search=a.search)
 
 
 if __name__ == "__main__":

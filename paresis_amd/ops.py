@@ -945,7 +945,7 @@ def status_scan(img):
           "psx_status_scan_f32")
 
 
-def _positions(imgs, name):
+def _positions(imgs, name, kmin=3):
     """The K images of one side of an LCS call as a list of 2-D tensors: a [K, n, m] tensor, or a sequence of K 2-D tensors
     (e.g. the bin slices S[ibin] of the chains' [nbins, n, m] stacks).  Counts and shapes only: devices come after both
     sides are known, so that the message names the first thing that is wrong."""
@@ -955,8 +955,8 @@ def _positions(imgs, name):
         imgs = [imgs[k] for k in range(imgs.shape[0])]
     imgs = list(imgs)
     K = len(imgs)
-    if K < 3 or K > _lib.PSX_MAX_LCS:
-        raise PsxError("%s: K=%d positions outside [3, %d]" % (name, K, _lib.PSX_MAX_LCS))
+    if K < kmin or K > _lib.PSX_MAX_LCS:
+        raise PsxError("%s: K=%d positions outside [%d, %d]" % (name, K, kmin, _lib.PSX_MAX_LCS))
     for k, t in enumerate(imgs):
         if not isinstance(t, torch.Tensor) or t.dim() != 2:
             raise PsxError("%s[%d] must be a 2-D tensor" % (name, k))
@@ -1029,6 +1029,32 @@ def lcs_df(sample, reference, max_shift=None, out=None):
         check(lib().psx_lcs_df_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K,
                                    shape[0], shape[1], c_float(ms), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
                                    _stream()), "psx_lcs_df_f32")
+    return out
+
+
+def umpa(sample, reference, window=2, search=3, out=None):
+    """UMPA windowed speckle tracking of one energy bin (psx_umpa_f32): K in [1, PSX_MAX_LCS] sample / reference pairs in the
+    forms ops.lcs takes -> (transmission, dx, dy, residual), n x m float32.  Per interior pixel, the integer shift u = (a, b),
+    |a|, |b| <= search, that minimises the float64 least-squares cost of S_k(q) ~ T*R_k(q - u) over a uniform
+    (2*window+1)^2 window (no Hamming taper) and all K positions, refined per axis by a parabola through the neighbouring
+    costs; dx along axis 0, dy along axis 1, the sign of ops.lcs.  residual = cost/sum S^2 at the minimum.  Pixels closer
+    than window+search to a border are exactly (1, 0, 0, 0).  window in [1, PSX_MAX_UMPA_WINDOW], search in
+    [1, PSX_MAX_UMPA_SEARCH], n, m >= 2*(window+search)+1.  out: four caller-owned n x m float32 tensors to write into."""
+    S = _positions(sample, "sample", kmin=1)
+    R = _positions(reference, "reference", kmin=1)
+    for nm, v, cap in (("window", window, _lib.PSX_MAX_UMPA_WINDOW), ("search", search, _lib.PSX_MAX_UMPA_SEARCH)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
+            raise PsxError("%s must be an integer in [1, %d], got %r" % (nm, cap, v))
+    w, sr = int(window), int(search)
+    least = 2 * (w + sr) + 1
+    if S[0].shape[0] < least or S[0].shape[1] < least:
+        raise PsxError("images %dx%d smaller than %dx%d = 2*(window+search)+1" % (tuple(S[0].shape) + (least, least)))
+    shape, dev, _, out = _lcs_args(S, R, None, out, ("transmission", "dx", "dy", "residual"))
+    K = len(S)
+    with torch.cuda.device(dev):
+        check(lib().psx_umpa_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K,
+                                 shape[0], shape[1], w, sr, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _stream()),
+              "psx_umpa_f32")
     return out
 
 

@@ -9,19 +9,27 @@ module turns them into the sample's transmission, its refraction (displacement) 
                              detector pixels, along axis 0 / axis 1, with the sign of the chain's Dxreal / Dyreal;
                              dark_field=True (LCS-DF, K >= 4) adds the column x3*lap(R_k), the diffusion term of the X-ray
                              Fokker-Planck model (Morgan & Paganin, Sci. Rep. 9, 17465, 2019): df = -x3 in detector px^2
+    umpa(sample, reference)  UMPA ("Unified Modulated Pattern Analysis", Zdora et al., PRL 118, 203903, 2017; separable form:
+                             De Marco et al., Opt. Express 31, 635, 2023): per pixel, the integer shift |a|, |b| <= search
+                             that minimises the float64 least-squares cost of S(q) = T*R(q - u) over a uniform
+                             (2*window+1)^2 window (no Hamming taper, unlike the UMPA package) and the K >= 1 positions,
+                             refined to sub-pixel by a parabola per axis: displacements of several pixels, where the
+                             first-order LCS (|D| < 1 px) fails; also 'residual', the cost at the minimum over sum S^2
     scattering_angle(df, ...) df -> the chain's scattering angle theta in radians
     phase_gradient(...)      displacement -> phase gradient in radians per detector pixel
     integrate(gx, gy)        Frankot-Chellappa (IEEE PAMI 10, 1988) with mirror extension -> phase (zero mean)
     retrieve(results, ...)   all of it for every bin of main.run's {position: (Sample, Reference, ...)}
 
-Both steps are HIP kernels (csrc/retrieve.hip; the integration's transforms are rocFFT); nothing runs on the host but
+All steps are HIP kernels (csrc/retrieve.hip, csrc/umpa.hip; the integration's transforms are rocFFT); nothing runs on the host but
 argument checks.  Command line, for a run already on disk (main.py's layout):
 
     python -m paresis_amd.retrieval RUN_DIR [--energy KEV --pixel-um P --distance Z --magnification M]
                                             [--max-shift S] [--format .tif] [--dark-field]
+                                            [--method {lcs,umpa} --window W --search M]
 
 writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory; without the four physical parameters
 only transmission, dx and dy.  --dark-field (4 positions or more) adds df, and scattering with the physical parameters.
+--method umpa (1 position or more; no --dark-field, no --max-shift) tracks with UMPA and adds residual.
 """
 import argparse
 import os
@@ -46,6 +54,37 @@ def lcs(sample, reference, max_shift=None, dark_field=False):
         return {'transmission': t, 'dx': dx, 'dy': dy, 'df': df}
     t, dx, dy = ops.lcs(sample, reference, max_shift=max_shift)
     return {'transmission': t, 'dx': dx, 'dy': dy}
+
+
+def umpa(sample, reference, window=2, search=3):
+    """K >= 1 sample / reference images of one bin (the forms lcs takes) -> {'transmission', 'dx', 'dy', 'residual'}, n x m
+    float32 on the same device (ops.umpa): the shift of a uniform (2*window+1)^2 window within |a|, |b| <= search pixels,
+    sub-pixel by a parabola per axis.  Pixels closer than window+search to a border are (1, 0, 0, 0)."""
+    from . import ops
+    t, dx, dy, res = ops.umpa(sample, reference, window=window, search=search)
+    return {'transmission': t, 'dx': dx, 'dy': dy, 'residual': res}
+
+
+METHODS = ("lcs", "umpa")
+
+
+def check_method(method, npos, max_shift=None, dark_field=False):
+    """The argument rules of retrieve(): ValueError for an unknown method, too few positions (lcs: 3, LCS-DF: 4, umpa: 1), or
+    umpa with dark_field or max_shift.  Needs no GPU."""
+    if method not in METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
+    if method == "umpa":
+        if dark_field:
+            raise ValueError("method='umpa' has no dark-field term: dark_field is an option of method='lcs'")
+        if max_shift is not None:
+            raise ValueError("method='umpa' is bounded by its search range: max_shift is an option of method='lcs'")
+        if npos < 1:
+            raise ValueError("phase retrieval needs at least 1 position, got %d" % npos)
+        return
+    if npos < 3:
+        raise ValueError("phase retrieval needs at least 3 positions, got %d" % npos)
+    if dark_field and npos < 4:
+        raise ValueError("dark-field retrieval needs at least 4 positions, got %d" % npos)
 
 
 def _plan(device, n, m):
@@ -120,7 +159,8 @@ def _stack(results, positions, slot, device):
     return [dev[k] for k in range(dev.shape[0])]
 
 
-def retrieve(results, params=None, bins=None, energies=None, max_shift=None, device=None, dark_field=False):
+def retrieve(results, params=None, bins=None, energies=None, max_shift=None, device=None, dark_field=False, method='lcs',
+             window=2, search=3):
     """Retrieve every bin of a run: results = main.run's {position: (Sample, Reference, ...)} with [nbins, n, m] stacks (host or
     device; host stacks are uploaded once) -> {bin: {'transmission', 'dx', 'dy', 'phi'}}, device tensors.
 
@@ -129,13 +169,12 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
     params['energy_keV'] -- the run's mean detected energy, which is right for one bin only: a multi-bin run should pass
     each bin's own energy.  max_shift: clamp of dx, dy in pixels (None: no clamp).  dark_field: LCS-DF (4 positions or
     more): every bin also gets 'df' (detector px^2) and, with params, 'scattering' (theta, radians; scattering_angle);
-    'phi' then integrates the four-unknown system's dx, dy."""
-    import torch
+    'phi' then integrates the four-unknown system's dx, dy.  method='umpa' (1 position or more; window, search: umpa's):
+    every bin's maps come from umpa() instead, with 'residual'; 'phi' integrates its dx, dy the same way.  It takes neither
+    dark_field nor max_shift (ValueError)."""
     positions = sorted(results)
-    if len(positions) < 3:
-        raise ValueError("phase retrieval needs at least 3 positions, got %d" % len(positions))
-    if dark_field and len(positions) < 4:
-        raise ValueError("dark-field retrieval needs at least 4 positions, got %d" % len(positions))
+    check_method(method, len(positions), max_shift, dark_field)
+    import torch
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     S = _stack(results, positions, 0, dev)
     R = _stack(results, positions, 1, dev)
@@ -145,7 +184,10 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
         raise ValueError("energies must hold one value per retrieved bin (%d), got %d" % (len(bins), len(energies)))
     out = {}
     for i, b in enumerate(bins):
-        r = lcs([s[b] for s in S], [s[b] for s in R], max_shift=max_shift, dark_field=dark_field)
+        if method == "umpa":
+            r = umpa([s[b] for s in S], [s[b] for s in R], window=window, search=search)
+        else:
+            r = lcs([s[b] for s in S], [s[b] for s in R], max_shift=max_shift, dark_field=dark_field)
         if params is not None:
             e = params['energy_keV'] if energies is None else energies[i]
             r['phi'] = integrate(r['dx'], r['dy'],
@@ -157,12 +199,13 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
 
 
 def save_retrieval(r, directory, exp_id, fmt):
-    """Write one bin's maps as directory/retrieval/<name>_<exp_id><fmt> (name: transmission, dx, dy[, phi][, df][, scattering])."""
+    """Write one bin's maps as directory/retrieval/<name>_<exp_id><fmt> (name: transmission, dx, dy[, phi][, df][, scattering]
+    [, residual])."""
     from .InputOutput.pagailleIO import save_image
     d = os.path.join(directory, "retrieval")
     os.makedirs(d, exist_ok=True)
     paths = []
-    for name in ("transmission", "dx", "dy", "phi", "df", "scattering"):
+    for name in ("transmission", "dx", "dy", "phi", "df", "scattering", "residual"):
         if name in r:
             paths.append(os.path.join(d, "%s_%s%s" % (name, exp_id, fmt)))
             save_image(r[name].detach().cpu().numpy(), paths[-1])
@@ -173,11 +216,11 @@ _SAMPLE = re.compile(r"^sampleImage_(.+)_(\d+)(\.[A-Za-z0-9]+)$")
 _REF = re.compile(r"^ReferenceImage_(.+)_(\d+)(\.[A-Za-z0-9]+)$")
 
 
-def discover(run_dir):
+def discover(run_dir, min_positions=3):
     """main.run's layout under run_dir -> [(bin_dir, exp_id, fmt, [(position, sample_path, reference_path), ...])], one entry
     per bin directory (run_dir itself for a one-bin run, run_dir/NN_NNkev/ otherwise), positions in increasing order.
     Raises ValueError when a sample has no reference partner (or the reverse), when one directory holds several runs or
-    formats, or when fewer than 3 positions are found.  Needs no GPU."""
+    formats, or when fewer than min_positions positions are found (3: LCS; UMPA takes 1).  Needs no GPU."""
     run_dir = os.path.abspath(run_dir)
     cands = [run_dir] + sorted(os.path.join(run_dir, d) for d in os.listdir(run_dir)
                                if re.match(r"^\d+_\d+kev$", d) and os.path.isdir(os.path.join(run_dir, d)))
@@ -206,26 +249,27 @@ def discover(run_dir):
             raise ValueError("%s holds several runs or formats %s: give one run's directory" % (d, runs))
         exp_id, fmt = runs[0]
         pos = sorted(k[1] for k in s)
-        if len(pos) < 3:
-            raise ValueError("%s: phase retrieval needs at least 3 positions, found %d" % (d, len(pos)))
+        if len(pos) < min_positions:
+            raise ValueError("%s: phase retrieval needs at least %d positions, found %d" % (d, min_positions, len(pos)))
         found.append((d, exp_id, fmt, [(p, s[(exp_id, p, fmt)], r[(exp_id, p, fmt)]) for p in pos]))
     if not found:
         raise ValueError("no sample/ and ref/ images of main.run's layout under %s" % run_dir)
     return found
 
 
-def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None, dark_field=False):
+def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None, dark_field=False, method='lcs', window=2, search=3):
     """discover() + lcs (+ integrate when params are given) + save_retrieval for every bin directory; returns the paths.
-    dark_field: LCS-DF (4 positions or more), df (+ scattering with params) written too."""
+    dark_field: LCS-DF (4 positions or more), df (+ scattering with params) written too.  method='umpa' (window, search):
+    UMPA instead of LCS, 1 position or more, residual written too."""
     import torch
     from .InputOutput.pagailleIO import openImage
     written = []
     dev = torch.device("cuda", torch.cuda.current_device())
-    for d, exp_id, in_fmt, pairs in discover(run_dir):
+    for d, exp_id, in_fmt, pairs in discover(run_dir, min_positions=1 if method == "umpa" else 3):
         S = torch.from_numpy(np.stack([np.asarray(openImage(s), dtype=np.float32) for _, s, _ in pairs])).to(dev)
         R = torch.from_numpy(np.stack([np.asarray(openImage(r), dtype=np.float32) for _, _, r in pairs])).to(dev)
         res = retrieve({p: (S[i:i + 1], R[i:i + 1]) for i, (p, _, _) in enumerate(pairs)}, params, max_shift=max_shift,
-                       dark_field=dark_field)[0]
+                       dark_field=dark_field, method=method, window=window, search=search)[0]
         written += save_retrieval(res, d, exp_id, fmt or in_fmt)
     return written
 
@@ -243,7 +287,16 @@ def main(argv=None):
     ap.add_argument("--dark-field", action="store_true",
                     help="LCS-DF (4 positions or more): also df (detector px^2) and, with the physical parameters, scattering "
                          "(rad)")
+    ap.add_argument("--method", choices=METHODS, default="lcs",
+                    help="lcs (3 positions or more, |D| < 1 px) or umpa (1 position or more, |D| up to --search px)")
+    ap.add_argument("--window", type=int, default=2, help="--method umpa: half-width w of the (2w+1)^2 window, 1..8")
+    ap.add_argument("--search", type=int, default=3, help="--method umpa: largest integer shift searched, 1..8")
     a = ap.parse_args(argv)
+    if a.method == "umpa":
+        if a.dark_field or a.max_shift is not None:
+            ap.error("--dark-field and --max-shift are options of --method lcs")
+        if not 1 <= a.window <= 8 or not 1 <= a.search <= 8:
+            ap.error("--window and --search must be in 1..8")
     phys = (a.energy, a.pixel_um, a.distance, a.magnification)
     if any(v is not None for v in phys) and any(v is None for v in phys):
         ap.error("--energy, --pixel-um, --distance and --magnification go together")
@@ -253,7 +306,8 @@ def main(argv=None):
         for d, _, _, pairs in discover(a.run_dir):
             if len(pairs) < 4:
                 ap.error("--dark-field needs at least 4 positions; %s has %d" % (d, len(pairs)))
-    for p in retrieve_run_dir(a.run_dir, params, max_shift=a.max_shift, fmt=a.format, dark_field=a.dark_field):
+    for p in retrieve_run_dir(a.run_dir, params, max_shift=a.max_shift, fmt=a.format, dark_field=a.dark_field, method=a.method,
+                              window=a.window, search=a.search):
         print(p)
     return 0
 

@@ -1,12 +1,17 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
 integration's extended grid is 2n x 2m complex64.  Times are HIP-event pairs per launch (psx_profile_summary), after warm-up,
 on a GPU the process has to itself.  --host adds the float64
 numpy oracle's time at the same sizes -- HOST time, one run, for scale only.
+
+k_umpa (UMPA, window w, search s) reads 2K images and writes 4: the same 4*n*m*(2K + 4) bytes from HBM, but it is bound by its
+float64 product sums: n*m*(2s+1)^2*K useful FMAs, set against the v_fma_f64 rate that tools/valu_bench measures (FMA64_CYCLES
+per wave64 instruction and SIMD).  Its cases end with time(w = 4)/time(w = 1): the separable window sums keep it below 3,
+direct ones would give about 9.
 """
 import argparse
 import ctypes
@@ -23,6 +28,8 @@ from paresis_amd import ops, retrieval  # noqa: E402
 from paresis_amd._lib import lib  # noqa: E402
 
 PEAK = 8e12
+FMA64_CYCLES, CLOCK, SIMDS = 4.0, 2.4e9, 256 * 4        # tools/valu_bench: cycles per wave64 v_fma_f64 and SIMD
+FMA64_PEAK = SIMDS * 64 / FMA64_CYCLES * CLOCK          # float64 FMAs per second, all lanes busy
 
 
 def summary():
@@ -85,13 +92,43 @@ def case(n, m, K, reps, host):
         print("    numpy oracle (HOST time): lcs %.2f s, integrate %.2f s, lcs_df %.2f s" % (t1 - t0, t2 - t1, t3 - t2))
 
 
+def umpa_case(n, m, K, w, s, reps):
+    g = torch.Generator(device="cuda").manual_seed(n + K)
+    S = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
+    R = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
+    outs = tuple(torch.empty((n, m), device="cuda") for _ in range(4))
+    for _ in range(3):
+        ops.umpa(S, R, window=w, search=s, out=outs)
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        ops.umpa(S, R, window=w, search=s, out=outs)
+    torch.cuda.synchronize()
+    c, ms = summary()["k_umpa"]
+    lib().psx_profile_enable(0)
+    t = ms / c * 1e-3
+    price = 4.0 * n * m * (2 * K + 4)
+    fma = float(n) * m * (2 * s + 1) ** 2 * K
+    print("%dx%d K=%d w=%d s=%d  k_umpa %.1f us  price %.1f MB (%.1f us at 8 TB/s)  %.2f G FMA64 (%.1f us at %.1f T FMA/s) = %.2f of "
+          "the float64 FMA rate" % (n, m, K, w, s, t * 1e6, price / 1e6, price / PEAK * 1e6, fma / 1e9, fma / FMA64_PEAK * 1e6,
+                                    FMA64_PEAK / 1e12, fma / t / FMA64_PEAK))
+    return t
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--umpa-only", action="store_true")
     a = ap.parse_args()
-    for n, m, K in ((2048, 2048, 16), (2048, 2048, 64), (200, 200, 12)):
+    for n, m, K in () if a.umpa_only else ((2048, 2048, 16), (2048, 2048, 64), (200, 200, 12)):
         case(n, m, K, a.reps, a.host)
+    umpa_case(2048, 2048, 16, 2, 3, a.reps)
+    umpa_case(200, 200, 12, 2, 3, a.reps)
+    t1 = umpa_case(2048, 2048, 16, 1, 3, a.reps)
+    t4 = umpa_case(2048, 2048, 16, 4, 3, a.reps)
+    print("k_umpa 2048x2048 K=16 s=3: time(w=4)/time(w=1) = %.2f" % (t4 / t1))
+    umpa_case(2048, 2048, 16, 8, 8, max(a.reps // 10, 2))
 
 
 if __name__ == "__main__":

@@ -148,6 +148,12 @@ __device__ __forceinline__ void mats_eval(const Mats &m, int64_t p, double &ph, 
 // smallest instantiated count >= n
 inline int mats_variant(int n) { return n <= 4 ? n : 8; }
 
+// The map pointers of a kernel that takes them apart from a packed Mats (its coefficients come per image or per source):
+// every slot the instantiated variant loads, pack_mats' padding included.  The ONE place such a table is built.
+inline void map_table(const float *(&T)[PSX_MAX_MAT], const Mats &m) {
+    for (int i = 0; i < PSX_MAX_MAT; ++i) T[i] = i < mats_variant(m.n) ? m.T[i] : nullptr;
+}
+
 // instantiate the statement for the variant matching n; NM is the compile-time count inside it
 #define PSX_DISPATCH_NMAT(n, ...)                    \
     switch (psx::mats_variant(n)) {                  \

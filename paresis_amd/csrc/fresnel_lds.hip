@@ -1999,10 +1999,8 @@ int lds_engine_propagate_sources(psx_fresnel_plan *p, const SourcesArgs &a) {
         SrcBatch b = {};
         MapPtrs mp = {};
         int vec_ok = p->Ny % 4 == 0;
-        for (int i = 0; i < a.maps.n && i < PSX_MAX_MAT; ++i) {
-            mp.T[i] = a.maps.T[i];
-            vec_ok = vec_ok && ((uintptr_t)a.maps.T[i] % 16 == 0);
-        }
+        map_table(mp.T, a.maps);                      // 5-7 maps run the <8> variant: the padded slots are loaded too
+        for (int i = 0; i < a.maps.n; ++i) vec_ok = vec_ok && ((uintptr_t)a.maps.T[i] % 16 == 0);
         for (int s = 0; s < a.n_src; ++s) {
             b.src[s] = a.wave_in ? a.wave_in[s] : nullptr;
             vec_ok = vec_ok && ((uintptr_t)b.src[s] % 16 == 0);

@@ -268,11 +268,9 @@ int psx_accumulate_many_f32(float *acc, const float *const *imgs, const float *s
     if (n == 0) return 0;
     ImgBatch b = {};
     b.n_img = n_img;
+    map_table(b.T, m);                                // 5-7 maps run k_accumulate_many<8>: the padded slots are loaded too
     int vec = (uintptr_t)acc % 16 == 0;
-    for (int i = 0; i < nmat && i < PSX_MAX_MAT; ++i) {
-        b.T[i] = T[i];
-        vec = vec && (uintptr_t)T[i] % 16 == 0;
-    }
+    for (int i = 0; i < nmat; ++i) vec = vec && (uintptr_t)T[i] % 16 == 0;
     for (int e = 0; e < n_img; ++e) {
         PSX_REQUIRE(imgs[e] != nullptr, "psx_accumulate_many_f32: null image %d", e);
         b.img[e] = imgs[e];

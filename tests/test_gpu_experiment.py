@@ -104,6 +104,49 @@ def test_energy_batched_chain_matches_energy_loop():
     assert relmax(outs[True, 0][0].cpu().numpy(), g[t + "Sample"]) < TOL
 
 
+def test_energy_batched_chain_takes_a_five_map_stack():
+    """The sample's map split into four float32 slices with their own coefficients, in air: the Propag image's stack
+    concat(air, sample) holds 5 maps, which the batched calls (psx_fresnel_propagate_sources, psx_accumulate_many_f32) run
+    through their NM = 8 kernels on three padded slots.  Batched against the per-energy loop and against the oracle."""
+    g = load("experiment.npz")
+    cfg = experiment_cfg(g, "poly/Fresnel", orc.Obj)
+    assert not cfg["inVacuum"] and cfg["air"] is not None and len(cfg["spectrum"]) > 1
+    rng = np.random.default_rng(4)
+    base = np.asarray(cfg["sample"].geometry[0], dtype=np.float32)
+    geom = np.stack([(base * f).astype(np.float32) for f in rng.uniform(0.5, 1.5, 4) / 4])
+    d0, b0 = np.asarray(cfg["sample"].delta)[0], np.asarray(cfg["sample"].beta)[0]
+    f = rng.uniform(0.6, 1.8, (4, 2))
+    cfg["sample"] = orc.Obj(geom, [list(d0 * f[m, 0]) for m in range(4)], [list(b0 * f[m, 1]) for m in range(4)])
+    cfg["air"] = orc.Obj(np.asarray(cfg["air"].geometry, dtype=np.float32), cfg["air"].delta, cfg["air"].beta)
+    if cfg["plate"] is not None:
+        cfg["plate"] = orc.Obj(np.asarray(cfg["plate"].geometry, dtype=np.float32), cfg["plate"].delta, cfg["plate"].beta)
+    mem = lambda p: np.asarray(g["poly/Fresnel/p%d/membrane" % p], dtype=np.float32)
+    outs = {}
+    for batched in (True, False):
+        exp = build_experiment(cfg, "Fresnel", sample_materials=["slice%d" % m for m in range(4)])
+        exp.exp_dict["batchEnergies"] = batched
+        assert not exp._folds("Fresnel") and len(exp.mySampleofInterest.myMaterials) + len(exp.myAirVolume.myMaterials) == 5
+        for point in (0, 1):
+            exp.myMembrane.myGeometry = mem(point)
+            exp.exp_dict["meanEnergy"] = 0
+            out = exp.computeSampleAndReferenceImages(point)
+            outs[batched, point] = [a.clone() for a in out] + [exp.exp_dict["meanEnergy"]]
+    bins = list(cfg["bins"])                                                # point 0 extends them, like the detector's own
+    for point in (0, 1):
+        b, l = outs[True, point], outs[False, point]
+        for k in range(4 if point == 0 else 2):
+            assert relmax(b[k].cpu().numpy(), l[k].cpu().numpy()) < 1e-6, (point, k)
+        assert abs(b[4] - l[4]) < 1e-9 * abs(l[4])
+        c = dict(cfg)
+        c["bins"] = bins
+        c["membrane"] = orc.Obj(mem(point).astype(np.float64), cfg["membrane"].delta, cfg["membrane"].beta)
+        ref = orc.compute_fresnel(c, point)
+        bins = c["bins"]
+        for i, nm in enumerate(("Sample", "Reference", "Propag", "White")):
+            assert relmax(b[i].cpu().numpy(), ref[i]) < TOL, (point, nm)
+        assert abs(b[4] - ref[4]) < 1e-4
+
+
 def test_energy_batched_rt_chain_matches_energy_loop():
     """The ray-tracing chain with the energies of a bin taken together (psx_refract_batch_f32) against the per-energy loop:
     same images (far rays are summed by float atomics in both), same displacement maps, same mean energy."""

@@ -1,9 +1,15 @@
 """Float64 numpy oracle of the UMPA contract (include/paresis_hip.h: psx_umpa_f32; csrc/umpa.hip).
 
-umpa():         the maps, the fallback mask and gap = (second-smallest - smallest valid cost)/E per pixel.
+umpa():         the maps, the fallback mask, gap = (second-smallest - smallest valid cost)/E and u* = (a, b) per pixel.
 umpa_brute():   the same contract as plain loops over pixels, candidates and window pixels (tiny images only).
 warped_model(): sample images warped by smooth displacement fields of several pixels.
 compare():      the comparison rule of the GPU tests (border band exact, fallback masks equal, near-ties excluded).
+
+On images of small integers every sum E, B, C is an exact integer in float64 in any order, and what follows is a fixed
+sequence of single IEEE operations, so a correct kernel gives umpa()'s four maps bit for bit:
+integer_model(): such images, with a block without reference, a block of negative sample, or an exactly periodic reference.
+classes():       which pixels of an instance are all-skipped, partly skipped, fallback through T <= 0, ordinary.
+compare_exact(): np.array_equal on the four whole maps, no exclusion.
 """
 import numpy as np
 
@@ -90,6 +96,9 @@ def umpa(S, R, window=2, search=3):
     out['gap'][inner] = gap
     out['interior'] = np.zeros((n, m), bool)
     out['interior'][inner] = True
+    for key, val in (('a', a0), ('b', b0)):                          # u*, 0 in the border band; meaningless where all skipped
+        out[key] = np.zeros((n, m), np.int64)
+        out[key][inner] = val
     return out
 
 
@@ -174,3 +183,139 @@ def compare(got, o, window, search, cap=1e-4, label=""):
     if live.any():
         assert f['ddx'] <= 1e-5 and f['ddy'] <= 1e-5 and f['dT'] <= 1e-5 and f['dres'] <= 1e-7, f
     return f
+
+
+# ------------------------------------------------------------------------------------------------ exact comparison
+KEYS = ('transmission', 'dx', 'dy', 'residual')
+TILE_H = 16                                                          # the kernel's output tile: 16 x tile_width(w)
+
+
+def tile_width(w):
+    return 32 if w <= 4 else 16
+
+
+def integer_shape(w, s):
+    """The smallest convenient image whose interior has pixels in two tile rows and two tile columns at every (w, s), both
+    last tiles ragged (n and m are odd), with room for the two planted blocks of side 2(w+s)+3 in opposite corners."""
+    return 4 * (w + s) + 13, 4 * (w + s) + tile_width(w) + 5
+
+
+def integer_model(w, s, K, seed, period=None, shape=None, vmax=4095, block=4):
+    """S, R: K float32 image pairs holding integers only.  R_k is random in [0, vmax], or with period = (p, q) an exact
+    tiling of a random p x q cell with entries in [1, vmax]; S_k(r) = 2 R_k(r - D(r)) + noise, D an integer field that is
+    constant on block x block pixels with |a|, |b| <= s (indices wrap), noise integer in [0, 7].  |S| <= 2 vmax + 7, so every
+    window sum is below K (2w+1)^2 (2 vmax + 7)^2 = 1.3e12 at K = 64, w = 8, vmax = 4095: 2^53 = 9.0e15 is far.
+    With neither period nor shape (the image is then integer_shape(w, s)) two blocks of side 2(w+s)+3 are planted: R_k = 0
+    in the first corner (before S is formed), so that 3 x 3 interior pixels have every candidate skipped and those around
+    them some; S_k negated in the last corner, so that T(u) < 0 at every candidate of the pixels well inside.  D = 0 on the
+    rows [Z-2w, Z] over the zero block, Z its side: the pixels of row Z-w then match at u = (0, 0) through the one row of
+    their window that lies outside the block, while their candidate (1, 0) lies inside it and is skipped."""
+    rng = np.random.default_rng(seed)
+    planted = period is None and shape is None
+    n, m = shape if shape is not None else integer_shape(w, s)
+    Z = 2 * (w + s) + 3
+    tiles = (-(-n // block), -(-m // block))
+    A = np.kron(rng.integers(-s, s + 1, tiles), np.ones((block, block), np.int64))[:n, :m]
+    Bf = np.kron(rng.integers(-s, s + 1, tiles), np.ones((block, block), np.int64))[:n, :m]
+    if planted:                                                      # see below: D = 0 on the rows across the block's last edge
+        A[Z - 2 * w:Z + 1, :Z] = 0
+        Bf[Z - 2 * w:Z + 1, :Z] = 0
+    ii, jj = np.indices((n, m))
+    si, sj = (ii - A) % n, (jj - Bf) % m
+    S, R = [], []
+    for _ in range(K):
+        if period is None:
+            r = rng.integers(0, vmax + 1, (n, m))
+        else:
+            cell = rng.integers(1, vmax + 1, period)
+            r = np.tile(cell, (n // period[0] + 1, m // period[1] + 1))[:n, :m]
+        if planted:
+            r[:Z, :Z] = 0
+        x = 2 * r[si, sj] + rng.integers(0, 8, (n, m))
+        if planted:
+            x[n - Z:, m - Z:] *= -1
+        S.append(x.astype(np.float32))
+        R.append(r.astype(np.float32))
+    assert all(np.array_equal(x, np.rint(x)) and np.abs(x).max() <= 2 * vmax + 7 for x in S + R)
+    return S, R
+
+
+def classes(S, R, window, search):
+    """Boolean n x m masks from the oracle's own cost volume (False in the border band): 'all_skipped'; 'some_skipped';
+    'lacks_neighbour' (some skipped, not a fallback pixel, and u* has |a*| < s with L(a*-1, b*) or L(a*+1, b*) skipped, or
+    the same along b); 'nonpositive' (a valid u* with T(u*) <= 0); 'ordinary' (no candidate skipped, T(u*) > 0).  And the
+    integer maps 'tile_row', 'tile_col' of the kernel's 16 x tile_width(w) output tiles."""
+    w, s = int(window), int(search)
+    n, m = np.asarray(S[0]).shape
+    E, B, C = cost_volume(S, R, w, s)
+    nc = 2 * s + 1
+    skipped = C == 0
+    Cs = np.where(skipped, 1.0, C)
+    L = np.where(skipped, np.inf, E[None] - B * B / Cs)
+    idx = np.argmin(L, axis=0)
+    T0 = np.take_along_axis(B / Cs, idx[None], 0)[0]
+    allsk = skipped.all(0)
+    a0, b0 = idx // nc - s, idx % nc - s
+    at = lambda k: np.take_along_axis(skipped, np.clip(k, 0, nc * nc - 1)[None], 0)[0]
+    lacks = ((np.abs(a0) < s) & (at(idx - nc) | at(idx + nc))) | ((np.abs(b0) < s) & (at(idx - 1) | at(idx + 1)))
+    vals = {'all_skipped': allsk, 'some_skipped': skipped.any(0) & ~allsk,
+            'lacks_neighbour': skipped.any(0) & ~allsk & (T0 > 0) & lacks, 'nonpositive': ~allsk & ~(T0 > 0),
+            'ordinary': ~skipped.any(0) & (T0 > 0)}
+    band = w + s
+    out = {}
+    for key, val in vals.items():
+        out[key] = np.zeros((n, m), bool)
+        out[key][band:n - band, band:m - band] = val
+    ii, jj = np.indices((n, m))
+    out['tile_row'], out['tile_col'] = ii // TILE_H, jj // tile_width(w)
+    return out
+
+
+def compare_exact(got, o, ties=False, label=""):
+    """np.array_equal of `got`'s four maps with the oracle's over the whole image: no exclusion, no cap, no tolerance.
+    Valid only where the inputs make the contract's float64 sums exact (integer_model).  An interior pixel whose two best
+    costs are equal (gap == 0) is an error of the test's inputs unless ties=True: then the first minimum is what is asked.
+    Prints and returns the counts; on a difference prints the first differing pixel of the first differing map."""
+    inner = o['interior']
+    tie = inner & (o['gap'] == 0)
+    f = {'pixels': int(inner.size), 'interior': int(inner.sum()), 'ties': int(tie.sum())}
+    print("umpa exact %s: %s" % (label, f))
+    assert ties or not tie.any(), "exact ties in inputs that were to have none: %s" % f
+    for key in KEYS:
+        assert np.isfinite(o[key]).all(), "the oracle's %s is not finite" % key
+        assert got[key].dtype == np.float32 and got[key].shape == inner.shape, key
+        if not np.array_equal(got[key], o[key]):
+            i, j = (int(x[0]) for x in np.nonzero(got[key] != o[key]))
+            text = ("umpa exact %s: %s differs at %d pixels, first (%d, %d): got %r, oracle %r, u* = (%d, %d), fallback %s, "
+                    "gap %.3g; there got %s, oracle %s"
+                    % (label, key, int((got[key] != o[key]).sum()), i, j, got[key][i, j], o[key][i, j], o['a'][i, j],
+                       o['b'][i, j], o['fallback'][i, j], o['gap'][i, j], [float(got[k][i, j]) for k in KEYS],
+                       [float(o[k][i, j]) for k in KEYS]))
+            print(text)
+            raise AssertionError(text)
+    return f
+
+
+# The instances that tests/test_gpu_umpa.py runs and tests/test_umpa_host.py qualifies: every (w, s), K cycling through 1..4
+# (both parities of the kernel's double buffer), and periodic references at both tile widths and every chunk count.
+PAIRS = [(w, s) for w in range(1, 9) for s in range(1, 9)]
+TIE_CASES = [(2, 3, (2, 3)), (1, 8, (3, 2)), (8, 5, (4, 5)), (5, 7, (2, 2)), (6, 2, (2, 3)), (3, 4, (3, 3))]    # w, s, period
+
+
+def sweep_K(w, s):
+    return 1 + (w + s) % 4
+
+
+def sweep_instance(w, s, rep=0):
+    return integer_model(w, s, sweep_K(w, s), seed=2000 + 100 * w + s + 10000 * rep)
+
+
+def tie_instance(w, s, period):
+    return integer_model(w, s, 2 + (w + s) % 2, seed=3000 + 100 * w + s, period=period)
+
+
+def warped_instance(w, s, rep=0):
+    """The float images of the warped sweep: displacements up to about s - 1/2 on (2(w+s)+21) x (2(w+s)+TW+9) pixels."""
+    q = w + s
+    return warped_model(2 * q + 21, 2 * q + tile_width(w) + 9, sweep_K(w, s), seed=1000 + 10 * w + s + 10000 * rep,
+                        dmax=max(0.5, s - 0.5))[3:]

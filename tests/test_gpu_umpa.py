@@ -16,6 +16,7 @@ from tests import _umpa_oracle as ou
 pytestmark = pytest.mark.gpu
 
 KEYS = ('transmission', 'dx', 'dy', 'residual')
+MULT = max(1, int(os.environ.get("PSX_FUZZ", "1")))                  # PSX_FUZZ=k: the two 64-pair sweeps under k seeds
 
 
 def _cuda(a):
@@ -108,6 +109,61 @@ def test_umpa_fallback_bits():
         for key, v in zip(KEYS, (1.0, 0.0, 0.0, 0.0)):
             assert np.array_equal(g[key][blk], np.full((8, 8), v, np.float32)), key
     ou.compare(g, o, 1, 1, cap=None, label="fallback blocks")
+
+
+# ------------------------------------------------------------------------------------------ every (w, s), bit for bit
+# The host picks one of 16 kernels, tile width 32 (w <= 4) or 16 times s = 1..8, and the LDS layout, the chunks of a candidate
+# row, the surplus candidate and the prologue's rows per thread vary with (w, s): all 64 pairs run.  On integer images the
+# contract's sums are exact and every later step is one IEEE operation (tests/_umpa_oracle.py), so the four maps are compared
+# with np.array_equal over the whole image.  tests/test_umpa_host.py shows that these inputs hold all-skipped, partly skipped,
+# T <= 0 and ordinary pixels in several tiles and no exact tie, and that wrong kernels of five kinds would differ on them.
+@pytest.mark.parametrize("w,s", ou.PAIRS)
+def test_umpa_every_window_and_search_exact(w, s):
+    for rep in range(MULT):
+        S, R = ou.sweep_instance(w, s, rep)
+        o = ou.umpa(S, R, w, s)
+        assert o['fallback'].sum() > 9                               # the 3 x 3 all-skipped pixels and the T <= 0 block
+        ou.compare_exact(_gpu_umpa(S, R, w, s), o, label="w=%d s=%d K=%d %dx%d" % ((w, s, len(S)) + S[0].shape))
+
+
+@pytest.mark.parametrize("w,s,period", ou.TIE_CASES)
+def test_umpa_ties_take_the_first_minimum(w, s, period):
+    """A reference of period (p, q) makes L(u) == L(u + (p, 0)) == L(u + (0, q)) exactly at every interior pixel: the first
+    minimum in scan order is asked for, with its parabola.  Both tile widths; one, two and three chunks per candidate row."""
+    S, R = ou.tie_instance(w, s, period)
+    o = ou.umpa(S, R, w, s)
+    f = ou.compare_exact(_gpu_umpa(S, R, w, s), o, ties=True, label="period %s w=%d s=%d" % (period, w, s))
+    assert f['ties'] == f['interior'] > 0
+
+
+@pytest.mark.parametrize("w,s", ou.PAIRS)
+def test_umpa_every_window_and_search_warped(w, s):
+    """Float images with displacements up to about s - 1/2 under the parity rule, cap 1e-4 (at the committed seed the oracle
+    alone excludes no pixel: tests/test_umpa_host.py)."""
+    for rep in range(MULT):
+        S, R = ou.warped_instance(w, s, rep)
+        f = ou.compare(_gpu_umpa(S, R, w, s), ou.umpa(S, R, w, s), w, s, label="warped %dx%d K=%d" % (S[0].shape + (len(S),)))
+        assert f['compared'] > 0
+
+
+@pytest.mark.parametrize("w,s", ou.PAIRS)
+def test_umpa_smallest_images(w, s):
+    """One interior pixel, and one interior row / column of 40 pixels (two or three tiles along it)."""
+    q = 2 * (w + s) + 1
+    for shape in ((q, q), (q, q + 39), (q + 39, q)):
+        S, R = ou.integer_model(w, s, ou.sweep_K(w, s), seed=4000 + 100 * w + s, shape=shape)
+        o = ou.umpa(S, R, w, s)
+        assert o['interior'].sum() == (shape[0] - q + 1) * (shape[1] - q + 1)
+        ou.compare_exact(_gpu_umpa(S, R, w, s), o, label="w=%d s=%d %dx%d" % ((w, s) + shape))
+
+
+@pytest.mark.parametrize("w,s", [(4, 8), (5, 1), (8, 7)])
+def test_umpa_many_positions_exact(w, s):
+    """K = 64 (the most) and 63.  |S| <= 2*4095 + 7 and R <= 4095, so E, B, C <= 64 * 17^2 * 8197^2 = 1.25e12 at w = 8: exact
+    integers in float64 (2^53 = 9.0e15) with vmax as everywhere else."""
+    for K in (64, 63):
+        S, R = ou.integer_model(w, s, K, seed=5000 + K)
+        ou.compare_exact(_gpu_umpa(S, R, w, s), ou.umpa(S, R, w, s), label="w=%d s=%d K=%d" % (w, s, K))
 
 
 def test_umpa_input_forms_streams_and_no_allocation_on_reuse():

@@ -405,6 +405,26 @@ int psx_lcs_df_f32(const float *const *S, const float *const *R, int K, int n, i
 #define PSX_MAX_UMPA_SEARCH 8
 int psx_umpa_f32(const float *const *S, const float *const *R, int K, int n, int m, int window, int search,
                  float *transmission, float *dx, float *dy, float *residual, void *stream);
+/* UMPA with its dark-field (visibility) term, the third modality of Zdora et al.: psx_umpa_f32 with the model
+ *   S_k(q) ~ alpha*R_k(q - u) + beta*mu_k = T*[mu_k + V*(R_k(q - u) - mu_k)],  T = alpha + beta,  V = alpha/T,
+ * mu_k the mean intensity of reference frame k: a sample that blurs the speckle lowers their visibility by V < 1.
+ *   mean: HOST array of K finite float64 values mu_k (copied into the argument block).
+ *   K, window = w, search = s, the image sizes, the border band, the candidate order, "first strict minimum", the parabola
+ *   and the argument errors are psx_umpa_f32's, word for word.
+ *   Interior pixel r, sums over k and over q in the window around r, all in float64 (any order): E, B(u), C(u) as
+ *   psx_umpa_f32, and
+ *     F = sum mu_k S_k(q),  G(u) = sum mu_k R_k(q-u),  H = (2w+1)^2 sum_k mu_k^2.
+ *   Then, each ONE rounded IEEE operation (no contraction into fma anywhere in the sequence):
+ *     p = C*H;  q = G*G;  det = p - q;  the candidate is skipped unless det > 1e-12*p (which covers C == 0, H == 0 and a
+ *     reference window proportional to mu);
+ *     alpha = (B*H - F*G)/det;  beta = (C*F - G*B)/det;  L = E - (alpha*B + beta*F);  T = alpha + beta;
+ *     u*, da, db exactly as psx_umpa_f32, on this L;
+ *     transmission = T(u*), visibility = alpha(u*)/T(u*), residual = max(L(u*), 0)/E, dx, dy as psx_umpa_f32, as float32;
+ *     (1, 0, 0, visibility 1, residual 0) exactly when every candidate is skipped or T(u*) <= 0, and in the border band.
+ *   visibility is not clamped: noise and model error give values above 1 or below 0, which are returned as they are.
+ * One launch, no scratch memory, the image traffic of psx_umpa_f32. */
+int psx_umpa_df_f32(const float *const *S, const float *const *R, const double *mean, int K, int n, int m, int window,
+                    int search, float *transmission, float *dx, float *dy, float *visibility, float *residual, void *stream);
 /* Frankot-Chellappa integration (IEEE PAMI 10, 1988) of the gradient field scale*(gx, gy) (rad per pixel along axis 0 / 1)
  * with mirror extension: on the 2n x 2m grid gx is odd in axis 0 and even in axis 1, gy even in axis 0 and odd in axis 1;
  * P = (-i kx Gx^ - i ky Gy^)/(kx^2 + ky^2), P(0) = 0, kx = 2 pi fftfreq(2n), ky = 2 pi fftfreq(2m); phi = Re ifft2(P) on

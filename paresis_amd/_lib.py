@@ -23,7 +23,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class PsxError(RuntimeError):
@@ -102,6 +102,7 @@ PROTOTYPES = {
     "psx_lcs_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp]),
     "psx_lcs_df_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp, _vp]),
     "psx_umpa_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, _vp]),
+    "psx_umpa_df_f32": (c_int, [_vpp, _vpp, _vp, c_int, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "psx_integrate_plan_create": (c_int, [c_int, c_int, _vpp]),
     "psx_integrate_plan_destroy": (c_int, [_vp]),
     "psx_integrate_plan_bytes": (c_size_t, [_vp]),

@@ -22,6 +22,13 @@
 //   registers (statically indexed: the chunk loop is unrolled), which is why the search half-width is a template parameter.
 // Nothing outside the images is ever read: staged pixels outside are 0 and belong to border-band windows only, whose pixels
 // get (1, 0, 0, 0) by the border rule.
+//
+// Dark field (psx_umpa_df_f32, k_umpa<TW, S, true>): the model S_k(q) ~ alpha*R_k(q - u) + beta*mu_k, mu_k the mean of reference
+// frame k, T = alpha + beta, visibility V = alpha/T.  The same kernel under `if constexpr (DF)`, with
+//   F = box_w[sum_k mu_k S_k] beside E (registers), G(u)(r) = box_w[sum_k mu_k R_k](r - u) beside C (a second LDS map Gb laid
+//   out like Cb, from the loads prologue 1 makes anyway), H = (2w+1)^2 sum_k mu_k^2 (host), mu and H in the argument block;
+//   per candidate the 2 x 2 normal equations (umpa_df_solve, every operation rounded on its own) instead of E - B*B/C.
+// The search loop's staging and product FMAs are the same code.
 #include "common.hpp"
 
 using namespace psx;
@@ -33,11 +40,25 @@ struct UmpaPtrs {
     const float *R[PSX_MAX_LCS];
 };
 
+// The dark-field kernel's own arguments, last in the argument block (empty without: k_umpa<TW, S, false> is then the kernel it
+// was): the reference frames' means, H = (2w+1)^2 sum_k mu_k^2 and the fifth map.
+template <bool DF>
+struct UmpaDf {};
+template <>
+struct UmpaDf<true> {
+    double mu[PSX_MAX_LCS];
+    double H;
+    float *vis;
+};
+
 constexpr int UMPA_TH = 16, UMPA_NT = 256, UMPA_NU = 2;
 // The tile is UMPA_TH x TW, TW = 32 up to w = 4 and 16 beyond, so that the region's (16+2w)(TW/2+w) units never exceed
 // UMPA_NU = 2 per thread (480 at w = 4, 512 at w = 8) and the accumulators, the previous cost row and the running minimum stay
 // inside the register file at every (w, s).  A thread has TH*TW/256 output pixels: rows ty, ty + 256/TW, column tx.
 inline int umpa_tw(int w) { return w <= 4 ? 32 : 16; }
+// The dark-field kernel takes the narrow tile at s = 8 for every w: its TW = 32, s = 8 instantiation (256 VGPRs + 56 AGPRs)
+// spilled 12 VGPRs, with a shorter chunk 20, and is not compiled; <16, 8> has 235 and none.
+inline int umpa_df_tw(int w, int s) { return s == 8 ? 16 : umpa_tw(w); }
 
 // candidates per chunk / chunks per row for the search half-width s: NB*NCH >= 2s+1 with at most one surplus candidate
 __host__ __device__ constexpr int umpa_nb(int s) { return s <= 3 ? 2 * s + 1 : s == 4 || s == 7 ? 5 : s == 6 ? 7 : 6; }
@@ -49,12 +70,13 @@ struct UmpaLds {   // byte offsets into the dynamic LDS
 
 // Cb | 16 B | R buffer 0 | 16 B | R buffer 1 | P | H, the prologue's sum R^2 map overlaying everything behind Cb.  The 16 bytes
 // before each R buffer take the one read at column -1 that a surplus candidate (b = s+1, dropped) makes in region row 0.
-inline UmpaLds umpa_lds(int w, int s) {
-    const int UMPA_TW = umpa_tw(w);
+// Dark field: Gb follows Cb at once (cb then spans both), at most 2 * 11 KB; the largest total is 46304 bytes at (4, 7).
+inline UmpaLds umpa_lds(int w, int s, bool df = false) {
+    const int UMPA_TW = df ? umpa_df_tw(w, s) : umpa_tw(w);
     const int Hr = UMPA_TH + 2 * w, Wr = UMPA_TW + 2 * w, Wrr = Wr + 2 * s;
     UmpaLds l;
     l.cb = 0;
-    const int cb_bytes = (UMPA_TH + 2 * s) * (UMPA_TW + 2 * s) * 8;
+    const int cb_bytes = (UMPA_TH + 2 * s) * (UMPA_TW + 2 * s) * 8 * (df ? 2 : 1);
     l.tmp = cb_bytes;
     l.rbuf0 = cb_bytes + 16;
     const int rb = (Hr * Wrr * 4 + 15) & ~15;
@@ -95,14 +117,32 @@ __device__ __forceinline__ void umpa_box(const double (&v0)[NU], const double (&
     }
 }
 
-template <int UMPA_TW, int S>
+// The dark-field candidate: the 2 x 2 normal equations of S ~ alpha*R(q-u) + beta*mu, every operation rounded on its own (the
+// contract fixes the sequence, and the tests compare bit for bit).  false: the candidate is skipped.
+__device__ __forceinline__ bool umpa_df_solve(double E, double B, double C, double F, double G, double H, double &Lc, double &al,
+                                              double &Tc) {
+#pragma clang fp contract(off)
+    const double pp = C * H, qq = G * G, det = pp - qq;
+    if (!(det > 1e-12 * pp)) return false;
+    const double bh = B * H, fg = F * G, cf = C * F, gb = G * B;
+    al = (bh - fg) / det;
+    const double be = (cf - gb) / det;
+    const double ab = al * B, bf = be * F;
+    Lc = E - (ab + bf);
+    Tc = al + be;
+    return true;
+}
+
+template <int UMPA_TW, int S, bool DF = false>
 __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int m, int w, UmpaLds L, float *__restrict__ trans,
-                                                  float *__restrict__ dx, float *__restrict__ dy, float *__restrict__ resid) {
+                                                  float *__restrict__ dx, float *__restrict__ dy, float *__restrict__ resid,
+                                                  UmpaDf<DF> mu) {
     constexpr int NU = UMPA_NU, UMPA_PX = UMPA_TH * UMPA_TW / UMPA_NT, RS = UMPA_NT / UMPA_TW;
     constexpr int NB = umpa_nb(S), NCH = umpa_nch(S), ROW = NB * NCH;
     constexpr int W2 = UMPA_TW + 2 * S, H2 = UMPA_TH + 2 * S;        // the tile grown by s: where C is needed
     extern __shared__ __attribute__((aligned(16))) unsigned char umpa_smem[];
     double *const Cb = reinterpret_cast<double *>(umpa_smem + L.cb);
+    double *const Gb = Cb + H2 * W2;                                 // dark field only
     float *const Rb0 = reinterpret_cast<float *>(umpa_smem + L.rbuf0);
     float *const Rb1 = reinterpret_cast<float *>(umpa_smem + L.rbuf1);
     double *const P = reinterpret_cast<double *>(umpa_smem + L.pmap);
@@ -116,29 +156,38 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
     const double NaN = __builtin_nan("");
 
     // ---- prologue 1: sum_k R_k^2 on (Hr+2s) x Wrr (lane = column, wave = rows wv, wv+4, ...) -> tmp -> box -> Cb ----------
+    // (dark field: sum_k mu_k R_k from the same loads, through the same box -> Gb)
     {
         constexpr int RMAX = (UMPA_TH + 2 * PSX_MAX_UMPA_WINDOW + 2 * S + 3) / 4;
         const int Hc = Hr + 2 * S;
         const int gj = j0 - w - S + lane;
         const bool cok = lane < Wrr && gj >= 0 && gj < m;
-        double acc[RMAX];
+        double acc[RMAX], accg[DF ? RMAX : 1];
 #pragma unroll
         for (int t = 0; t < RMAX; ++t) acc[t] = 0.0;
+        if constexpr (DF) {
+#pragma unroll
+            for (int t = 0; t < RMAX; ++t) accg[t] = 0.0;
+        }
         for (int k = 0; k < K; ++k) {
             const float *Rk = p.R[k];
+            double muk = 0.0;
+            if constexpr (DF) muk = mu.mu[k];
 #pragma unroll
             for (int t = 0; t < RMAX; ++t) {
                 const int row = wv + 4 * t, gi = i0 - w - S + row;
                 if (row < Hc && cok && gi >= 0 && gi < n) {
                     const double r = Rk[gi * m + gj];
                     acc[t] = fma(r, r, acc[t]);
+                    if constexpr (DF) accg[t] = fma(muk, r, accg[t]);
                 }
             }
         }
+        auto box = [&](const double *src, double *dst) {
 #pragma unroll
         for (int t = 0; t < RMAX; ++t) {
             const int row = wv + 4 * t;
-            if (row < Hc && lane < Wrr) tmp[row * Wrr + lane] = acc[t];
+            if (row < Hc && lane < Wrr) tmp[row * Wrr + lane] = src[t];
         }
         __syncthreads();
         // row sums: Hc x W2, kept in registers until every thread has read, then written over the map
@@ -166,9 +215,12 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
             const double *q = tmp + e;                               // row e / W2 is the window's first row
             double a = q[0];
             for (int d = 1; d <= 2 * w; ++d) a += q[d * W2];
-            Cb[e] = a;                                               // Cb[y][x]: pixel (i0 - s + y, j0 - s + x)
+            dst[e] = a;                                              // Cb[y][x]: pixel (i0 - s + y, j0 - s + x)
         }
         __syncthreads();
+        };
+        box(acc, Cb);
+        if constexpr (DF) box(accg, Gb);
     }
 
     // ---- the thread's units: region pixels (ri, rj) and (ri, rj+1), rj even --------------------------------------------
@@ -190,21 +242,28 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
     }
 
     // ---- prologue 2: E = box[sum_k S_k^2] --------------------------------------------------------------------------------
-    double E[UMPA_PX];
+    double E[UMPA_PX], F[UMPA_PX];                                   // F = box[sum_k mu_k S_k]: dark field only
     {
-        double e0[NU], e1[NU];
+        double e0[NU], e1[NU], f0[NU], f1[NU];
 #pragma unroll
-        for (int u = 0; u < NU; ++u) e0[u] = e1[u] = 0.0;
+        for (int u = 0; u < NU; ++u) e0[u] = e1[u] = f0[u] = f1[u] = 0.0;
         for (int k = 0; k < K; ++k) {
             const float *Sk = p.S[k];
+            double muk = 0.0;
+            if constexpr (DF) muk = mu.mu[k];
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
                 const double a = soff0[u] >= 0 ? Sk[soff0[u]] : 0.f, b = soff1[u] >= 0 ? Sk[soff1[u]] : 0.f;
                 e0[u] = fma(a, a, e0[u]);
                 e1[u] = fma(b, b, e1[u]);
+                if constexpr (DF) {
+                    f0[u] = fma(muk, a, f0[u]);
+                    f1[u] = fma(muk, b, f1[u]);
+                }
             }
         }
         umpa_box<UMPA_TW>(e0, e1, uok, upos, P, H, w, Hr, Wr, tx, ty, E);
+        if constexpr (DF) umpa_box<UMPA_TW>(f0, f1, uok, upos, P, H, w, Hr, Wr, tx, ty, F);
     }
 
     // ---- the search ----------------------------------------------------------------------------------------------------------
@@ -213,13 +272,13 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
     const int sgj = j0 - w - S + lane;
     const bool scok = lane < Wrr && sgj >= 0 && sgj < m;
 
-    double bestL[UMPA_PX], bestT[UMPA_PX], Lam[UMPA_PX], Lap[UMPA_PX], Lbm[UMPA_PX], Lbp[UMPA_PX], last[UMPA_PX];
+    double bestL[UMPA_PX], bestT[UMPA_PX], bestA[UMPA_PX], Lam[UMPA_PX], Lap[UMPA_PX], Lbm[UMPA_PX], Lbp[UMPA_PX], last[UMPA_PX];
     double prev[UMPA_PX][ROW];
     int ba[UMPA_PX], bb[UMPA_PX];
 #pragma unroll
     for (int t = 0; t < UMPA_PX; ++t) {
         bestL[t] = __builtin_inf();
-        bestT[t] = 0.0;
+        bestT[t] = bestA[t] = 0.0;                                   // bestA: alpha at the minimum, dark field only
         Lam[t] = Lap[t] = Lbm[t] = Lbp[t] = last[t] = NaN;
         ba[t] = bb[t] = -100;                                        // no minimum yet
 #pragma unroll
@@ -302,8 +361,16 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
 #pragma unroll
                 for (int t = 0; t < UMPA_PX; ++t) {
                     const double Cv = Cb[(ty + RS * t - a + S) * W2 + (tx - b + S)];
-                    double Lc = NaN, Tc = 0.0;
-                    if (Cv != 0.0) {
+                    double Lc = NaN, Tc = 0.0, Ac = 0.0;
+                    if constexpr (DF) {
+                        const double Gv = Gb[(ty + RS * t - a + S) * W2 + (tx - b + S)];
+                        double Ls, As, Ts;
+                        if (umpa_df_solve(E[t], B[t], Cv, F[t], Gv, mu.H, Ls, As, Ts)) {
+                            Lc = Ls;
+                            Ac = As;
+                            Tc = Ts;
+                        }
+                    } else if (Cv != 0.0) {
                         Lc = E[t] - B[t] * B[t] / Cv;
                         Tc = B[t] / Cv;
                     }
@@ -312,6 +379,7 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
                     if (Lc < bestL[t]) {                             // false for NaN: strict, first in scan order
                         bestL[t] = Lc;
                         bestT[t] = Tc;
+                        if constexpr (DF) bestA[t] = Ac;
                         ba[t] = a;
                         bb[t] = b;
                         Lam[t] = prev[t][ch * NB + c];
@@ -331,7 +399,7 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
         const int i = i0 + ty + RS * t, j = j0 + tx;
         if (i >= n || j >= m) continue;
         const int band = w + S;
-        float ot = 1.f, ox = 0.f, oy = 0.f, orr = 0.f;
+        float ot = 1.f, ox = 0.f, oy = 0.f, ov = 1.f, orr = 0.f;
         const bool interior = i >= band && i < n - band && j >= band && j < m - band;
         if (interior && ba[t] != -100 && bestT[t] > 0.0) {
             double da = 0.0, db = 0.0;
@@ -347,11 +415,13 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
             ox = (float)((double)ba[t] + da);
             oy = (float)((double)bb[t] + db);
             orr = (float)(fmax(bestL[t], 0.0) / E[t]);
+            if constexpr (DF) ov = (float)(bestA[t] / bestT[t]);
         }
         const int64_t o = (int64_t)i * m + j;
         trans[o] = ot;
         dx[o] = ox;
         dy[o] = oy;
+        if constexpr (DF) mu.vis[o] = ov;
         resid[o] = orr;
     }
 }
@@ -361,7 +431,7 @@ void umpa_launch(int s, dim3 grid, const UmpaLds &L, hipStream_t st, const UmpaP
                  float *dx, float *dy, float *res) {
 #define PSX_UMPA_CASE(SV)                                                                                                   \
     case SV:                                                                                                                \
-        PSX_TIMED("k_umpa", st, k_umpa<UMPA_TW, SV><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res));      \
+        PSX_TIMED("k_umpa", st, k_umpa<UMPA_TW, SV><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res, {})); \
         break;
     switch (s) {
         PSX_UMPA_CASE(1)
@@ -376,11 +446,32 @@ void umpa_launch(int s, dim3 grid, const UmpaLds &L, hipStream_t st, const UmpaP
 #undef PSX_UMPA_CASE
 }
 
-}  // namespace
+template <int UMPA_TW>
+int umpa_df_launch(int s, dim3 grid, const UmpaLds &L, hipStream_t st, const UmpaPtrs &p, const UmpaDf<true> &mu, int K, int n,
+                   int m, int w, float *t, float *dx, float *dy, float *res) {
+#define PSX_UMPA_CASE(SV)                                                                                                         \
+    case SV:                                                                                                                      \
+        PSX_TIMED("k_umpa_df", st,                                                                                                \
+                  k_umpa<UMPA_TW, SV, true><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res, mu));                 \
+        break;
+    if constexpr (UMPA_TW == 16) {                                   // s = 8 exists at the narrow tile only (umpa_df_tw)
+        if (s == 8) PSX_TIMED("k_umpa_df", st, k_umpa<16, 8, true><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res, mu));
+    }
+    switch (s) {
+        PSX_UMPA_CASE(1)
+        PSX_UMPA_CASE(2)
+        PSX_UMPA_CASE(3)
+        PSX_UMPA_CASE(4)
+        PSX_UMPA_CASE(5)
+        PSX_UMPA_CASE(6)
+        PSX_UMPA_CASE(7)
+    }
+#undef PSX_UMPA_CASE
+    return 0;
+}
 
-extern "C" int psx_umpa_f32(const float *const *S, const float *const *R, int K, int n, int m, int window, int search,
-                            float *transmission, float *dx, float *dy, float *residual, void *stream) {
-    const char *fn = "psx_umpa_f32";
+// The argument checks psx_umpa_f32 and psx_umpa_df_f32 share, and the pointer block.
+int umpa_args(const char *fn, const float *const *S, const float *const *R, int K, int n, int m, int window, int search, UmpaPtrs &p) {
     PSX_REQUIRE(K >= 1 && K <= PSX_MAX_LCS, "%s: K=%d positions outside [1,%d]", fn, K, PSX_MAX_LCS);
     PSX_REQUIRE(window >= 1 && window <= PSX_MAX_UMPA_WINDOW, "%s: window=%d outside [1,%d]", fn, window, PSX_MAX_UMPA_WINDOW);
     PSX_REQUIRE(search >= 1 && search <= PSX_MAX_UMPA_SEARCH, "%s: search=%d outside [1,%d]", fn, search, PSX_MAX_UMPA_SEARCH);
@@ -388,8 +479,6 @@ extern "C" int psx_umpa_f32(const float *const *S, const float *const *R, int K,
     PSX_REQUIRE(n >= least && m >= least, "%s: images %dx%d smaller than %dx%d = 2(window+search)+1", fn, n, m, least, least);
     PSX_REQUIRE((int64_t)n * m <= (int64_t)1 << 30, "%s: images %dx%d too large", fn, n, m);
     PSX_REQUIRE(S != nullptr && R != nullptr, "%s: null pointer array", fn);
-    PSX_REQUIRE(transmission && dx && dy && residual, "%s: null output map", fn);
-    UmpaPtrs p;
     for (int k = 0; k < PSX_MAX_LCS; ++k) {
         p.S[k] = nullptr;
         p.R[k] = nullptr;
@@ -399,6 +488,17 @@ extern "C" int psx_umpa_f32(const float *const *S, const float *const *R, int K,
         p.S[k] = S[k];
         p.R[k] = R[k];
     }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int psx_umpa_f32(const float *const *S, const float *const *R, int K, int n, int m, int window, int search,
+                            float *transmission, float *dx, float *dy, float *residual, void *stream) {
+    const char *fn = "psx_umpa_f32";
+    UmpaPtrs p;
+    if (int rc = umpa_args(fn, S, R, K, n, m, window, search, p)) return rc;
+    PSX_REQUIRE(transmission && dx && dy && residual, "%s: null output map", fn);
     const UmpaLds L = umpa_lds(window, search);
     const dim3 grid((unsigned)cdiv(m, umpa_tw(window)), (unsigned)cdiv(n, UMPA_TH));
     hipStream_t st = (hipStream_t)stream;
@@ -407,4 +507,34 @@ extern "C" int psx_umpa_f32(const float *const *S, const float *const *R, int K,
     else
         umpa_launch<16>(search, grid, L, st, p, K, n, m, window, transmission, dx, dy, residual);
     return launch_check("k_umpa");
+}
+
+extern "C" int psx_umpa_df_f32(const float *const *S, const float *const *R, const double *mean, int K, int n, int m, int window,
+                               int search, float *transmission, float *dx, float *dy, float *visibility, float *residual,
+                               void *stream) {
+    const char *fn = "psx_umpa_df_f32";
+    UmpaPtrs p;
+    if (int rc = umpa_args(fn, S, R, K, n, m, window, search, p)) return rc;
+    PSX_REQUIRE(mean != nullptr, "%s: null mean array", fn);
+    PSX_REQUIRE(transmission && dx && dy && visibility && residual, "%s: null output map", fn);
+    UmpaDf<true> mu;
+    mu.vis = visibility;
+    double sq = 0.0;
+    for (int k = 0; k < PSX_MAX_LCS; ++k) mu.mu[k] = 0.0;
+    for (int k = 0; k < K; ++k) {
+        PSX_REQUIRE(std::isfinite(mean[k]), "%s: mean[%d] is not finite", fn, k);
+        mu.mu[k] = mean[k];
+        sq += mean[k] * mean[k];
+    }
+    const double side = 2 * window + 1;
+    mu.H = side * side * sq;
+    const UmpaLds L = umpa_lds(window, search, true);
+    const int tw = umpa_df_tw(window, search);
+    const dim3 grid((unsigned)cdiv(m, tw), (unsigned)cdiv(n, UMPA_TH));
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = tw == 32
+                       ? umpa_df_launch<32>(search, grid, L, st, p, mu, K, n, m, window, transmission, dx, dy, residual)
+                       : umpa_df_launch<16>(search, grid, L, st, p, mu, K, n, m, window, transmission, dx, dy, residual);
+    if (rc) return rc;
+    return launch_check("k_umpa_df");
 }

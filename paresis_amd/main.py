@@ -3,7 +3,7 @@
 
     python -m paresis_amd.main [--experiment NAME] [--type RayT|Fresnel] [--oversampling N] [--points N]
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
-                               [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa --window W --search M]]
+                               [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa|umpa-df --window W --search M]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
@@ -11,7 +11,8 @@ has its own seed.  --retrieve (needs 3 positions or more) runs the speckle-track
 after the gather (paresis_amd/retrieval.py) and writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under the bin's
 directory.  --dark-field (needs 4 positions or more) retrieves with LCS-DF and adds df_ and scattering_<expID><fmt>.
 --method umpa (1 position or more) retrieves with UMPA, for displacements of up to --search pixels, and adds
-residual_<expID><fmt>; it takes neither --dark-field nor --max-shift.
+residual_<expID><fmt>; it takes neither --dark-field nor --max-shift.  --method umpa-df (the same rules) also fits UMPA's
+dark-field term and adds visibility_<expID><fmt>.
 """
 import argparse
 import datetime
@@ -29,7 +30,8 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     (retrieval.retrieve with the experiment's parameters, max_shift its clamp); with save, the maps go to
     <bin dir>/retrieval/.  exp_dict['retrievalParams'] then holds the parameters it used.  dark_field (with retrieve, 4
     positions or more): LCS-DF, the maps gain df and scattering (retrieval.retrieve(..., dark_field=True)).  method='umpa'
-    (with retrieve, 1 position or more; window, search as retrieval.umpa): UMPA instead of LCS, the maps gain residual."""
+    (with retrieve, 1 position or more; window, search as retrieval.umpa): UMPA instead of LCS, the maps gain residual;
+    method='umpa-df' (the same rules): UMPA with its dark-field term, the maps gain visibility and residual."""
     if retrieve and method != "lcs":
         from .retrieval import check_method
         check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
@@ -184,11 +186,12 @@ def main(argv=None):
     ap.add_argument("--max-shift", type=float, default=None, help="--retrieve: clamp of the displacements, in pixels")
     ap.add_argument("--dark-field", action="store_true",
                     help="--retrieve with LCS-DF (4 positions or more): also retrieval/{df,scattering}_<expID><fmt>")
-    ap.add_argument("--method", default="lcs", choices=["lcs", "umpa"],
-                    help="--retrieve with LCS (3 positions or more, |D| < 1 px) or UMPA (1 position or more, |D| up to --search "
-                         "px; also retrieval/residual_<expID><fmt>)")
-    ap.add_argument("--window", type=int, default=2, help="--method umpa: half-width w of the (2w+1)^2 window, 1..8")
-    ap.add_argument("--search", type=int, default=3, help="--method umpa: largest integer shift searched, 1..8")
+    ap.add_argument("--method", default="lcs", choices=["lcs", "umpa", "umpa-df"],
+                    help="--retrieve with LCS (3 positions or more, |D| < 1 px), UMPA (1 position or more, |D| up to --search "
+                         "px; also retrieval/residual_<expID><fmt>) or UMPA with its dark-field term (umpa-df: also "
+                         "retrieval/visibility_<expID><fmt>)")
+    ap.add_argument("--window", type=int, default=2, help="--method umpa, umpa-df: half-width w of the (2w+1)^2 window, 1..8")
+    ap.add_argument("--search", type=int, default=3, help="--method umpa, umpa-df: largest integer shift searched, 1..8")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -196,7 +199,7 @@ def main(argv=None):
     if a.xml:
         exp_dict['xmlDir'] = a.xml
     os.makedirs(exp_dict['filepath'], exist_ok=True)
-    if a.method == "umpa":
+    if a.method in ("umpa", "umpa-df"):
         if not a.retrieve:
             ap.error("--method is an option of --retrieve")
         if a.dark_field or a.max_shift is not None:

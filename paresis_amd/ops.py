@@ -5,6 +5,7 @@ hand-written HIP kernels behind the C ABI.  Every function checks devices/dtypes
 launched, and raises PsxError on any failure -- there is no CPU fallback.
 """
 import ctypes
+import math
 from ctypes import c_double, c_float, c_int, c_void_p
 
 import torch
@@ -1055,6 +1056,48 @@ def umpa(sample, reference, window=2, search=3, out=None):
         check(lib().psx_umpa_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K,
                                  shape[0], shape[1], w, sr, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _stream()),
               "psx_umpa_f32")
+    return out
+
+
+def umpa_df(sample, reference, window=2, search=3, mean=None, out=None):
+    """UMPA with its dark-field term (psx_umpa_df_f32): ops.umpa under the model S_k(q) ~ T*[mu_k + V*(R_k(q - u) - mu_k)], mu_k
+    the mean of reference frame k -> (transmission, dx, dy, visibility, residual), n x m float32.  V is the ratio of the
+    speckle visibility behind the sample to that of the reference: 1 where nothing scatters, below 1 where the sample
+    blurs the speckle.  It is not clamped (noise and model error give values above 1 or below 0) and it is NOT converted
+    to a scattering angle: that depends on the speckle's spectrum.  Border-band and fallback pixels are exactly
+    (1, 0, 0, 1, 0).  mean: K finite floats, the mu_k; None computes each reference frame's mean in float64 on the device
+    and copies the K values to the host, which SYNCHRONISES the stream -- pass the means to stay asynchronous.  Everything
+    else (window, search, sizes, input forms) as ops.umpa.  out: five caller-owned n x m float32 tensors to write into."""
+    S = _positions(sample, "sample", kmin=1)
+    R = _positions(reference, "reference", kmin=1)
+    for nm, v, cap in (("window", window, _lib.PSX_MAX_UMPA_WINDOW), ("search", search, _lib.PSX_MAX_UMPA_SEARCH)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
+            raise PsxError("%s must be an integer in [1, %d], got %r" % (nm, cap, v))
+    w, sr = int(window), int(search)
+    least = 2 * (w + sr) + 1
+    if S[0].shape[0] < least or S[0].shape[1] < least:
+        raise PsxError("images %dx%d smaller than %dx%d = 2*(window+search)+1" % (tuple(S[0].shape) + (least, least)))
+    if len(S) != len(R):
+        raise PsxError("sample has %d positions, reference %d" % (len(S), len(R)))
+    K = len(S)
+    if mean is not None:
+        try:
+            mean = [float(v) for v in mean]
+        except (TypeError, ValueError):
+            raise PsxError("mean must be a sequence of %d finite floats, got %r" % (K, mean))
+        if len(mean) != K:
+            raise PsxError("mean must hold one value per position (%d), got %d" % (K, len(mean)))
+        if not all(math.isfinite(v) for v in mean):
+            raise PsxError("mean must be finite, got %r" % (mean,))
+    if out is not None and len(tuple(out)) != 5:
+        raise PsxError("out must hold five tensors (transmission, dx, dy, visibility, residual)")
+    shape, dev, _, out = _lcs_args(S, R, None, out, ("transmission", "dx", "dy", "visibility", "residual"))
+    with torch.cuda.device(dev):
+        if mean is None:
+            mean = torch.stack([t.mean(dtype=torch.float64) for t in R]).tolist()      # one copy to the host: synchronises
+        check(lib().psx_umpa_df_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]),
+                                    (c_double * K)(*mean), K, shape[0], shape[1], w, sr, _ptr(out[0]), _ptr(out[1]),
+                                    _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _stream()), "psx_umpa_df_f32")
     return out
 
 

@@ -14,7 +14,9 @@ module turns them into the sample's transmission, its refraction (displacement) 
                              that minimises the float64 least-squares cost of S(q) = T*R(q - u) over a uniform
                              (2*window+1)^2 window (no Hamming taper, unlike the UMPA package) and the K >= 1 positions,
                              refined to sub-pixel by a parabola per axis: displacements of several pixels, where the
-                             first-order LCS (|D| < 1 px) fails; also 'residual', the cost at the minimum over sum S^2
+                             first-order LCS (|D| < 1 px) fails; also 'residual', the cost at the minimum over sum S^2;
+                             dark_field=True fits S(q) = T*[mu + V*(R(q - u) - mu)], mu the reference frame's mean, and
+                             adds 'visibility' V, UMPA's dark-field signal (1: no scattering)
     scattering_angle(df, ...) df -> the chain's scattering angle theta in radians
     phase_gradient(...)      displacement -> phase gradient in radians per detector pixel
     integrate(gx, gy)        Frankot-Chellappa (IEEE PAMI 10, 1988) with mirror extension -> phase (zero mean)
@@ -25,11 +27,12 @@ argument checks.  Command line, for a run already on disk (main.py's layout):
 
     python -m paresis_amd.retrieval RUN_DIR [--energy KEV --pixel-um P --distance Z --magnification M]
                                             [--max-shift S] [--format .tif] [--dark-field]
-                                            [--method {lcs,umpa} --window W --search M]
+                                            [--method {lcs,umpa,umpa-df} --window W --search M]
 
 writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory; without the four physical parameters
 only transmission, dx and dy.  --dark-field (4 positions or more) adds df, and scattering with the physical parameters.
---method umpa (1 position or more; no --dark-field, no --max-shift) tracks with UMPA and adds residual.
+--method umpa (1 position or more; no --dark-field, no --max-shift) tracks with UMPA and adds residual; --method umpa-df
+(the same rules) also fits UMPA's dark-field term and adds visibility.
 """
 import argparse
 import os
@@ -56,28 +59,39 @@ def lcs(sample, reference, max_shift=None, dark_field=False):
     return {'transmission': t, 'dx': dx, 'dy': dy}
 
 
-def umpa(sample, reference, window=2, search=3):
+def umpa(sample, reference, window=2, search=3, dark_field=False, mean=None):
     """K >= 1 sample / reference images of one bin (the forms lcs takes) -> {'transmission', 'dx', 'dy', 'residual'}, n x m
     float32 on the same device (ops.umpa): the shift of a uniform (2*window+1)^2 window within |a|, |b| <= search pixels,
-    sub-pixel by a parabola per axis.  Pixels closer than window+search to a border are (1, 0, 0, 0)."""
+    sub-pixel by a parabola per axis.  Pixels closer than window+search to a border are (1, 0, 0, 0).
+    dark_field: the three-modality model S = T*[mu + V*(R(q - u) - mu)] (ops.umpa_df), and 'visibility' V in the dict: the
+    speckle visibility behind the sample over the reference's, 1 in the border band, not clamped.  mean: the K reference
+    means mu_k (None: computed on the device, which synchronises).  V is not converted to a scattering angle: that
+    conversion depends on the speckle's spectrum."""
     from . import ops
+    if dark_field:
+        t, dx, dy, vis, res = ops.umpa_df(sample, reference, window=window, search=search, mean=mean)
+        return {'transmission': t, 'dx': dx, 'dy': dy, 'visibility': vis, 'residual': res}
+    if mean is not None:
+        raise ValueError("mean is an option of dark_field=True")
     t, dx, dy, res = ops.umpa(sample, reference, window=window, search=search)
     return {'transmission': t, 'dx': dx, 'dy': dy, 'residual': res}
 
 
-METHODS = ("lcs", "umpa")
+METHODS = ("lcs", "umpa", "umpa-df")
+UMPA_METHODS = ("umpa", "umpa-df")
 
 
 def check_method(method, npos, max_shift=None, dark_field=False):
-    """The argument rules of retrieve(): ValueError for an unknown method, too few positions (lcs: 3, LCS-DF: 4, umpa: 1), or
-    umpa with dark_field or max_shift.  Needs no GPU."""
+    """The argument rules of retrieve(): ValueError for an unknown method, too few positions (lcs: 3, LCS-DF: 4, umpa and
+    umpa-df: 1), or umpa / umpa-df with dark_field or max_shift.  Needs no GPU."""
     if method not in METHODS:
         raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
-    if method == "umpa":
+    if method in UMPA_METHODS:
         if dark_field:
-            raise ValueError("method='umpa' has no dark-field term: dark_field is an option of method='lcs'")
+            raise ValueError("method='umpa' has no dark-field term: dark_field is an option of method='lcs'" if method == "umpa"
+                             else "method='umpa-df' always fits its dark-field term: dark_field is an option of method='lcs'")
         if max_shift is not None:
-            raise ValueError("method='umpa' is bounded by its search range: max_shift is an option of method='lcs'")
+            raise ValueError("method=%r is bounded by its search range: max_shift is an option of method='lcs'" % method)
         if npos < 1:
             raise ValueError("phase retrieval needs at least 1 position, got %d" % npos)
         return
@@ -171,7 +185,8 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
     more): every bin also gets 'df' (detector px^2) and, with params, 'scattering' (theta, radians; scattering_angle);
     'phi' then integrates the four-unknown system's dx, dy.  method='umpa' (1 position or more; window, search: umpa's):
     every bin's maps come from umpa() instead, with 'residual'; 'phi' integrates its dx, dy the same way.  It takes neither
-    dark_field nor max_shift (ValueError)."""
+    dark_field nor max_shift (ValueError).  method='umpa-df': umpa(dark_field=True), the same rules; every bin gains
+    'visibility' as well (no scattering angle is derived from it)."""
     positions = sorted(results)
     check_method(method, len(positions), max_shift, dark_field)
     import torch
@@ -184,8 +199,8 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
         raise ValueError("energies must hold one value per retrieved bin (%d), got %d" % (len(bins), len(energies)))
     out = {}
     for i, b in enumerate(bins):
-        if method == "umpa":
-            r = umpa([s[b] for s in S], [s[b] for s in R], window=window, search=search)
+        if method in UMPA_METHODS:
+            r = umpa([s[b] for s in S], [s[b] for s in R], window=window, search=search, dark_field=method == "umpa-df")
         else:
             r = lcs([s[b] for s in S], [s[b] for s in R], max_shift=max_shift, dark_field=dark_field)
         if params is not None:
@@ -200,12 +215,12 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
 
 def save_retrieval(r, directory, exp_id, fmt):
     """Write one bin's maps as directory/retrieval/<name>_<exp_id><fmt> (name: transmission, dx, dy[, phi][, df][, scattering]
-    [, residual])."""
+    [, visibility][, residual])."""
     from .InputOutput.pagailleIO import save_image
     d = os.path.join(directory, "retrieval")
     os.makedirs(d, exist_ok=True)
     paths = []
-    for name in ("transmission", "dx", "dy", "phi", "df", "scattering", "residual"):
+    for name in ("transmission", "dx", "dy", "phi", "df", "scattering", "visibility", "residual"):
         if name in r:
             paths.append(os.path.join(d, "%s_%s%s" % (name, exp_id, fmt)))
             save_image(r[name].detach().cpu().numpy(), paths[-1])
@@ -260,12 +275,12 @@ def discover(run_dir, min_positions=3):
 def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None, dark_field=False, method='lcs', window=2, search=3):
     """discover() + lcs (+ integrate when params are given) + save_retrieval for every bin directory; returns the paths.
     dark_field: LCS-DF (4 positions or more), df (+ scattering with params) written too.  method='umpa' (window, search):
-    UMPA instead of LCS, 1 position or more, residual written too."""
+    UMPA instead of LCS, 1 position or more, residual written too; method='umpa-df': visibility as well."""
     import torch
     from .InputOutput.pagailleIO import openImage
     written = []
     dev = torch.device("cuda", torch.cuda.current_device())
-    for d, exp_id, in_fmt, pairs in discover(run_dir, min_positions=1 if method == "umpa" else 3):
+    for d, exp_id, in_fmt, pairs in discover(run_dir, min_positions=1 if method in UMPA_METHODS else 3):
         S = torch.from_numpy(np.stack([np.asarray(openImage(s), dtype=np.float32) for _, s, _ in pairs])).to(dev)
         R = torch.from_numpy(np.stack([np.asarray(openImage(r), dtype=np.float32) for _, _, r in pairs])).to(dev)
         res = retrieve({p: (S[i:i + 1], R[i:i + 1]) for i, (p, _, _) in enumerate(pairs)}, params, max_shift=max_shift,
@@ -288,11 +303,12 @@ def main(argv=None):
                     help="LCS-DF (4 positions or more): also df (detector px^2) and, with the physical parameters, scattering "
                          "(rad)")
     ap.add_argument("--method", choices=METHODS, default="lcs",
-                    help="lcs (3 positions or more, |D| < 1 px) or umpa (1 position or more, |D| up to --search px)")
-    ap.add_argument("--window", type=int, default=2, help="--method umpa: half-width w of the (2w+1)^2 window, 1..8")
-    ap.add_argument("--search", type=int, default=3, help="--method umpa: largest integer shift searched, 1..8")
+                    help="lcs (3 positions or more, |D| < 1 px), umpa (1 position or more, |D| up to --search px) or umpa-df "
+                         "(umpa with its dark-field term: also visibility)")
+    ap.add_argument("--window", type=int, default=2, help="--method umpa, umpa-df: half-width w of the (2w+1)^2 window, 1..8")
+    ap.add_argument("--search", type=int, default=3, help="--method umpa, umpa-df: largest integer shift searched, 1..8")
     a = ap.parse_args(argv)
-    if a.method == "umpa":
+    if a.method in UMPA_METHODS:
         if a.dark_field or a.max_shift is not None:
             ap.error("--dark-field and --max-shift are options of --method lcs")
         if not 1 <= a.window <= 8 or not 1 <= a.search <= 8:

@@ -11,7 +11,9 @@ numpy oracle's time at the same sizes -- HOST time, one run, for scale only.
 k_umpa (UMPA, window w, search s) reads 2K images and writes 4: the same 4*n*m*(2K + 4) bytes from HBM, but it is bound by its
 float64 product sums: n*m*(2s+1)^2*K useful FMAs, set against the v_fma_f64 rate that tools/valu_bench measures (FMA64_CYCLES
 per wave64 instruction and SIMD).  Its cases end with time(w = 4)/time(w = 1): the separable window sums keep it below 3,
-direct ones would give about 9.
+direct ones would give about 9.  k_umpa_df (its dark-field variant, ops.umpa_df with the means given, so that nothing
+synchronises) writes 5 maps and is timed in the same process, alternating with k_umpa launch by launch on the same inputs: two
+box passes more in the prologue against (2s+1)^2 in the search, and a 2 x 2 solve per candidate.
 """
 import argparse
 import ctypes
@@ -97,21 +99,26 @@ def umpa_case(n, m, K, w, s, reps):
     S = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
     R = 1e4 * (1 + 0.3 * torch.rand((K, n, m), device="cuda", generator=g))
     outs = tuple(torch.empty((n, m), device="cuda") for _ in range(4))
+    outs_df = tuple(torch.empty((n, m), device="cuda") for _ in range(5))
+    mean = R.mean(dim=(1, 2), dtype=torch.float64).tolist()
     for _ in range(3):
         ops.umpa(S, R, window=w, search=s, out=outs)
+        ops.umpa_df(S, R, window=w, search=s, mean=mean, out=outs_df)
     torch.cuda.synchronize()
     lib().psx_profile_enable(1)
     for _ in range(reps):
         ops.umpa(S, R, window=w, search=s, out=outs)
+        ops.umpa_df(S, R, window=w, search=s, mean=mean, out=outs_df)
     torch.cuda.synchronize()
-    c, ms = summary()["k_umpa"]
+    prof = summary()
     lib().psx_profile_enable(0)
-    t = ms / c * 1e-3
+    t, tdf = (prof[k][1] / prof[k][0] * 1e-3 for k in ("k_umpa", "k_umpa_df"))
     price = 4.0 * n * m * (2 * K + 4)
     fma = float(n) * m * (2 * s + 1) ** 2 * K
     print("%dx%d K=%d w=%d s=%d  k_umpa %.1f us  price %.1f MB (%.1f us at 8 TB/s)  %.2f G FMA64 (%.1f us at %.1f T FMA/s) = %.2f of "
           "the float64 FMA rate" % (n, m, K, w, s, t * 1e6, price / 1e6, price / PEAK * 1e6, fma / 1e9, fma / FMA64_PEAK * 1e6,
                                     FMA64_PEAK / 1e12, fma / t / FMA64_PEAK))
+    print("%dx%d K=%d w=%d s=%d  k_umpa_df %.1f us = %.3f x k_umpa" % (n, m, K, w, s, tdf * 1e6, tdf / t))
     return t
 
 

@@ -107,6 +107,24 @@ struct Mats {
 // Validates (T, cphase, catt, nmat) and packs them.  Null coefficient arrays mean zeros.
 int pack_mats(Mats &m, const float *const *T, const double *cphase, const double *catt, int nmat);
 
+// ---- the K sample / reference image pairs of a speckle tracker (retrieve.hip, umpa.hip), passed to kernels by value ----
+struct SpecklePtrs {
+    const float *S[PSX_MAX_LCS];
+    const float *R[PSX_MAX_LCS];
+};
+
+// Validates (S, R, K) for the entry point `fn`, whose smallest K is Kmin, and packs them; the unused slots are null.
+inline int pack_speckle(SpecklePtrs &p, const char *fn, int Kmin, const float *const *S, const float *const *R, int K) {
+    PSX_REQUIRE(K >= Kmin && K <= PSX_MAX_LCS, "%s: K=%d positions outside [%d,%d]", fn, K, Kmin, PSX_MAX_LCS);
+    PSX_REQUIRE(S != nullptr && R != nullptr, "%s: null pointer array", fn);
+    for (int k = 0; k < PSX_MAX_LCS; ++k) {
+        PSX_REQUIRE(k >= K || (S[k] != nullptr && R[k] != nullptr), "%s: position %d has a null image", fn, k);
+        p.S[k] = k < K ? S[k] : nullptr;
+        p.R[k] = k < K ? R[k] : nullptr;
+    }
+    return 0;
+}
+
 // ---- device math ---------------------------------------------------------------------------------------------
 #define PSX_TWO_PI 6.283185307179586476925286766559
 #define PSX_INV_TWO_PI 0.15915494309189533576888376337251

@@ -25,15 +25,10 @@ using namespace psx;
 
 namespace {
 
-struct LcsPtrs {
-    const float *S[PSX_MAX_LCS];
-    const float *R[PSX_MAX_LCS];
-};
-
 constexpr int LCS_BX = 64, LCS_BY = 4;
 
 // one thread per pixel (i, j) of the n x m images; no barrier, so out-of-range threads leave at once
-__global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs(LcsPtrs p, int K, int n, int m, float max_shift,
+__global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs(SpecklePtrs p, int K, int n, int m, float max_shift,
                                                          float *__restrict__ trans, float *__restrict__ dx,
                                                          float *__restrict__ dy) {
     const int j = blockIdx.x * LCS_BX + threadIdx.x;
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs(LcsPtrs p, int K, int n
 // as the gradients, so the same six loads), formed in float64 from the float32 samples: exact for image data.  The 4x4
 // system is solved by LDL^T without pivoting; fallback x = (1, 0, 0, 0) when a pivot is <= 0, when prod d_i (= det M) <=
 // 1e-12*M00*M11*M22*M33, or when x0 <= 0.  df = -x3 is not clamped.
-__global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs_df(LcsPtrs p, int K, int n, int m, float max_shift,
+__global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs_df(SpecklePtrs p, int K, int n, int m, float max_shift,
                                                             float *__restrict__ trans, float *__restrict__ dx,
                                                             float *__restrict__ dy, float *__restrict__ df) {
     const int j = blockIdx.x * LCS_BX + threadIdx.x;
@@ -235,24 +230,14 @@ struct psx_integrate_plan {
 
 namespace {
 
-// The argument checks, pointer packing and grid shared by psx_lcs_f32 and psx_lcs_df_f32.  fn: the entry point's name in the
-// error texts; Kmin: its smallest K; outputs_ok: all its output maps are there.
+// The argument checks, pointer packing (pack_speckle) and grid shared by psx_lcs_f32 and psx_lcs_df_f32.  fn: the entry point's
+// name in the error texts; Kmin: its smallest K; outputs_ok: all its output maps are there.
 int lcs_prepare(const char *fn, int Kmin, const float *const *S, const float *const *R, int K, int n, int m, float max_shift,
-                bool outputs_ok, LcsPtrs &p, dim3 &grid) {
-    PSX_REQUIRE(K >= Kmin && K <= PSX_MAX_LCS, "%s: K=%d positions outside [%d,%d]", fn, K, Kmin, PSX_MAX_LCS);
+                bool outputs_ok, SpecklePtrs &p, dim3 &grid) {
+    if (int rc = pack_speckle(p, fn, Kmin, S, R, K)) return rc;
     PSX_REQUIRE(n >= 3 && m >= 3, "%s: images %dx%d smaller than 3x3", fn, n, m);
-    PSX_REQUIRE(S != nullptr && R != nullptr, "%s: null pointer array", fn);
     PSX_REQUIRE(outputs_ok, "%s: null output map", fn);
     PSX_REQUIRE(max_shift >= 0.0f, "%s: max_shift=%g < 0", fn, (double)max_shift);
-    for (int k = 0; k < PSX_MAX_LCS; ++k) {
-        p.S[k] = nullptr;
-        p.R[k] = nullptr;
-    }
-    for (int k = 0; k < K; ++k) {
-        PSX_REQUIRE(S[k] != nullptr && R[k] != nullptr, "%s: position %d has a null image", fn, k);
-        p.S[k] = S[k];
-        p.R[k] = R[k];
-    }
     grid = dim3((unsigned)cdiv(m, LCS_BX), (unsigned)cdiv(n, LCS_BY));
     return 0;
 }
@@ -263,7 +248,7 @@ extern "C" {
 
 int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
                 float *dx, float *dy, void *stream) {
-    LcsPtrs p;
+    SpecklePtrs p;
     dim3 grid;
     if (int rc = lcs_prepare("psx_lcs_f32", 3, S, R, K, n, m, max_shift, transmission && dx && dy, p, grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -273,7 +258,7 @@ int psx_lcs_f32(const float *const *S, const float *const *R, int K, int n, int 
 
 int psx_lcs_df_f32(const float *const *S, const float *const *R, int K, int n, int m, float max_shift, float *transmission,
                    float *dx, float *dy, float *df, void *stream) {
-    LcsPtrs p;
+    SpecklePtrs p;
     dim3 grid;
     if (int rc = lcs_prepare("psx_lcs_df_f32", 4, S, R, K, n, m, max_shift, transmission && dx && dy && df, p, grid)) return rc;
     hipStream_t st = (hipStream_t)stream;

@@ -35,11 +35,6 @@ using namespace psx;
 
 namespace {
 
-struct UmpaPtrs {
-    const float *S[PSX_MAX_LCS];
-    const float *R[PSX_MAX_LCS];
-};
-
 // The dark-field kernel's own arguments, last in the argument block (empty without: k_umpa<TW, S, false> is then the kernel it
 // was): the reference frames' means, H = (2w+1)^2 sum_k mu_k^2 and the fifth map.
 template <bool DF>
@@ -55,10 +50,9 @@ constexpr int UMPA_TH = 16, UMPA_NT = 256, UMPA_NU = 2;
 // The tile is UMPA_TH x TW, TW = 32 up to w = 4 and 16 beyond, so that the region's (16+2w)(TW/2+w) units never exceed
 // UMPA_NU = 2 per thread (480 at w = 4, 512 at w = 8) and the accumulators, the previous cost row and the running minimum stay
 // inside the register file at every (w, s).  A thread has TH*TW/256 output pixels: rows ty, ty + 256/TW, column tx.
-inline int umpa_tw(int w) { return w <= 4 ? 32 : 16; }
 // The dark-field kernel takes the narrow tile at s = 8 for every w: its TW = 32, s = 8 instantiation (256 VGPRs + 56 AGPRs)
-// spilled 12 VGPRs, with a shorter chunk 20, and is not compiled; <16, 8> has 235 and none.
-inline int umpa_df_tw(int w, int s) { return s == 8 ? 16 : umpa_tw(w); }
+// spilled 12 VGPRs, with a shorter chunk 20, and is not compiled (umpa_launch); <16, 8> has 235 and none.
+inline int umpa_tw(int w, int s, bool df) { return w > 4 || (df && s == 8) ? 16 : 32; }
 
 // candidates per chunk / chunks per row for the search half-width s: NB*NCH >= 2s+1 with at most one surplus candidate
 __host__ __device__ constexpr int umpa_nb(int s) { return s <= 3 ? 2 * s + 1 : s == 4 || s == 7 ? 5 : s == 6 ? 7 : 6; }
@@ -71,8 +65,8 @@ struct UmpaLds {   // byte offsets into the dynamic LDS
 // Cb | 16 B | R buffer 0 | 16 B | R buffer 1 | P | H, the prologue's sum R^2 map overlaying everything behind Cb.  The 16 bytes
 // before each R buffer take the one read at column -1 that a surplus candidate (b = s+1, dropped) makes in region row 0.
 // Dark field: Gb follows Cb at once (cb then spans both), at most 2 * 11 KB; the largest total is 46304 bytes at (4, 7).
-inline UmpaLds umpa_lds(int w, int s, bool df = false) {
-    const int UMPA_TW = df ? umpa_df_tw(w, s) : umpa_tw(w);
+inline UmpaLds umpa_lds(int w, int s, bool df) {
+    const int UMPA_TW = umpa_tw(w, s, df);
     const int Hr = UMPA_TH + 2 * w, Wr = UMPA_TW + 2 * w, Wrr = Wr + 2 * s;
     UmpaLds l;
     l.cb = 0;
@@ -134,7 +128,7 @@ __device__ __forceinline__ bool umpa_df_solve(double E, double B, double C, doub
 }
 
 template <int UMPA_TW, int S, bool DF = false>
-__global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int m, int w, UmpaLds L, float *__restrict__ trans,
+__global__ __launch_bounds__(UMPA_NT) void k_umpa(SpecklePtrs p, int K, int n, int m, int w, UmpaLds L, float *__restrict__ trans,
                                                   float *__restrict__ dx, float *__restrict__ dy, float *__restrict__ resid,
                                                   UmpaDf<DF> mu) {
     constexpr int NU = UMPA_NU, UMPA_PX = UMPA_TH * UMPA_TW / UMPA_NT, RS = UMPA_NT / UMPA_TW;
@@ -426,115 +420,81 @@ __global__ __launch_bounds__(UMPA_NT) void k_umpa(UmpaPtrs p, int K, int n, int 
     }
 }
 
-template <int UMPA_TW>
-void umpa_launch(int s, dim3 grid, const UmpaLds &L, hipStream_t st, const UmpaPtrs &p, int K, int n, int m, int w, float *t,
-                 float *dx, float *dy, float *res) {
-#define PSX_UMPA_CASE(SV)                                                                                                   \
-    case SV:                                                                                                                \
-        PSX_TIMED("k_umpa", st, k_umpa<UMPA_TW, SV><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res, {})); \
-        break;
+// The launch of k_umpa<UMPA_TW, s, DF>, s in [1, PSX_MAX_UMPA_SEARCH] (umpa_args has checked it).
+template <int UMPA_TW, bool DF>
+void umpa_launch(int s, dim3 grid, const UmpaLds &L, hipStream_t st, const SpecklePtrs &p, int K, int n, int m, int w, float *t,
+                 float *dx, float *dy, float *res, const UmpaDf<DF> &mu) {
+#define PSX_UMPA_GO(SV)                        \
+    PSX_TIMED(DF ? "k_umpa_df" : "k_umpa", st, \
+              k_umpa<UMPA_TW, SV, DF><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res, mu))
     switch (s) {
-        PSX_UMPA_CASE(1)
-        PSX_UMPA_CASE(2)
-        PSX_UMPA_CASE(3)
-        PSX_UMPA_CASE(4)
-        PSX_UMPA_CASE(5)
-        PSX_UMPA_CASE(6)
-        PSX_UMPA_CASE(7)
-        PSX_UMPA_CASE(8)
+        case 1: PSX_UMPA_GO(1); break;
+        case 2: PSX_UMPA_GO(2); break;
+        case 3: PSX_UMPA_GO(3); break;
+        case 4: PSX_UMPA_GO(4); break;
+        case 5: PSX_UMPA_GO(5); break;
+        case 6: PSX_UMPA_GO(6); break;
+        case 7: PSX_UMPA_GO(7); break;
+        case 8:
+            // k_umpa<32, 8, true> spills and must not be instantiated, not even in dead code; umpa_tw never sends s = 8 to it
+            if constexpr (!DF || UMPA_TW == 16) PSX_UMPA_GO(8);
+            break;
     }
-#undef PSX_UMPA_CASE
+#undef PSX_UMPA_GO
 }
 
-template <int UMPA_TW>
-int umpa_df_launch(int s, dim3 grid, const UmpaLds &L, hipStream_t st, const UmpaPtrs &p, const UmpaDf<true> &mu, int K, int n,
-                   int m, int w, float *t, float *dx, float *dy, float *res) {
-#define PSX_UMPA_CASE(SV)                                                                                                         \
-    case SV:                                                                                                                      \
-        PSX_TIMED("k_umpa_df", st,                                                                                                \
-                  k_umpa<UMPA_TW, SV, true><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res, mu));                 \
-        break;
-    if constexpr (UMPA_TW == 16) {                                   // s = 8 exists at the narrow tile only (umpa_df_tw)
-        if (s == 8) PSX_TIMED("k_umpa_df", st, k_umpa<16, 8, true><<<grid, UMPA_NT, L.total, st>>>(p, K, n, m, w, L, t, dx, dy, res, mu));
-    }
-    switch (s) {
-        PSX_UMPA_CASE(1)
-        PSX_UMPA_CASE(2)
-        PSX_UMPA_CASE(3)
-        PSX_UMPA_CASE(4)
-        PSX_UMPA_CASE(5)
-        PSX_UMPA_CASE(6)
-        PSX_UMPA_CASE(7)
-    }
-#undef PSX_UMPA_CASE
-    return 0;
-}
-
-// The argument checks psx_umpa_f32 and psx_umpa_df_f32 share, and the pointer block.
-int umpa_args(const char *fn, const float *const *S, const float *const *R, int K, int n, int m, int window, int search, UmpaPtrs &p) {
-    PSX_REQUIRE(K >= 1 && K <= PSX_MAX_LCS, "%s: K=%d positions outside [1,%d]", fn, K, PSX_MAX_LCS);
+// The argument checks of psx_umpa_f32 and psx_umpa_df_f32 beyond pack_speckle's.
+int umpa_args(const char *fn, int n, int m, int window, int search) {
     PSX_REQUIRE(window >= 1 && window <= PSX_MAX_UMPA_WINDOW, "%s: window=%d outside [1,%d]", fn, window, PSX_MAX_UMPA_WINDOW);
     PSX_REQUIRE(search >= 1 && search <= PSX_MAX_UMPA_SEARCH, "%s: search=%d outside [1,%d]", fn, search, PSX_MAX_UMPA_SEARCH);
     const int least = 2 * (window + search) + 1;
     PSX_REQUIRE(n >= least && m >= least, "%s: images %dx%d smaller than %dx%d = 2(window+search)+1", fn, n, m, least, least);
     PSX_REQUIRE((int64_t)n * m <= (int64_t)1 << 30, "%s: images %dx%d too large", fn, n, m);
-    PSX_REQUIRE(S != nullptr && R != nullptr, "%s: null pointer array", fn);
-    for (int k = 0; k < PSX_MAX_LCS; ++k) {
-        p.S[k] = nullptr;
-        p.R[k] = nullptr;
-    }
-    for (int k = 0; k < K; ++k) {
-        PSX_REQUIRE(S[k] != nullptr && R[k] != nullptr, "%s: position %d has a null image", fn, k);
-        p.S[k] = S[k];
-        p.R[k] = R[k];
-    }
     return 0;
+}
+
+// The host side of both entry points.  DF: mean and visibility are psx_umpa_df_f32's, null otherwise.
+template <bool DF>
+int umpa_run(const char *fn, const float *const *S, const float *const *R, const double *mean, int K, int n, int m, int window,
+             int search, float *transmission, float *dx, float *dy, float *visibility, float *residual, void *stream) {
+    SpecklePtrs p;
+    if (int rc = pack_speckle(p, fn, 1, S, R, K)) return rc;
+    if (int rc = umpa_args(fn, n, m, window, search)) return rc;
+    PSX_REQUIRE(!DF || mean != nullptr, "%s: null mean array", fn);
+    PSX_REQUIRE(transmission && dx && dy && (!DF || visibility) && residual, "%s: null output map", fn);
+    UmpaDf<DF> mu;
+    if constexpr (DF) {
+        mu.vis = visibility;
+        double sq = 0.0;
+        for (int k = 0; k < PSX_MAX_LCS; ++k) mu.mu[k] = 0.0;
+        for (int k = 0; k < K; ++k) {
+            PSX_REQUIRE(std::isfinite(mean[k]), "%s: mean[%d] is not finite", fn, k);
+            mu.mu[k] = mean[k];
+            sq += mean[k] * mean[k];
+        }
+        const double side = 2 * window + 1;
+        mu.H = side * side * sq;
+    }
+    const UmpaLds L = umpa_lds(window, search, DF);
+    const int tw = umpa_tw(window, search, DF);
+    const dim3 grid((unsigned)cdiv(m, tw), (unsigned)cdiv(n, UMPA_TH));
+    hipStream_t st = (hipStream_t)stream;
+    if (tw == 32)
+        umpa_launch<32, DF>(search, grid, L, st, p, K, n, m, window, transmission, dx, dy, residual, mu);
+    else
+        umpa_launch<16, DF>(search, grid, L, st, p, K, n, m, window, transmission, dx, dy, residual, mu);
+    return launch_check(DF ? "k_umpa_df" : "k_umpa");
 }
 
 }  // namespace
 
 extern "C" int psx_umpa_f32(const float *const *S, const float *const *R, int K, int n, int m, int window, int search,
                             float *transmission, float *dx, float *dy, float *residual, void *stream) {
-    const char *fn = "psx_umpa_f32";
-    UmpaPtrs p;
-    if (int rc = umpa_args(fn, S, R, K, n, m, window, search, p)) return rc;
-    PSX_REQUIRE(transmission && dx && dy && residual, "%s: null output map", fn);
-    const UmpaLds L = umpa_lds(window, search);
-    const dim3 grid((unsigned)cdiv(m, umpa_tw(window)), (unsigned)cdiv(n, UMPA_TH));
-    hipStream_t st = (hipStream_t)stream;
-    if (umpa_tw(window) == 32)
-        umpa_launch<32>(search, grid, L, st, p, K, n, m, window, transmission, dx, dy, residual);
-    else
-        umpa_launch<16>(search, grid, L, st, p, K, n, m, window, transmission, dx, dy, residual);
-    return launch_check("k_umpa");
+    return umpa_run<false>("psx_umpa_f32", S, R, nullptr, K, n, m, window, search, transmission, dx, dy, nullptr, residual, stream);
 }
 
 extern "C" int psx_umpa_df_f32(const float *const *S, const float *const *R, const double *mean, int K, int n, int m, int window,
                                int search, float *transmission, float *dx, float *dy, float *visibility, float *residual,
                                void *stream) {
-    const char *fn = "psx_umpa_df_f32";
-    UmpaPtrs p;
-    if (int rc = umpa_args(fn, S, R, K, n, m, window, search, p)) return rc;
-    PSX_REQUIRE(mean != nullptr, "%s: null mean array", fn);
-    PSX_REQUIRE(transmission && dx && dy && visibility && residual, "%s: null output map", fn);
-    UmpaDf<true> mu;
-    mu.vis = visibility;
-    double sq = 0.0;
-    for (int k = 0; k < PSX_MAX_LCS; ++k) mu.mu[k] = 0.0;
-    for (int k = 0; k < K; ++k) {
-        PSX_REQUIRE(std::isfinite(mean[k]), "%s: mean[%d] is not finite", fn, k);
-        mu.mu[k] = mean[k];
-        sq += mean[k] * mean[k];
-    }
-    const double side = 2 * window + 1;
-    mu.H = side * side * sq;
-    const UmpaLds L = umpa_lds(window, search, true);
-    const int tw = umpa_df_tw(window, search);
-    const dim3 grid((unsigned)cdiv(m, tw), (unsigned)cdiv(n, UMPA_TH));
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = tw == 32
-                       ? umpa_df_launch<32>(search, grid, L, st, p, mu, K, n, m, window, transmission, dx, dy, residual)
-                       : umpa_df_launch<16>(search, grid, L, st, p, mu, K, n, m, window, transmission, dx, dy, residual);
-    if (rc) return rc;
-    return launch_check("k_umpa_df");
+    return umpa_run<true>("psx_umpa_df_f32", S, R, mean, K, n, m, window, search, transmission, dx, dy, visibility, residual, stream);
 }

@@ -163,6 +163,7 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
 
 
 def main(argv=None):
+    from . import retrieval
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--experiment", default="Fil_Nylon_ID17")
     ap.add_argument("--type", default="RayT", choices=["RayT", "Fresnel"])
@@ -183,15 +184,7 @@ def main(argv=None):
     ap.add_argument("--retrieve", action="store_true",
                     help="speckle-tracking phase retrieval of every bin after the run (3 positions or more): "
                          "retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory")
-    ap.add_argument("--max-shift", type=float, default=None, help="--retrieve: clamp of the displacements, in pixels")
-    ap.add_argument("--dark-field", action="store_true",
-                    help="--retrieve with LCS-DF (4 positions or more): also retrieval/{df,scattering}_<expID><fmt>")
-    ap.add_argument("--method", default="lcs", choices=["lcs", "umpa", "umpa-df"],
-                    help="--retrieve with LCS (3 positions or more, |D| < 1 px), UMPA (1 position or more, |D| up to --search "
-                         "px; also retrieval/residual_<expID><fmt>) or UMPA with its dark-field term (umpa-df: also "
-                         "retrieval/visibility_<expID><fmt>)")
-    ap.add_argument("--window", type=int, default=2, help="--method umpa, umpa-df: half-width w of the (2w+1)^2 window, 1..8")
-    ap.add_argument("--search", type=int, default=3, help="--method umpa, umpa-df: largest integer shift searched, 1..8")
+    retrieval.add_retrieval_options(ap)          # --max-shift, --dark-field, --method, --window, --search: options of --retrieve
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -199,19 +192,16 @@ def main(argv=None):
     if a.xml:
         exp_dict['xmlDir'] = a.xml
     os.makedirs(exp_dict['filepath'], exist_ok=True)
-    if a.method in ("umpa", "umpa-df"):
-        if not a.retrieve:
-            ap.error("--method is an option of --retrieve")
-        if a.dark_field or a.max_shift is not None:
-            ap.error("--dark-field and --max-shift are options of --method lcs")
-        if not 1 <= a.window <= 8 or not 1 <= a.search <= 8:
-            ap.error("--window and --search must be in 1..8")
-    if a.retrieve and a.method == "lcs" and a.points < 3:
-        ap.error("--retrieve needs --points 3 or more")
+    if a.method != "lcs" and not a.retrieve:
+        ap.error("--method is an option of --retrieve")
+    retrieval.check_retrieval_options(ap, a)
+    floor = {df: t.min_positions for (m, df), t in retrieval.TRACKERS.items() if m == a.method}
+    if a.retrieve and a.points < floor[False]:
+        ap.error("--retrieve needs --points %d or more" % floor[False])
     if a.dark_field and not a.retrieve:
         ap.error("--dark-field is an option of --retrieve")
-    if a.dark_field and a.points < 4:
-        ap.error("--dark-field needs --points 4 or more")
+    if a.dark_field and a.points < floor[True]:
+        ap.error("--dark-field needs --points %d or more" % floor[True])
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search)
 

@@ -25,6 +25,12 @@ def _ptr(t):
     return c_void_p(t.data_ptr()) if t is not None else c_void_p(None)
 
 
+def _ptrs(tensors):
+    """The void* host array of a sequence of tensors for the C ABI; None gives NULL."""
+    tensors = list(tensors)
+    return (c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
 def _need(t, dtype, name, shape=None):
     if not isinstance(t, torch.Tensor):
         raise PsxError("%s must be a torch.Tensor, got %r" % (name, type(t)))
@@ -130,7 +136,7 @@ class MaterialStack:
         maps = [self.map(i) for i in range(self.n)]
         for i, m in enumerate(maps):
             _need(m, torch.float32, "thickness map %d" % i, shape)
-        self._c = ((c_void_p * max(1, self.n))(*[m.data_ptr() for m in maps]),
+        self._c = (_ptrs(maps or [None]),
                    (c_double * max(1, self.n))(*self.cphase), (c_double * max(1, self.n))(*self.catt))
         return self._c[0], self._c[1], self._c[2], self.n
 
@@ -152,7 +158,7 @@ def fold_materials(maps, cphase, catt):
     ms, cp, ca = list(maps), [float(v) for v in cphase], [float(v) for v in catt]
     while True:
         k = min(len(ms), _lib.PSX_MAX_FOLD)
-        check(lib().psx_fold_materials_f32((c_void_p * k)(*[m.data_ptr() for m in ms[:k]]), (c_double * k)(*cp[:k]),
+        check(lib().psx_fold_materials_f32(_ptrs(ms[:k]), (c_double * k)(*cp[:k]),
                                            (c_double * k)(*ca[:k]), k, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                                            out[0].numel(), _stream()), "psx_fold_materials_f32")
         if k == len(ms):
@@ -398,7 +404,7 @@ def accumulate_many(acc, imgs, sums, weights, scales=None, mats=None, add=True):
         el = range(e0, min(ne, e0 + _lib.PSX_MAX_SRC))
         n = len(el)
         check(lib().psx_accumulate_many_f32(
-            _ptr(acc), (c_void_p * n)(*[imgs[e].data_ptr() for e in el]), (c_float * n)(*[scales[e] for e in el]), n, T,
+            _ptr(acc), _ptrs(imgs[e] for e in el), (c_float * n)(*[scales[e] for e in el]), n, T,
             (c_double * max(1, n * nm))(*[c for e in el for c in cat[e]]), nm, 1 if (add or e0 > 0) else 0,
             imgs[0].numel(), _ptr(sums), (c_double * n)(*[float(weights[e]) for e in el]), _stream()),
             "psx_accumulate_many_f32")
@@ -486,11 +492,11 @@ def refract_batch(shape, mats, dscales, clamp, margin=15, I_in=None, I0=None, ou
         n = len(el)
         ws = _workspace(dev, lib().psx_refract_batch_workspace_bytes(Nx, Ny, n))
         check(lib().psx_refract_batch_f32(
-            n, (c_void_p * n)(*[I_in[e].data_ptr() for e in el]) if I_in is not None else None,
+            n, _ptrs(I_in[e] for e in el) if I_in is not None else None,
             (c_float * n)(*[I0[e] for e in el]), T,
             (c_double * (n * nm))(*[c for e in el for c in cph[e]]),
             (c_double * (n * nm))(*[c for e in el for c in cat[e]]), nm,
-            (c_void_p * n)(*[outs[e].data_ptr() for e in el]), c_float(out_scale), 1 if add else 0, Nx, Ny, int(margin),
+            _ptrs(outs[e] for e in el), c_float(out_scale), 1 if add else 0, Nx, Ny, int(margin),
             (c_double * n)(*[float(dscales[e]) for e in el]), c_double(clamp[0]), c_double(clamp[1]),
             _ptr(status_word(dev)), _ptr(ws), _stream()), "psx_refract_batch_f32")
     return outs
@@ -519,9 +525,8 @@ def refract_multi(shape, mats, dscales, clamp, margin=15, I_in=None, I0=1.0, phi
         _need(o, torch.float32, "I_out", (Nx, Ny))
     ws = _workspace(dev, lib().psx_refract_multi_workspace_bytes(Nx, Ny, nd))
     T, cp, ca, n = mats.cargs((Nx, Ny))
-    optr = (c_void_p * nd)(*[o.data_ptr() for o in outs])
     dsc = (c_double * nd)(*[float(x) for x in dscales])
-    check(lib().psx_refract_multi_f32(_ptr(I_in), c_float(I0), T, cp, ca, n, _ptr(phi_in), optr, c_float(out_scale),
+    check(lib().psx_refract_multi_f32(_ptr(I_in), c_float(I0), T, cp, ca, n, _ptr(phi_in), _ptrs(outs), c_float(out_scale),
                                       1 if add else 0, None, None, None, Nx, Ny, int(margin), dsc, nd,
                                       c_double(clamp[0]), c_double(clamp[1]), _ptr(status_word(dev)), _ptr(ws),
                                       _stream()), "psx_refract_multi_f32")
@@ -762,12 +767,11 @@ class FresnelPlan(_Plan):
             if t is not None:
                 _need(t, torch.float32, "inten_out[%d]" % i, shape)
         T, cp, ca, n = mats.cargs(shape)
-        wo = (c_void_p * nd)(*[w.data_ptr() if w is not None else None for w in waves])
-        io = (c_void_p * nd)(*[t.data_ptr() if t is not None else None for t in inten_out])
         check(lib().psx_fresnel_propagate(self._h, _ptr(wave_in), c_float(amp), T, cp, ca, n, nd,
                                           (c_double * nd)(*[float(v) for v in a]),
                                           (c_double * nd)(*[float(v) for v in gphase]), c_double(du[0]), c_double(du[1]),
-                                          wo, io, (c_float * nd)(*inten_scale), 1 if add else 0, _stream()),
+                                          _ptrs(waves), _ptrs(inten_out), (c_float * nd)(*inten_scale), 1 if add else 0,
+                                          _stream()),
               "psx_fresnel_propagate")
         return waves
 
@@ -797,9 +801,8 @@ class FresnelPlan(_Plan):
                 for d, t in enumerate(inten_out[s]):
                     if t is not None:
                         _need(t, torch.float32, "inten_out[%d][%d]" % (s, d), shape)
-            wi = (c_void_p * n)(*[(wave_in[s].data_ptr() if wave_in is not None and wave_in[s] is not None else None) for s in sl])
-            wo = (c_void_p * (n * nd))(*[(waves[s][d].data_ptr() if waves[s][d] is not None else None) for s in sl for d in range(nd)])
-            io = (c_void_p * (n * nd))(*[(inten_out[s][d].data_ptr() if inten_out[s][d] is not None else None) for s in sl for d in range(nd)])
+            wi = _ptrs(None if wave_in is None else wave_in[s] for s in sl)
+            wo, io = _ptrs(waves[s][d] for s in sl for d in range(nd)), _ptrs(inten_out[s][d] for s in sl for d in range(nd))
             check(lib().psx_fresnel_propagate_sources(
                 self._h, n, nd, wi, (c_float * n)(*[amp[s] for s in sl]), T,
                 (c_double * max(1, n * nm))(*[c for s in sl for c in cph[s]]),
@@ -844,9 +847,8 @@ class DetectorPlan(_Plan):
             _need(outs[k], torch.float32, "outs[%d]" % k, (self.nx, self.ny))
         for k0 in range(0, len(imgs), _lib.PSX_MAX_DETECT):
             part_in, part_out = imgs[k0:k0 + _lib.PSX_MAX_DETECT], outs[k0:k0 + _lib.PSX_MAX_DETECT]
-            pin = (c_void_p * len(part_in))(*[t.data_ptr() for t in part_in])
-            pout = (c_void_p * len(part_out))(*[t.data_ptr() for t in part_out])
-            check(lib().psx_detect_multi_f32(self._h, pin, pout, len(part_in), _stream()), "psx_detect_multi_f32")
+            check(lib().psx_detect_multi_f32(self._h, _ptrs(part_in), _ptrs(part_out), len(part_in), _stream()),
+                  "psx_detect_multi_f32")
         return outs
 
 
@@ -906,9 +908,8 @@ def poisson_multi(imgs, seeds):
         raise PsxError("poisson_multi: 1..%d images with one key each" % _lib.PSX_MAX_POISSON)
     for i, t in enumerate(imgs):
         _need(t, torch.float32, "imgs[%d]" % i, imgs[0].shape)
-    ptr = (c_void_p * len(imgs))(*[t.data_ptr() for t in imgs])
     sd = (ctypes.c_uint64 * len(imgs))(*[int(v) & (2 ** 64 - 1) for v in seeds])
-    check(lib().psx_poisson_multi_f32(ptr, sd, len(imgs), imgs[0].numel(), _stream()), "psx_poisson_multi_f32")
+    check(lib().psx_poisson_multi_f32(_ptrs(imgs), sd, len(imgs), imgs[0].numel(), _stream()), "psx_poisson_multi_f32")
     return imgs
 
 
@@ -966,11 +967,49 @@ def _positions(imgs, name, kmin=3):
     return imgs
 
 
-def _lcs_args(S, R, max_shift, out, names):
-    """The checks ops.lcs and ops.lcs_df share, after _positions: equal counts and shapes, float32 images in HBM on one device,
-    max_shift > 0 or None; out= tensors of the n x m shape (`names`, one per output map), or new ones.  -> (shape, dev, ms, out)"""
-    if len(S) != len(R):
-        raise PsxError("sample has %d positions, reference %d" % (len(S), len(R)))
+_NO_MEAN = object()      # _tracker_args: the tracker takes no reference means (None means "compute them")
+_COUNT_WORDS = {3: "three", 4: "four", 5: "five"}
+
+
+def _out_count(out, names):
+    if len(out) != len(names):
+        raise PsxError("out must hold %s tensors (%s)" % (_COUNT_WORDS[len(names)], ", ".join(names)))
+
+
+def _tracker_args(sample, reference, kmin, names, out, max_shift=None, window_search=None, mean=_NO_MEAN):
+    """The front end of the four speckle trackers (lcs, lcs_df, umpa, umpa_df), the checks in the order their callers document:
+    K in [kmin, PSX_MAX_LCS] on both sides (_positions), window / search and the smallest image they allow (UMPA), equal
+    counts, the reference means (umpa_df: host-only, so they and the number of out= tensors come before any device
+    check), equal shapes, float32 images in HBM on one device, max_shift > 0 or None (LCS), and out= tensors of the n x m
+    shape (`names`, one per output map), or new ones.  -> (S, R, device, out, mean)"""
+    S = _positions(sample, "sample", min(kmin, 3))
+    R = _positions(reference, "reference", min(kmin, 3))
+    for nm, imgs in (("sample", S), ("reference", R)):
+        if len(imgs) < kmin:      # LCS-DF: one position more than LCS, whose own floor _positions has reported
+            raise PsxError("%s: K=%d positions outside [%d, %d]: dark field has four unknowns" % (nm, len(imgs), kmin, _lib.PSX_MAX_LCS))
+    if window_search is not None:
+        for nm, v, cap in zip(("window", "search"), window_search, (_lib.PSX_MAX_UMPA_WINDOW, _lib.PSX_MAX_UMPA_SEARCH)):
+            if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
+                raise PsxError("%s must be an integer in [1, %d], got %r" % (nm, cap, v))
+        least = 2 * (int(window_search[0]) + int(window_search[1])) + 1
+        if S[0].shape[0] < least or S[0].shape[1] < least:
+            raise PsxError("images %dx%d smaller than %dx%d = 2*(window+search)+1" % (tuple(S[0].shape) + (least, least)))
+    K = len(S)
+    if K != len(R):
+        raise PsxError("sample has %d positions, reference %d" % (K, len(R)))
+    if mean is not _NO_MEAN:
+        if mean is not None:
+            try:
+                mean = [float(v) for v in mean]
+            except (TypeError, ValueError):
+                raise PsxError("mean must be a sequence of %d finite floats, got %r" % (K, mean))
+            if len(mean) != K:
+                raise PsxError("mean must hold one value per position (%d), got %d" % (K, len(mean)))
+            if not all(math.isfinite(v) for v in mean):
+                raise PsxError("mean must be finite, got %r" % (mean,))
+        if out is not None:
+            out = tuple(out)
+            _out_count(out, names)
     shape = tuple(S[0].shape)
     if tuple(R[0].shape) != shape:
         raise PsxError("reference images have shape %s, sample images %s" % (tuple(R[0].shape), shape))
@@ -982,20 +1021,18 @@ def _lcs_args(S, R, max_shift, out, names):
             _need(t, torch.float32, "%s[%d]" % (nm, k))
             if t.device != dev:
                 raise PsxError("%s[%d] is on %s, sample[0] on %s" % (nm, k, t.device, dev))
-    ms = 0.0 if max_shift is None else float(max_shift)
-    if max_shift is not None and not ms > 0.0:
+    if max_shift is not None and not float(max_shift) > 0.0:
         raise PsxError("max_shift must be > 0 pixels (None: no clamp), got %r" % (max_shift,))
     if out is None:
         out = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for _ in names)
     else:
         out = tuple(out)
-        if len(out) != len(names):
-            raise PsxError("out must hold %s tensors (%s)" % (("three", "four")[len(names) - 3], ", ".join(names)))
+        _out_count(out, names)
         for nm, t in zip(names, out):
             _need(t, torch.float32, "out " + nm, shape)
             if t.device != dev:
                 raise PsxError("out %s is on %s, the images on %s" % (nm, t.device, dev))
-    return shape, dev, ms, out
+    return S, R, dev, out, mean
 
 
 def lcs(sample, reference, max_shift=None, out=None):
@@ -1003,13 +1040,10 @@ def lcs(sample, reference, max_shift=None, out=None):
     images in HBM -> (transmission, dx, dy), n x m float32.  dx is the displacement along axis 0, dy along axis 1, in pixels,
     with the sign of the chain's Dxreal / Dyreal.  max_shift (pixels, > 0) clamps dx and dy; None: no clamp.  out: three
     caller-owned n x m float32 tensors (transmission, dx, dy) to write into."""
-    S = _positions(sample, "sample")
-    R = _positions(reference, "reference")
-    shape, dev, ms, out = _lcs_args(S, R, max_shift, out, ("transmission", "dx", "dy"))
-    K = len(S)
+    S, R, dev, out, _ = _tracker_args(sample, reference, 3, ("transmission", "dx", "dy"), out, max_shift=max_shift)
     with torch.cuda.device(dev):
-        check(lib().psx_lcs_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K, shape[0], shape[1], c_float(ms),
-                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), "psx_lcs_f32")
+        check(lib().psx_lcs_f32(_ptrs(S), _ptrs(R), len(S), *S[0].shape, c_float(float(max_shift or 0)), *map(_ptr, out), _stream()),
+              "psx_lcs_f32")
     return out
 
 
@@ -1019,17 +1053,10 @@ def lcs_df(sample, reference, max_shift=None, out=None):
     pairs in the forms ops.lcs takes -> (transmission, dx, dy, df), n x m float32.  dx, dy as ops.lcs (max_shift clamps these
     two only); df is the diffusion coefficient in detector pixels^2 (a Gaussian blur of per-axis variance s^2 gives
     df = s^2/2), not clamped.  out: four caller-owned n x m float32 tensors (transmission, dx, dy, df) to write into."""
-    S = _positions(sample, "sample")
-    R = _positions(reference, "reference")
-    for nm, imgs in (("sample", S), ("reference", R)):
-        if len(imgs) < 4:
-            raise PsxError("%s: K=%d positions outside [4, %d]: dark field has four unknowns" % (nm, len(imgs), _lib.PSX_MAX_LCS))
-    shape, dev, ms, out = _lcs_args(S, R, max_shift, out, ("transmission", "dx", "dy", "df"))
-    K = len(S)
+    S, R, dev, out, _ = _tracker_args(sample, reference, 4, ("transmission", "dx", "dy", "df"), out, max_shift=max_shift)
     with torch.cuda.device(dev):
-        check(lib().psx_lcs_df_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K,
-                                   shape[0], shape[1], c_float(ms), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
-                                   _stream()), "psx_lcs_df_f32")
+        check(lib().psx_lcs_df_f32(_ptrs(S), _ptrs(R), len(S), *S[0].shape, c_float(float(max_shift or 0)), *map(_ptr, out), _stream()),
+              "psx_lcs_df_f32")
     return out
 
 
@@ -1041,20 +1068,10 @@ def umpa(sample, reference, window=2, search=3, out=None):
     costs; dx along axis 0, dy along axis 1, the sign of ops.lcs.  residual = cost/sum S^2 at the minimum.  Pixels closer
     than window+search to a border are exactly (1, 0, 0, 0).  window in [1, PSX_MAX_UMPA_WINDOW], search in
     [1, PSX_MAX_UMPA_SEARCH], n, m >= 2*(window+search)+1.  out: four caller-owned n x m float32 tensors to write into."""
-    S = _positions(sample, "sample", kmin=1)
-    R = _positions(reference, "reference", kmin=1)
-    for nm, v, cap in (("window", window, _lib.PSX_MAX_UMPA_WINDOW), ("search", search, _lib.PSX_MAX_UMPA_SEARCH)):
-        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
-            raise PsxError("%s must be an integer in [1, %d], got %r" % (nm, cap, v))
-    w, sr = int(window), int(search)
-    least = 2 * (w + sr) + 1
-    if S[0].shape[0] < least or S[0].shape[1] < least:
-        raise PsxError("images %dx%d smaller than %dx%d = 2*(window+search)+1" % (tuple(S[0].shape) + (least, least)))
-    shape, dev, _, out = _lcs_args(S, R, None, out, ("transmission", "dx", "dy", "residual"))
-    K = len(S)
+    S, R, dev, out, _ = _tracker_args(sample, reference, 1, ("transmission", "dx", "dy", "residual"), out,
+                                      window_search=(window, search))
     with torch.cuda.device(dev):
-        check(lib().psx_umpa_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]), K,
-                                 shape[0], shape[1], w, sr, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _stream()),
+        check(lib().psx_umpa_f32(_ptrs(S), _ptrs(R), len(S), *S[0].shape, int(window), int(search), *map(_ptr, out), _stream()),
               "psx_umpa_f32")
     return out
 
@@ -1068,36 +1085,13 @@ def umpa_df(sample, reference, window=2, search=3, mean=None, out=None):
     (1, 0, 0, 1, 0).  mean: K finite floats, the mu_k; None computes each reference frame's mean in float64 on the device
     and copies the K values to the host, which SYNCHRONISES the stream -- pass the means to stay asynchronous.  Everything
     else (window, search, sizes, input forms) as ops.umpa.  out: five caller-owned n x m float32 tensors to write into."""
-    S = _positions(sample, "sample", kmin=1)
-    R = _positions(reference, "reference", kmin=1)
-    for nm, v, cap in (("window", window, _lib.PSX_MAX_UMPA_WINDOW), ("search", search, _lib.PSX_MAX_UMPA_SEARCH)):
-        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
-            raise PsxError("%s must be an integer in [1, %d], got %r" % (nm, cap, v))
-    w, sr = int(window), int(search)
-    least = 2 * (w + sr) + 1
-    if S[0].shape[0] < least or S[0].shape[1] < least:
-        raise PsxError("images %dx%d smaller than %dx%d = 2*(window+search)+1" % (tuple(S[0].shape) + (least, least)))
-    if len(S) != len(R):
-        raise PsxError("sample has %d positions, reference %d" % (len(S), len(R)))
-    K = len(S)
-    if mean is not None:
-        try:
-            mean = [float(v) for v in mean]
-        except (TypeError, ValueError):
-            raise PsxError("mean must be a sequence of %d finite floats, got %r" % (K, mean))
-        if len(mean) != K:
-            raise PsxError("mean must hold one value per position (%d), got %d" % (K, len(mean)))
-        if not all(math.isfinite(v) for v in mean):
-            raise PsxError("mean must be finite, got %r" % (mean,))
-    if out is not None and len(tuple(out)) != 5:
-        raise PsxError("out must hold five tensors (transmission, dx, dy, visibility, residual)")
-    shape, dev, _, out = _lcs_args(S, R, None, out, ("transmission", "dx", "dy", "visibility", "residual"))
+    S, R, dev, out, mean = _tracker_args(sample, reference, 1, ("transmission", "dx", "dy", "visibility", "residual"), out,
+                                         window_search=(window, search), mean=mean)
     with torch.cuda.device(dev):
         if mean is None:
             mean = torch.stack([t.mean(dtype=torch.float64) for t in R]).tolist()      # one copy to the host: synchronises
-        check(lib().psx_umpa_df_f32((c_void_p * K)(*[t.data_ptr() for t in S]), (c_void_p * K)(*[t.data_ptr() for t in R]),
-                                    (c_double * K)(*mean), K, shape[0], shape[1], w, sr, _ptr(out[0]), _ptr(out[1]),
-                                    _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _stream()), "psx_umpa_df_f32")
+        check(lib().psx_umpa_df_f32(_ptrs(S), _ptrs(R), (c_double * len(S))(*mean), len(S), *S[0].shape, int(window), int(search),
+                                    *map(_ptr, out), _stream()), "psx_umpa_df_f32")
     return out
 
 

@@ -35,15 +35,42 @@ only transmission, dx and dy.  --dark-field (4 positions or more) adds df, and s
 (the same rules) also fits UMPA's dark-field term and adds visibility.
 """
 import argparse
+import collections
 import os
 import re
 import sys
 
 import numpy as np
 
+from . import _lib
 from .getk import getk
 
 _plans = {}
+
+
+# The trackers, keyed by what the user says: (method, dark_field).  Each row: the ops function, the fewest positions, the
+# output maps in that function's order, and the options the method takes.  A new tracker is a new row.
+Tracker = collections.namedtuple("Tracker", "op min_positions maps options")
+TRACKERS = {
+    ('lcs', False): Tracker('lcs', 3, ('transmission', 'dx', 'dy'), ('max_shift',)),
+    ('lcs', True): Tracker('lcs_df', 4, ('transmission', 'dx', 'dy', 'df'), ('max_shift',)),
+    ('umpa', False): Tracker('umpa', 1, ('transmission', 'dx', 'dy', 'residual'), ('window', 'search')),
+    ('umpa-df', False): Tracker('umpa_df', 1, ('transmission', 'dx', 'dy', 'visibility', 'residual'), ('window', 'search', 'mean')),
+}
+METHODS = tuple(dict.fromkeys(m for m, _ in TRACKERS))
+UMPA_METHODS = tuple(m for (m, _), t in TRACKERS.items() if 'window' in t.options)
+# why a method of UMPA_METHODS has no row with dark_field=True
+_NO_DARK_FIELD = {'umpa': "has no dark-field term", 'umpa-df': "always fits its dark-field term"}
+# every map a bin's result may hold, in the order save_retrieval writes them
+MAP_ORDER = ("transmission", "dx", "dy", "phi", "df", "scattering", "visibility", "residual")
+assert all(set(t.maps) <= set(MAP_ORDER) for t in TRACKERS.values())
+
+
+def _track(key, sample, reference, **options):
+    """One bin through the tracker of TRACKERS[key] -> {map name: n x m float32 tensor}."""
+    from . import ops
+    t = TRACKERS[key]
+    return dict(zip(t.maps, getattr(ops, t.op)(sample, reference, **options)))
 
 
 def lcs(sample, reference, max_shift=None, dark_field=False):
@@ -51,12 +78,7 @@ def lcs(sample, reference, max_shift=None, dark_field=False):
     {'transmission', 'dx', 'dy'}, n x m float32 on the same device.  max_shift (pixels): clamp dx, dy; None: no clamp.
     dark_field: LCS-DF (K >= 4, ops.lcs_df) -- the four-unknown system, whose transmission and displacement are not biased
     by the lost speckle visibility of a scattering sample, and 'df' (detector px^2, unclamped) in the dict."""
-    from . import ops
-    if dark_field:
-        t, dx, dy, df = ops.lcs_df(sample, reference, max_shift=max_shift)
-        return {'transmission': t, 'dx': dx, 'dy': dy, 'df': df}
-    t, dx, dy = ops.lcs(sample, reference, max_shift=max_shift)
-    return {'transmission': t, 'dx': dx, 'dy': dy}
+    return _track(('lcs', bool(dark_field)), sample, reference, max_shift=max_shift)
 
 
 def umpa(sample, reference, window=2, search=3, dark_field=False, mean=None):
@@ -67,38 +89,31 @@ def umpa(sample, reference, window=2, search=3, dark_field=False, mean=None):
     speckle visibility behind the sample over the reference's, 1 in the border band, not clamped.  mean: the K reference
     means mu_k (None: computed on the device, which synchronises).  V is not converted to a scattering angle: that
     conversion depends on the speckle's spectrum."""
-    from . import ops
-    if dark_field:
-        t, dx, dy, vis, res = ops.umpa_df(sample, reference, window=window, search=search, mean=mean)
-        return {'transmission': t, 'dx': dx, 'dy': dy, 'visibility': vis, 'residual': res}
-    if mean is not None:
+    key = ('umpa-df' if dark_field else 'umpa', False)
+    options = {'window': window, 'search': search}
+    if 'mean' in TRACKERS[key].options:
+        options['mean'] = mean
+    elif mean is not None:
         raise ValueError("mean is an option of dark_field=True")
-    t, dx, dy, res = ops.umpa(sample, reference, window=window, search=search)
-    return {'transmission': t, 'dx': dx, 'dy': dy, 'residual': res}
-
-
-METHODS = ("lcs", "umpa", "umpa-df")
-UMPA_METHODS = ("umpa", "umpa-df")
+    return _track(key, sample, reference, **options)
 
 
 def check_method(method, npos, max_shift=None, dark_field=False):
     """The argument rules of retrieve(): ValueError for an unknown method, too few positions (lcs: 3, LCS-DF: 4, umpa and
-    umpa-df: 1), or umpa / umpa-df with dark_field or max_shift.  Needs no GPU."""
+    umpa-df: 1), or umpa / umpa-df with dark_field or max_shift.  Needs no GPU.  -> the method's key in TRACKERS."""
     if method not in METHODS:
         raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
-    if method in UMPA_METHODS:
-        if dark_field:
-            raise ValueError("method='umpa' has no dark-field term: dark_field is an option of method='lcs'" if method == "umpa"
-                             else "method='umpa-df' always fits its dark-field term: dark_field is an option of method='lcs'")
-        if max_shift is not None:
-            raise ValueError("method=%r is bounded by its search range: max_shift is an option of method='lcs'" % method)
-        if npos < 1:
-            raise ValueError("phase retrieval needs at least 1 position, got %d" % npos)
-        return
-    if npos < 3:
-        raise ValueError("phase retrieval needs at least 3 positions, got %d" % npos)
-    if dark_field and npos < 4:
-        raise ValueError("dark-field retrieval needs at least 4 positions, got %d" % npos)
+    key = (method, bool(dark_field))
+    if key not in TRACKERS:
+        raise ValueError("method=%r %s: dark_field is an option of method='lcs'" % (method, _NO_DARK_FIELD[method]))
+    if max_shift is not None and 'max_shift' not in TRACKERS[key].options:
+        raise ValueError("method=%r is bounded by its search range: max_shift is an option of method='lcs'" % method)
+    least = TRACKERS[(method, False)].min_positions
+    if npos < least:
+        raise ValueError("phase retrieval needs at least %d position%s, got %d" % (least, "s" if least > 1 else "", npos))
+    if npos < TRACKERS[key].min_positions:
+        raise ValueError("dark-field retrieval needs at least %d positions, got %d" % (TRACKERS[key].min_positions, npos))
+    return key
 
 
 def _plan(device, n, m):
@@ -188,7 +203,9 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
     dark_field nor max_shift (ValueError).  method='umpa-df': umpa(dark_field=True), the same rules; every bin gains
     'visibility' as well (no scattering angle is derived from it)."""
     positions = sorted(results)
-    check_method(method, len(positions), max_shift, dark_field)
+    key = check_method(method, len(positions), max_shift, dark_field)
+    options = {'max_shift': max_shift, 'window': window, 'search': search}
+    options = {k: v for k, v in options.items() if k in TRACKERS[key].options}
     import torch
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     S = _stack(results, positions, 0, dev)
@@ -199,15 +216,12 @@ def retrieve(results, params=None, bins=None, energies=None, max_shift=None, dev
         raise ValueError("energies must hold one value per retrieved bin (%d), got %d" % (len(bins), len(energies)))
     out = {}
     for i, b in enumerate(bins):
-        if method in UMPA_METHODS:
-            r = umpa([s[b] for s in S], [s[b] for s in R], window=window, search=search, dark_field=method == "umpa-df")
-        else:
-            r = lcs([s[b] for s in S], [s[b] for s in R], max_shift=max_shift, dark_field=dark_field)
+        r = _track(key, [s[b] for s in S], [s[b] for s in R], **options)
         if params is not None:
             e = params['energy_keV'] if energies is None else energies[i]
             r['phi'] = integrate(r['dx'], r['dy'],
                                  scale=gradient_scale(e, params['pixel_um'], params['distance_m'], params['magnification']))
-            if dark_field:
+            if 'df' in r:
                 r['scattering'] = scattering_angle(r['df'], params['pixel_um'], params['distance_m'])
         out[b] = r
     return out
@@ -220,7 +234,7 @@ def save_retrieval(r, directory, exp_id, fmt):
     d = os.path.join(directory, "retrieval")
     os.makedirs(d, exist_ok=True)
     paths = []
-    for name in ("transmission", "dx", "dy", "phi", "df", "scattering", "visibility", "residual"):
+    for name in MAP_ORDER:
         if name in r:
             paths.append(os.path.join(d, "%s_%s%s" % (name, exp_id, fmt)))
             save_image(r[name].detach().cpu().numpy(), paths[-1])
@@ -272,21 +286,62 @@ def discover(run_dir, min_positions=3):
     return found
 
 
-def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None, dark_field=False, method='lcs', window=2, search=3):
-    """discover() + lcs (+ integrate when params are given) + save_retrieval for every bin directory; returns the paths.
-    dark_field: LCS-DF (4 positions or more), df (+ scattering with params) written too.  method='umpa' (window, search):
-    UMPA instead of LCS, 1 position or more, residual written too; method='umpa-df': visibility as well."""
+def _first_floor(method):
+    """The fewest positions discover() asks for: the method's without dark field (an unknown method is retrieve()'s to report,
+    after discovery as ever: LCS's floor)."""
+    return TRACKERS.get((method, False), TRACKERS[('lcs', False)]).min_positions
+
+
+def _retrieve_found(found, params, fmt, **how):
     import torch
     from .InputOutput.pagailleIO import openImage
     written = []
     dev = torch.device("cuda", torch.cuda.current_device())
-    for d, exp_id, in_fmt, pairs in discover(run_dir, min_positions=1 if method in UMPA_METHODS else 3):
+    for d, exp_id, in_fmt, pairs in found:
         S = torch.from_numpy(np.stack([np.asarray(openImage(s), dtype=np.float32) for _, s, _ in pairs])).to(dev)
         R = torch.from_numpy(np.stack([np.asarray(openImage(r), dtype=np.float32) for _, _, r in pairs])).to(dev)
-        res = retrieve({p: (S[i:i + 1], R[i:i + 1]) for i, (p, _, _) in enumerate(pairs)}, params, max_shift=max_shift,
-                       dark_field=dark_field, method=method, window=window, search=search)[0]
+        res = retrieve({p: (S[i:i + 1], R[i:i + 1]) for i, (p, _, _) in enumerate(pairs)}, params, **how)[0]
         written += save_retrieval(res, d, exp_id, fmt or in_fmt)
     return written
+
+
+def retrieve_run_dir(run_dir, params=None, max_shift=None, fmt=None, dark_field=False, method='lcs', window=2, search=3):
+    """discover() + lcs (+ integrate when params are given) + save_retrieval for every bin directory; returns the paths.
+    dark_field: LCS-DF (4 positions or more), df (+ scattering with params) written too.  method='umpa' (window, search):
+    UMPA instead of LCS, 1 position or more, residual written too; method='umpa-df': visibility as well."""
+    return _retrieve_found(discover(run_dir, min_positions=_first_floor(method)), params, fmt, max_shift=max_shift,
+                           dark_field=dark_field, method=method, window=window, search=search)
+
+
+def add_retrieval_options(ap):
+    """--max-shift, --dark-field, --method, --window, --search on an argparse parser: the retrieval options of this module's
+    command line and of main.py's --retrieve."""
+    ap.add_argument("--max-shift", type=float, default=None, help="--method lcs: clamp of dx, dy in pixels")
+    ap.add_argument("--dark-field", action="store_true",
+                    help="--method lcs: LCS-DF (4 positions or more): also df (detector px^2) and, with the physical "
+                         "parameters, scattering (rad)")
+    ap.add_argument("--method", choices=METHODS, default="lcs",
+                    help="lcs (3 positions or more, |D| < 1 px), umpa (1 position or more, |D| up to --search px; also residual) "
+                         "or umpa-df (umpa with its dark-field term: also visibility)")
+    ap.add_argument("--window", type=int, default=2, help="--method umpa, umpa-df: half-width w of the (2w+1)^2 window, 1..%d"
+                    % _lib.PSX_MAX_UMPA_WINDOW)
+    ap.add_argument("--search", type=int, default=3, help="--method umpa, umpa-df: largest integer shift searched, 1..%d"
+                    % _lib.PSX_MAX_UMPA_SEARCH)
+
+
+def check_retrieval_options(ap, a, positions=None):
+    """The rules of add_retrieval_options' five, as ap.error: which options the method takes, the bounds of --window and --search
+    and, where the positions are known (positions: (directory, count) pairs), how many the tracker needs."""
+    options = TRACKERS[(a.method, False)].options
+    if 'max_shift' not in options and (a.dark_field or a.max_shift is not None):
+        ap.error("--dark-field and --max-shift are options of --method lcs")
+    wmax, smax = _lib.PSX_MAX_UMPA_WINDOW, _lib.PSX_MAX_UMPA_SEARCH
+    if 'window' in options and not (1 <= a.window <= wmax and 1 <= a.search <= smax):
+        ap.error("--window and --search must be in 1..%d" % wmax + (" and 1..%d" % smax) * (smax != wmax))
+    least = TRACKERS[(a.method, a.dark_field)].min_positions
+    for d, n in positions or ():
+        if n < least:
+            ap.error("--dark-field needs at least %d positions; %s has %d" % (least, d, n))
 
 
 def main(argv=None):
@@ -297,33 +352,19 @@ def main(argv=None):
     ap.add_argument("--pixel-um", type=float, default=None, help="detector pixel size, micrometres")
     ap.add_argument("--distance", type=float, default=None, help="object-to-detector distance, metres")
     ap.add_argument("--magnification", type=float, default=None, help="exp_dict['magnification']")
-    ap.add_argument("--max-shift", type=float, default=None, help="clamp of dx, dy in pixels")
     ap.add_argument("--format", default=None, help="output format (.tif, .edf, .npy); default: the input's")
-    ap.add_argument("--dark-field", action="store_true",
-                    help="LCS-DF (4 positions or more): also df (detector px^2) and, with the physical parameters, scattering "
-                         "(rad)")
-    ap.add_argument("--method", choices=METHODS, default="lcs",
-                    help="lcs (3 positions or more, |D| < 1 px), umpa (1 position or more, |D| up to --search px) or umpa-df "
-                         "(umpa with its dark-field term: also visibility)")
-    ap.add_argument("--window", type=int, default=2, help="--method umpa, umpa-df: half-width w of the (2w+1)^2 window, 1..8")
-    ap.add_argument("--search", type=int, default=3, help="--method umpa, umpa-df: largest integer shift searched, 1..8")
+    add_retrieval_options(ap)
     a = ap.parse_args(argv)
-    if a.method in UMPA_METHODS:
-        if a.dark_field or a.max_shift is not None:
-            ap.error("--dark-field and --max-shift are options of --method lcs")
-        if not 1 <= a.window <= 8 or not 1 <= a.search <= 8:
-            ap.error("--window and --search must be in 1..8")
+    check_retrieval_options(ap, a)
     phys = (a.energy, a.pixel_um, a.distance, a.magnification)
     if any(v is not None for v in phys) and any(v is None for v in phys):
         ap.error("--energy, --pixel-um, --distance and --magnification go together")
     params = None if phys[0] is None else {'energy_keV': a.energy, 'pixel_um': a.pixel_um, 'distance_m': a.distance,
                                            'magnification': a.magnification}
-    if a.dark_field:
-        for d, _, _, pairs in discover(a.run_dir):
-            if len(pairs) < 4:
-                ap.error("--dark-field needs at least 4 positions; %s has %d" % (d, len(pairs)))
-    for p in retrieve_run_dir(a.run_dir, params, max_shift=a.max_shift, fmt=a.format, dark_field=a.dark_field, method=a.method,
-                              window=a.window, search=a.search):
+    found = discover(a.run_dir, min_positions=_first_floor(a.method))
+    check_retrieval_options(ap, a, [(d, len(pairs)) for d, _, _, pairs in found])
+    for p in _retrieve_found(found, params, a.format, max_shift=a.max_shift, dark_field=a.dark_field, method=a.method,
+                             window=a.window, search=a.search):
         print(p)
     return 0
 

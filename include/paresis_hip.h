@@ -435,6 +435,30 @@ int psx_integrate_plan_create(int n, int m, psx_integrate_plan **plan);
 int psx_integrate_plan_destroy(psx_integrate_plan *plan);
 size_t psx_integrate_plan_bytes(const psx_integrate_plan *plan);
 int psx_integrate_f32(psx_integrate_plan *plan, const float *gx, const float *gy, double scale, float *phi, void *stream);
+/* Paganin's single-distance, single-material phase retrieval (Paganin et al., J. Microsc. 206, 33, 2002) of B propagation
+ * images of the plan's n x m shape, on the plan's 2n x 2m buffer and transforms (no allocation in the call).  Per image b,
+ * I = image[b], I0 = white[b] (the flat field; absent when `white` or white[b] is NULL), alpha[b] >= 0 the filter strength
+ * in detector px^2, mu[b] > 0 the linear attenuation coefficient in 1/m (both HOST arrays of B finite values):
+ *   r = I/I0 formed in float64 (r = I where I0 is absent); a pixel whose I is not finite, or whose I0 is not finite or
+ *   not > 0, gets r = 1;
+ *   x = float32(r - 1): the transform carries r - 1, not r (the filter passes DC unchanged, and the float32 transform
+ *   error then scales with the contrast, not with 1);
+ *   ext[a][b] = x[a < n ? a : 2n-1-a][b < m ? b : 2m-1-b], the even mirror extension, psx_integrate_f32's indices;
+ *   y = ifft2( fft2(ext) / (1 + alpha*(kx^2 + ky^2)) ), kx = 2 pi fftfreq(2n), ky = 2 pi fftfreq(2m) (psx_integrate_f32's),
+ *   the denominator formed in float64;
+ *   c = 1 + y on the n x m corner: the contact image exp(-mu*t);
+ *   thickness = -log1p(y)/mu in float64 where c > 0, else -log(FLT_MIN)/mu: finite wherever y is.
+ * Two images share one complex transform pair: image 2j is the real part, image 2j+1 the imaginary part (zero for a last
+ * odd image); the filter separates the two spectra through the Hermitian pair (k, -k), A^(k) = (Z(k) + conj Z(-k))/2,
+ * B^(k) = (Z(k) - conj Z(-k))/(2i), applies each image's own factor and recombines A^ + i B^; self-paired points (DC, the
+ * Nyquist row and column) go through the same formula.
+ * image: HOST array of B in [1, PSX_MAX_PAGANIN] device pointers to n x m float32 images.  contact, thickness: HOST arrays
+ * of B device pointers to n x m float32 outputs; either array, or single entries of it, may be NULL (that map is not
+ * written), but every image needs one of the two.  Calls on one plan (psx_integrate_f32's included) are ordered on one
+ * stream: they share its buffer. */
+#define PSX_MAX_PAGANIN 64
+int psx_paganin_f32(psx_integrate_plan *plan, int B, const float *const *image, const float *const *white,
+                    const double *alpha, const double *mu, float *const *contact, float *const *thickness, void *stream);
 
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------------------------------------
  * psx_profile_enable(1) clears the log and makes every kernel launch of the library record a HIP event pair on the

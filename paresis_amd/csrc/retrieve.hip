@@ -19,6 +19,13 @@
 //                   P = (-i kx Gx^ - i ky Gy^)/(kx^2 + ky^2), P(0) = 0; one thread owns the pair (k, -k)
 //   rocFFT inverse, in place
 //   k_integ_crop    phi = Re(.)/(4nm) on the n x m corner
+//
+// Paganin (J. Microsc. 206, 33, 2002; psx_paganin_f32) on the same plan, two images per transform pair:
+//   k_pag_pack      Z = xA + i*xB, x = float32(I/I0 - 1) (1 -> 0 at guarded pixels), mirrored evenly: one thread per source pixel
+//   rocFFT forward, in place
+//   k_pag_filter    A^(k) = (Z(k) + conj Z(-k))/2, B^(k) = (Z(k) - conj Z(-k))/(2i), Y = fA A^ + i fB B^, f = 1/(1 + alpha k^2)
+//   rocFFT inverse, in place
+//   k_pag_crop      y = Re / Im (.)/(4nm) on the n x m corner; contact = 1 + y, thickness = -log1p(y)/mu
 #include "fresnel_plan.hpp"
 
 using namespace psx;
@@ -219,6 +226,82 @@ __global__ __launch_bounds__(256) void k_integ_crop(const float2 *__restrict__ Z
     }
 }
 
+// The two images of one Paganin transform (psx_paganin_f32): B's pointers are null and its numbers unused for a last odd image
+struct PagPair {
+    const float *I[2], *W[2];
+    float *contact[2], *thickness[2];
+    double alpha[2], mu[2];
+};
+
+// x = float32(I/I0 - 1) of pixel p of image s of the pair; 0 for an absent image and at a guarded pixel
+__device__ __forceinline__ float pag_contrast(const PagPair &pp, int s, int64_t p) {
+    if (!pp.I[s]) return 0.0f;
+    const float v = pp.I[s][p];
+    if (!isfinite(v)) return 0.0f;
+    if (!pp.W[s]) return (float)((double)v - 1.0);
+    const float w = pp.W[s][p];
+    if (!(isfinite(w) && w > 0.0f)) return 0.0f;
+    return (float)((double)v / (double)w - 1.0);
+}
+
+// one thread per source pixel (i, j): its value goes to the four mirror images (i | 2n-1-i, j | 2m-1-j) of the extension
+__global__ __launch_bounds__(256) void k_pag_pack(PagPair pp, float2 *__restrict__ Z, int n, int m) {
+    const int64_t N = (int64_t)n * m, W = 2 * (int64_t)m;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (int64_t)gridDim.x * blockDim.x) {
+        const int i = (int)(p / m), j = (int)(p - (int64_t)i * m);
+        const float2 z = make_float2(pag_contrast(pp, 0, p), pag_contrast(pp, 1, p));
+        const int64_t r0 = (int64_t)i * W, r1 = (int64_t)(2 * n - 1 - i) * W;
+        const int j1 = 2 * m - 1 - j;
+        Z[r0 + j] = z;
+        Z[r0 + j1] = z;
+        Z[r1 + j] = z;
+        Z[r1 + j1] = z;
+    }
+}
+
+// Y(k) from Z(k) and Z(-k): the two real images' spectra, each times its own factor, recombined
+__device__ __forceinline__ float2 pag_filter(float2 zk, float2 zm, float fa, float fb) {
+    // A^ = (zk + conj zm)/2;  B^ = (-i)(zk - conj zm)/2
+    const float ar = 0.5f * (zk.x + zm.x), ai = 0.5f * (zk.y - zm.y);
+    const float br = 0.5f * (zk.y + zm.y), bi = -0.5f * (zk.x - zm.x);
+    // fa*A^ + i*fb*B^
+    return make_float2(fa * ar - fb * bi, fa * ai + fb * br);
+}
+
+// k_integ_filter's pairing: the thread of the smaller index owns (k, -k); k^2 is the same for both
+__global__ __launch_bounds__(256) void k_pag_filter(float2 *__restrict__ Z, int n, int m, double alpha_a, double alpha_b) {
+    const int H = 2 * n, W = 2 * m;
+    const int64_t N = (int64_t)H * W;
+    const double wx = PSX_TWO_PI / (double)H, wy = PSX_TWO_PI / (double)W;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < N; q += (int64_t)gridDim.x * blockDim.x) {
+        const int a = (int)(q / W), b = (int)(q - (int64_t)a * W);
+        const int a2 = a ? H - a : 0, b2 = b ? W - b : 0;
+        const int64_t q2 = (int64_t)a2 * W + b2;
+        if (q2 < q) continue;
+        const double kx = wx * (a < n ? a : a - H), ky = wy * (b < m ? b : b - W);
+        const double k2 = kx * kx + ky * ky;
+        const float fa = (float)(1.0 / (1.0 + alpha_a * k2)), fb = (float)(1.0 / (1.0 + alpha_b * k2));
+        const float2 z1 = Z[q], z2 = Z[q2];
+        if (q2 != q) Z[q2] = pag_filter(z2, z1, fa, fb);
+        Z[q] = pag_filter(z1, z2, fa, fb);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pag_crop(PagPair pp, const float2 *__restrict__ Z, int n, int m, double norm) {
+    const int64_t N = (int64_t)n * m;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (int64_t)gridDim.x * blockDim.x) {
+        const int i = (int)(p / m), j = (int)(p - (int64_t)i * m);
+        const float2 z = Z[(int64_t)i * 2 * m + j];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const double y = (double)(s ? z.y : z.x) * norm;
+            const double c = 1.0 + y;
+            if (pp.contact[s]) pp.contact[s][p] = (float)c;
+            if (pp.thickness[s]) pp.thickness[s][p] = (float)((c > 0.0 ? -log1p(y) : 87.33654475055310898657) / pp.mu[s]);
+        }
+    }
+}
+
 }  // namespace
 
 struct psx_integrate_plan {
@@ -304,6 +387,47 @@ int psx_integrate_f32(psx_integrate_plan *plan, const float *gx, const float *gy
     const float norm = (float)(1.0 / (double)N);
     PSX_TIMED("k_integ_crop", st, k_integ_crop<<<ew_grid((int64_t)n * m, 256), 256, 0, st>>>(Z, phi, n, m, norm));
     return launch_check("k_integ_crop");
+}
+
+int psx_paganin_f32(psx_integrate_plan *plan, int B, const float *const *image, const float *const *white,
+                    const double *alpha, const double *mu, float *const *contact, float *const *thickness, void *stream) {
+    PSX_REQUIRE(plan != nullptr, "psx_paganin_f32: null plan");
+    PSX_REQUIRE(B >= 1 && B <= PSX_MAX_PAGANIN, "psx_paganin_f32: B=%d images outside [1,%d]", B, PSX_MAX_PAGANIN);
+    PSX_REQUIRE(image && alpha && mu, "psx_paganin_f32: null image, alpha or mu array");
+    PSX_REQUIRE(contact || thickness, "psx_paganin_f32: neither contact nor thickness asked for");
+    for (int b = 0; b < B; ++b) {
+        PSX_REQUIRE(image[b] != nullptr, "psx_paganin_f32: image %d is null", b);
+        PSX_REQUIRE(std::isfinite(alpha[b]) && alpha[b] >= 0.0, "psx_paganin_f32: alpha[%d]=%g is not a finite value >= 0", b, alpha[b]);
+        PSX_REQUIRE(std::isfinite(mu[b]) && mu[b] > 0.0, "psx_paganin_f32: mu[%d]=%g is not a finite value > 0", b, mu[b]);
+        PSX_REQUIRE((contact && contact[b]) || (thickness && thickness[b]), "psx_paganin_f32: image %d has neither output", b);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int n = plan->n, m = plan->m;
+    const int64_t N = 4 * (int64_t)n * m;
+    float2 *const Z = plan->Z.get();
+    const double norm = 1.0 / (double)N;
+    for (int b0 = 0; b0 < B; b0 += 2) {
+        PagPair pp = {};
+        for (int s = 0; s < 2; ++s) {
+            const int b = b0 + s;
+            const bool on = b < B;
+            pp.I[s] = on ? image[b] : nullptr;
+            pp.W[s] = on && white ? white[b] : nullptr;
+            pp.contact[s] = on && contact ? contact[b] : nullptr;
+            pp.thickness[s] = on && thickness ? thickness[b] : nullptr;
+            pp.alpha[s] = on ? alpha[b] : 0.0;
+            pp.mu[s] = on ? mu[b] : 1.0;
+        }
+        PSX_TIMED("k_pag_pack", st, k_pag_pack<<<ew_grid((int64_t)n * m, 256), 256, 0, st>>>(pp, Z, n, m));
+        if (int rc = launch_check("k_pag_pack")) return rc;
+        if (int rc = plan->fft.execute(FftPlan::FWD, Z, st, "rocfft_paganin_forward")) return rc;
+        PSX_TIMED("k_pag_filter", st, k_pag_filter<<<ew_grid(N, 256), 256, 0, st>>>(Z, n, m, pp.alpha[0], pp.alpha[1]));
+        if (int rc = launch_check("k_pag_filter")) return rc;
+        if (int rc = plan->fft.execute(FftPlan::INV, Z, st, "rocfft_paganin_inverse")) return rc;
+        PSX_TIMED("k_pag_crop", st, k_pag_crop<<<ew_grid((int64_t)n * m, 256), 256, 0, st>>>(pp, Z, n, m, norm));
+        if (int rc = launch_check("k_pag_crop")) return rc;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
     python -m paresis_amd.main [--experiment NAME] [--type RayT|Fresnel] [--oversampling N] [--points N]
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
                                [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa|umpa-df --window W --search M]]
+                               [--retrieve-propagation [--material NAME]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
@@ -12,7 +13,10 @@ after the gather (paresis_amd/retrieval.py) and writes retrieval/{transmission,d
 directory.  --dark-field (needs 4 positions or more) retrieves with LCS-DF and adds df_ and scattering_<expID><fmt>.
 --method umpa (1 position or more) retrieves with UMPA, for displacements of up to --search pixels, and adds
 residual_<expID><fmt>; it takes neither --dark-field nor --max-shift.  --method umpa-df (the same rules) also fits UMPA's
-dark-field term and adds visibility_<expID><fmt>.
+dark-field term and adds visibility_<expID><fmt>.  --retrieve-propagation (independent of --retrieve; any number of
+positions) runs Paganin's single-material retrieval of each bin's propagation image over its flat field on rank 0 and writes
+propag/retrieval/{contact,thickness,phi}_<expID><fmt> under the bin's directory; --material names the sample material whose
+delta and beta the filter takes (default: the sample of interest's first).
 """
 import argparse
 import datetime
@@ -23,7 +27,7 @@ import numpy as np
 
 
 def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
-        method='lcs', window=2, search=3):
+        method='lcs', window=2, search=3, propagation=False, material=None):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
@@ -31,7 +35,15 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     <bin dir>/retrieval/.  exp_dict['retrievalParams'] then holds the parameters it used.  dark_field (with retrieve, 4
     positions or more): LCS-DF, the maps gain df and scattering (retrieval.retrieve(..., dark_field=True)).  method='umpa'
     (with retrieve, 1 position or more; window, search as retrieval.umpa): UMPA instead of LCS, the maps gain residual;
-    method='umpa-df' (the same rules): UMPA with its dark-field term, the maps gain visibility and residual."""
+    method='umpa-df' (the same rules): UMPA with its dark-field term, the maps gain visibility and residual.
+
+    propagation (extension, independent of retrieve, any number of positions): rank 0 also retrieves every bin's
+    propagation image over its flat field with Paganin's filter (retrieval.retrieve_propagation with the experiment's
+    parameters and the delta, beta of `material` -- retrieval.propagation_material: by default the sample of interest's
+    first); with save, contact, thickness and phi go to <bin dir>/propag/retrieval/.  exp_dict['propagationParams'] then
+    holds the parameters, the material and the delta, beta, alpha and mu it used."""
+    if material is not None and not propagation:
+        raise ValueError("material is an option of propagation")
     if retrieve and method != "lcs":
         from .retrieval import check_method
         check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
@@ -59,6 +71,9 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     # as it is
     print("\n\nINITIALIZING EXPERIMENT PARAMETERS AND GEOMETRIES")
     experiment = Experiment(exp_dict)
+    if propagation:
+        from .retrieval import propagation_material
+        material = propagation_material(experiment, material)       # a wrong name fails before the images are computed
     sim = exp_dict['simulation_type']
     root = exp_dict['filepath'] + ('Fresnel_' if sim == "Fresnel" else 'RayTracing_') + str(exp_dict['expID']) + '/'
     if save:
@@ -157,6 +172,16 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
         if save:
             for ibin in sorted(retrieved):
                 retrieval.save_retrieval(retrieved[ibin], paths[ibin], exp_dict['expID'], saving_format)
+    if rank == 0 and propagation:
+        from . import materials, retrieval
+        params = retrieval.params_from_experiment(experiment)
+        delta, beta = materials.delta_beta(material, params['energy_keV'])      # every bin at the run's mean energy, as retrieve
+        alpha, mu = retrieval.paganin_alpha(delta, beta, **params)
+        propagated = retrieval.retrieve_propagation(gathered, params, (delta, beta))
+        exp_dict['propagationParams'] = dict(params, material=material, delta=delta, beta=beta, alpha=alpha, mu=mu)
+        if save:
+            for ibin in sorted(propagated):
+                retrieval.save_propagation(propagated[ibin], paths[ibin], exp_dict['expID'], saving_format)
     dist.finish()
     print("\nfini")
     return gathered
@@ -185,6 +210,11 @@ def main(argv=None):
                     help="speckle-tracking phase retrieval of every bin after the run (3 positions or more): "
                          "retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's directory")
     retrieval.add_retrieval_options(ap)          # --max-shift, --dark-field, --method, --window, --search: options of --retrieve
+    ap.add_argument("--retrieve-propagation", action="store_true",
+                    help="Paganin retrieval of every bin's propagation image after the run (any --points): "
+                         "propag/retrieval/{contact,thickness,phi}_<expID><fmt> under each bin's directory")
+    ap.add_argument("--material", default=None,
+                    help="--retrieve-propagation: the sample material the filter assumes (default: the sample's first)")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -202,8 +232,11 @@ def main(argv=None):
         ap.error("--dark-field is an option of --retrieve")
     if a.dark_field and a.points < floor[True]:
         ap.error("--dark-field needs --points %d or more" % floor[True])
+    if a.material is not None and not a.retrieve_propagation:
+        ap.error("--material is an option of --retrieve-propagation")
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
-        dark_field=a.dark_field, method=a.method, window=a.window, search=a.search)
+        dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
+        material=a.material)
 
 
 if __name__ == "__main__":

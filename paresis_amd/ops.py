@@ -1125,3 +1125,87 @@ class IntegratePlan(_Plan):
             check(lib().psx_integrate_f32(self._h, _ptr(gx), _ptr(gy), c_double(scale), _ptr(out), _stream()),
                   "psx_integrate_f32")
         return out
+
+    def paganin(self, images, whites, alpha, mu, out=None):
+        """ops.paganin on this plan."""
+        return paganin(images, whites, alpha, mu, self, out=out)
+
+
+def _image_list(imgs, name, B=None):
+    """B images as a list of 2-D tensors from a [B, n, m] tensor or a sequence of B [n, m] tensors (ops.lcs's two forms);
+    entries of a sequence may be None.  Counts only: dtypes, shapes and devices are the caller's to check."""
+    if isinstance(imgs, torch.Tensor):
+        if imgs.dim() != 3:
+            raise PsxError("%s must be [B, n, m] or a sequence of B [n, m] images; got shape %s" % (name, tuple(imgs.shape)))
+        imgs = [imgs[b] for b in range(imgs.shape[0])]
+    imgs = list(imgs)
+    if B is None and not 1 <= len(imgs) <= _lib.PSX_MAX_PAGANIN:
+        raise PsxError("%s: B=%d images outside [1, %d]" % (name, len(imgs), _lib.PSX_MAX_PAGANIN))
+    if B is not None and len(imgs) != B:
+        raise PsxError("%s holds %d images, images %d" % (name, len(imgs), B))
+    return imgs
+
+
+def _per_image(v, name, B):
+    """A scalar, or a sequence of B of them -> B floats."""
+    try:
+        v = [float(v)] * B if not hasattr(v, "__len__") else [float(x) for x in v]
+    except (TypeError, ValueError):
+        raise PsxError("%s must be a number or a sequence of %d numbers, got %r" % (name, B, v))
+    if len(v) != B:
+        raise PsxError("%s must hold one value per image (%d), got %d" % (name, B, len(v)))
+    return v
+
+
+def paganin(images, whites, alpha, mu, plan, out=None):
+    """Paganin's single-material phase retrieval of B propagation images (psx_paganin_f32; the contract is in
+    include/paresis_hip.h): images, a [B, n, m] float32 tensor in HBM or a sequence of B n x m ones (ops.lcs's input forms),
+    B in [1, PSX_MAX_PAGANIN]; whites, the flat fields in the same forms, None for none (entries of a sequence may be None);
+    alpha (>= 0, detector px^2) and mu (> 0, 1/m), one number for all images or B of them; plan, an IntegratePlan of the
+    images' shape, whose buffer and transforms the call uses -> (contact, thickness), two [B, n, m] float32 tensors:
+    contact = exp(-mu*t) as retrieved, thickness = t in metres.  out: (contact, thickness) to write into, each a
+    [B, n, m] tensor, a sequence of B n x m tensors, or None for a map that is not wanted (not both); they are returned as
+    given.  Two images share one transform; calls on one plan are ordered on the current stream."""
+    I = _image_list(images, "images")
+    B = len(I)
+    W = [None] * B if whites is None else _image_list(whites, "whites", B)
+    alpha, mu = _per_image(alpha, "alpha", B), _per_image(mu, "mu", B)
+    for b in range(B):
+        if not (math.isfinite(alpha[b]) and alpha[b] >= 0.0):
+            raise PsxError("alpha must be finite and >= 0, got %r" % alpha[b])
+        if not (math.isfinite(mu[b]) and mu[b] > 0.0):
+            raise PsxError("mu must be finite and > 0, got %r" % mu[b])
+    if not isinstance(plan, IntegratePlan):
+        raise PsxError("plan must be an ops.IntegratePlan, got %r" % type(plan))
+    shape = (plan.n, plan.m)
+    for nm, imgs in (("images", I), ("whites", W)):
+        for b, t in enumerate(imgs):
+            if t is None and nm == "whites":
+                continue
+            _need(t, torch.float32, "%s[%d]" % (nm, b), shape)
+            if t.device != plan.device:
+                raise PsxError("%s[%d] is on %s, the plan on %s" % (nm, b, t.device, plan.device))
+    if out is None:
+        out = tuple(torch.empty((B,) + shape, dtype=torch.float32, device=plan.device) for _ in range(2))
+    else:
+        out = tuple(out)
+        if len(out) != 2:
+            raise PsxError("out must hold two entries (contact, thickness), either of which may be None")
+        if out[0] is None and out[1] is None:
+            raise PsxError("out asks for neither contact nor thickness")
+    lists = []
+    for nm, o in zip(("contact", "thickness"), out):
+        if o is None:
+            lists.append(None)
+            continue
+        lst = _image_list(o, "out " + nm, B)
+        for b, t in enumerate(lst):
+            _need(t, torch.float32, "out %s[%d]" % (nm, b), shape)
+            if t.device != plan.device:
+                raise PsxError("out %s[%d] is on %s, the plan on %s" % (nm, b, t.device, plan.device))
+        lists.append(lst)
+    with torch.cuda.device(plan.device):
+        check(lib().psx_paganin_f32(plan._h, B, _ptrs(I), None if whites is None else _ptrs(W), (c_double * B)(*alpha),
+                                    (c_double * B)(*mu), None if lists[0] is None else _ptrs(lists[0]),
+                                    None if lists[1] is None else _ptrs(lists[1]), _stream()), "psx_paganin_f32")
+    return out

@@ -21,6 +21,10 @@ module turns them into the sample's transmission, its refraction (displacement) 
     phase_gradient(...)      displacement -> phase gradient in radians per detector pixel
     integrate(gx, gy)        Frankot-Chellappa (IEEE PAMI 10, 1988) with mirror extension -> phase (zero mean)
     retrieve(results, ...)   all of it for every bin of main.run's {position: (Sample, Reference, ...)}
+    paganin(image, white)    propagation-based imaging's answer from the same run: Paganin's single-distance, single-material
+                             filter (Paganin et al., J. Microsc. 206, 33, 2002) of the propagation image (the sample
+                             without the membrane) over the flat field -> contact image, thickness and phase
+    retrieve_propagation(results, ...)   paganin for every bin of main.run's position 0 (its Propag and White stacks)
 
 All steps are HIP kernels (csrc/retrieve.hip, csrc/umpa.hip; the integration's transforms are rocFFT); nothing runs on the host but
 argument checks.  Command line, for a run already on disk (main.py's layout):
@@ -33,6 +37,12 @@ writes retrieval/{transmission,dx,dy,phi}_<expID><fmt> under each bin's director
 only transmission, dx and dy.  --dark-field (4 positions or more) adds df, and scattering with the physical parameters.
 --method umpa (1 position or more; no --dark-field, no --max-shift) tracks with UMPA and adds residual; --method umpa-df
 (the same rules) also fits UMPA's dark-field term and adds visibility.
+
+    python -m paresis_amd.retrieval RUN_DIR --propagation --delta D --beta B --energy KEV --pixel-um P --distance Z
+                                            --magnification M [--format .tif]
+
+writes propag/retrieval/{contact,thickness,phi}_<expID><fmt> under each bin's directory from its propag/PropagImage_ and
+White_ pair (paganin; delta, beta: the sample's single material at --energy).  It takes none of the tracker options.
 """
 import argparse
 import collections
@@ -170,6 +180,131 @@ def phase_gradient(dx, dy, energy_keV, pixel_um, distance_m, magnification):
     return dx * c, dy * c
 
 
+def paganin_alpha(delta, beta, energy_keV, pixel_um, distance_m, magnification):
+    """(alpha, mu) of Paganin's filter 1/(1 + alpha*k^2), k in radians per detector pixel: mu = 2*k0*beta (1/m) and
+    alpha = z*M*delta/(mu*p^2) (detector px^2).  Needs no GPU.
+
+    A single material of thickness t attenuates by exp(-mu*t), mu = 2*k0*beta, and shifts the phase by phi = -k0*delta*t,
+    k0 = getk(E) (the chain's constants; Sample.setWave's -k*delta*t and -k*beta*t on the amplitude).  Propagating the wave
+    over an effective distance d on a grid of spacing h, the transport-of-intensity equation gives, for that material,
+    I/I0 = (1 - (d*delta/mu)*lap) exp(-mu*t), lap the Laplacian in metres: in pixels of size h the operator is
+    1 + alpha_h*k^2 with alpha_h = d*delta/(mu*h^2).  The chain propagates the cone beam as a parallel one over d = z/M
+    on the study grid h = p/(ov*M) (z = distObjectToDetector, M the object->detector magnification it passes, p the
+    detector pixel, ov the oversampling), so alpha_h = (z/M)*delta*ov^2*M^2/(mu*p^2) study px^2; the detector bins ov x ov
+    study pixels into one, and a frequency per detector pixel is ov times the frequency per study pixel, so
+    alpha = alpha_h/ov^2 = z*M*delta/(mu*p^2) detector px^2; ov drops out, as in gradient_scale.  delta, beta: the
+    material's index decrements at energy_keV; pixel_um: the detector pixel; distance_m: distObjectToDetector;
+    magnification: exp_dict['magnification']."""
+    delta, beta = float(delta), float(beta)
+    p = float(pixel_um) * 1e-6
+    z, M = float(distance_m), float(magnification)
+    if not (delta >= 0.0 and np.isfinite(delta)):
+        raise ValueError("delta must be finite and >= 0, got %r" % delta)
+    if not (beta > 0.0 and np.isfinite(beta)):
+        raise ValueError("beta must be finite and > 0 (a material that does not absorb has no Paganin filter), got %r" % beta)
+    if not (float(energy_keV) > 0.0 and p > 0.0 and z >= 0.0 and M > 0.0):
+        raise ValueError("energy_keV, pixel_um and magnification must be > 0 and distance_m >= 0")
+    mu = 2.0 * getk(float(energy_keV) * 1e3) * beta
+    return z * M * delta / (mu * p * p), mu
+
+
+def _per_image(v, B):
+    return [float(v)] * B if np.ndim(v) == 0 else [float(x) for x in v]
+
+
+def paganin(image, white=None, *, delta, beta, energy_keV, pixel_um, distance_m, magnification):
+    """Paganin's single-distance, single-material retrieval of a propagation image (ops.paganin, psx_paganin_f32; the
+    filter's units: paganin_alpha) -> {'contact', 'thickness', 'phi'}, float32 on the image's device:
+    contact = exp(-mu*t) as it would be measured at the sample (I/I0 with the propagation fringes filtered out),
+    thickness = t of the material in metres, phi = -k*delta*t in radians (k = getk(E), Sample.setWave's phase).
+    image: one n x m float32 CUDA tensor -> n x m maps; or a [B, n, m] stack / a sequence of B images -> [B, n, m] maps,
+    with delta, beta and energy_keV one number each or B of them (the bins of a run differ in energy).  white: the flat
+    field(s) in the same form, None when the image is already I/I0.  The plan is retrieval's own per (device, shape):
+    a shape shared with integrate() uses one buffer."""
+    import torch
+    from . import ops
+    single = isinstance(image, torch.Tensor) and image.dim() == 2
+    images = [image] if single else image
+    whites = [white] if single and white is not None else white
+    I = ops._image_list(images, "image")
+    B = len(I)
+    try:
+        d, b, e = _per_image(delta, B), _per_image(beta, B), _per_image(energy_keV, B)
+    except (TypeError, ValueError):
+        raise ValueError("delta, beta and energy_keV must be numbers or sequences of %d numbers" % B)
+    if not len(d) == len(b) == len(e) == B:
+        raise ValueError("delta, beta and energy_keV must hold one value per image (%d), got %d, %d, %d" % (B, len(d), len(b), len(e)))
+    am = [paganin_alpha(d[i], b[i], e[i], pixel_um, distance_m, magnification) for i in range(B)]
+    for i, t in enumerate(I):
+        ops._need(t, torch.float32, "image[%d]" % i)          # before a plan is looked up on the image's device
+    n, m = I[0].shape
+    contact, thickness = ops.paganin(I, whites, [a for a, _ in am], [u for _, u in am], _plan(I[0].device, n, m))
+    c = torch.tensor([-getk(e[i] * 1e3) * d[i] for i in range(B)], dtype=torch.float32, device=thickness.device)
+    r = {'contact': contact, 'thickness': thickness, 'phi': thickness * c[:, None, None]}
+    return {k: v[0] for k, v in r.items()} if single else r
+
+
+PROPAGATION_MAPS = ("contact", "thickness", "phi")
+
+
+def propagation_material(experiment, material=None):
+    """The single material Paganin's filter assumes, of an Experiment: by default the sample of interest's first one;
+    a name that is not among the sample's materials is a ValueError.  Needs no GPU."""
+    mats = list(experiment.mySampleofInterest.myMaterials)
+    if material is None:
+        if not mats:
+            raise ValueError("the sample of interest names no material")
+        return mats[0]
+    if material not in mats:
+        raise ValueError("material %r is not one of the sample of interest's (%s)" % (material, ", ".join(map(str, mats))))
+    return material
+
+
+def retrieve_propagation(results, params, delta_beta, bins=None, energies=None, device=None):
+    """Paganin retrieval of every bin of a run's propagation image: results = main.run's {position: (Sample, Reference, Propag,
+    White, ...)}, of which position 0's [nbins, n, m] Propag and White stacks are read (host or device; host stacks are
+    uploaded once) -> {bin: {'contact', 'thickness', 'phi'}}, device tensors.  params: params_from_experiment's dict.
+    delta_beta: (delta, beta) of the sample's single material, or the material's name, resolved at each bin's energy
+    through materials.delta_beta.  bins, energies: as retrieve() -- without energies every bin uses params['energy_keV'],
+    which is right for one bin only.  All bins go through one ops.paganin call per PSX_MAX_PAGANIN of them."""
+    if 0 not in results or len(results[0]) < 4:
+        raise ValueError("results hold no propagation image: position 0's (Sample, Reference, Propag, White) is needed")
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    P = _stack(results, [0], 2, dev)[0]
+    W = _stack(results, [0], 3, dev)[0]
+    bins = list(range(P.shape[0])) if bins is None else [int(b) for b in bins]
+    if energies is not None and len(energies) != len(bins):
+        raise ValueError("energies must hold one value per retrieved bin (%d), got %d" % (len(bins), len(energies)))
+    e = [float(params['energy_keV'])] * len(bins) if energies is None else [float(v) for v in energies]
+    if isinstance(delta_beta, str):
+        from . import materials
+        db = [materials.delta_beta(delta_beta, v) for v in e]
+    else:
+        db = [(float(delta_beta[0]), float(delta_beta[1]))] * len(bins)
+    out = {}
+    for i0 in range(0, len(bins), _lib.PSX_MAX_PAGANIN):
+        sl = slice(i0, i0 + _lib.PSX_MAX_PAGANIN)
+        r = paganin([P[b] for b in bins[sl]], [W[b] for b in bins[sl]], delta=[d for d, _ in db[sl]], beta=[b for _, b in db[sl]],
+                    energy_keV=e[sl], pixel_um=params['pixel_um'], distance_m=params['distance_m'],
+                    magnification=params['magnification'])
+        for i, b in enumerate(bins[sl]):
+            out[b] = {k: r[k][i] for k in PROPAGATION_MAPS}
+    return out
+
+
+def save_propagation(r, directory, exp_id, fmt):
+    """Write one bin's Paganin maps as directory/propag/retrieval/<name>_<exp_id><fmt> (name: contact, thickness, phi)."""
+    from .InputOutput.pagailleIO import save_image
+    d = os.path.join(directory, "propag", "retrieval")
+    os.makedirs(d, exist_ok=True)
+    paths = []
+    for name in PROPAGATION_MAPS:
+        paths.append(os.path.join(d, "%s_%s%s" % (name, exp_id, fmt)))
+        save_image(r[name].detach().cpu().numpy(), paths[-1])
+    return paths
+
+
 def params_from_experiment(experiment):
     """The physical parameters of an Experiment's retrieval: {'energy_keV': exp_dict['meanEnergy'] (known after a run),
     'pixel_um': the detector pixel, 'distance_m': distObjectToDetector, 'magnification': exp_dict['magnification']}."""
@@ -286,6 +421,60 @@ def discover(run_dir, min_positions=3):
     return found
 
 
+_PROPAG = re.compile(r"^PropagImage_(.+)_(\.[A-Za-z0-9]+)$")
+_WHITE = re.compile(r"^White_(.+)_(\.[A-Za-z0-9]+)$")
+
+
+def discover_propagation(run_dir):
+    """main.run's layout under run_dir -> [(bin_dir, exp_id, fmt, propag_path, white_path)], one entry per bin directory
+    (discover's candidates) that holds propag/PropagImage_<id>_<fmt> and White_<id>_<fmt>.  Raises ValueError when a
+    propagation image has no flat field (or the reverse), when one directory holds several runs or formats, or when
+    nothing is found.  Needs no GPU."""
+    run_dir = os.path.abspath(run_dir)
+    cands = [run_dir] + sorted(os.path.join(run_dir, d) for d in os.listdir(run_dir)
+                               if re.match(r"^\d+_\d+kev$", d) and os.path.isdir(os.path.join(run_dir, d)))
+    found = []
+    for d in cands:
+        side = []
+        for sub, pat in ((os.path.join(d, "propag"), _PROPAG), (d, _WHITE)):
+            files = {}
+            for f in sorted(os.listdir(sub)) if os.path.isdir(sub) else []:
+                mt = pat.match(f)
+                if mt and os.path.isfile(os.path.join(sub, f)):
+                    files[(mt.group(1), mt.group(2))] = os.path.join(sub, f)
+            side.append(files)
+        pg, wh = side
+        for key in sorted(set(pg) ^ set(wh)):
+            raise ValueError("%s: %s of run %s (%s) has no %s partner"
+                             % (d, "propagation image" if key in pg else "flat field", key[0], key[1],
+                                "flat field (White_)" if key in pg else "propagation image (propag/PropagImage_)"))
+        if not pg:
+            continue
+        if len(pg) > 1:
+            raise ValueError("%s holds several runs or formats %s: give one run's directory" % (d, sorted(pg)))
+        (exp_id, fmt), = pg
+        found.append((d, exp_id, fmt, pg[(exp_id, fmt)], wh[(exp_id, fmt)]))
+    if not found:
+        raise ValueError("no propag/PropagImage_ and White_ images of main.run's layout under %s" % run_dir)
+    return found
+
+
+def retrieve_propagation_run_dir(run_dir, params, delta, beta, fmt=None):
+    """discover_propagation() + paganin + save_propagation for every bin directory; returns the paths.  params:
+    params_from_experiment's four; delta, beta: the sample's material at params['energy_keV']."""
+    import torch
+    from .InputOutput.pagailleIO import openImage
+    found = discover_propagation(run_dir)                          # before the device: a wrong directory needs no GPU
+    written = []
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for d, exp_id, in_fmt, pg, wh in found:
+        P = torch.from_numpy(np.asarray(openImage(pg), dtype=np.float32)[None]).to(dev)
+        W = torch.from_numpy(np.asarray(openImage(wh), dtype=np.float32)[None]).to(dev)
+        res = retrieve_propagation({0: (None, None, P, W)}, params, (delta, beta))[0]
+        written += save_propagation(res, d, exp_id, fmt or in_fmt)
+    return written
+
+
 def _first_floor(method):
     """The fewest positions discover() asks for: the method's without dark field (an unknown method is retrieve()'s to report,
     after discovery as ever: LCS's floor)."""
@@ -353,10 +542,30 @@ def main(argv=None):
     ap.add_argument("--distance", type=float, default=None, help="object-to-detector distance, metres")
     ap.add_argument("--magnification", type=float, default=None, help="exp_dict['magnification']")
     ap.add_argument("--format", default=None, help="output format (.tif, .edf, .npy); default: the input's")
+    ap.add_argument("--propagation", action="store_true",
+                    help="Paganin retrieval of each bin's propagation image over its flat field instead of speckle tracking: "
+                         "propag/retrieval/{contact,thickness,phi}; needs --delta, --beta and the four physical parameters")
+    ap.add_argument("--delta", type=float, default=None, help="--propagation: the sample material's delta at --energy")
+    ap.add_argument("--beta", type=float, default=None, help="--propagation: the sample material's beta at --energy")
     add_retrieval_options(ap)
     a = ap.parse_args(argv)
-    check_retrieval_options(ap, a)
     phys = (a.energy, a.pixel_um, a.distance, a.magnification)
+    if a.propagation:
+        if any(getattr(a, k) != ap.get_default(k) for k in ("max_shift", "dark_field", "method", "window", "search")):
+            ap.error("--propagation takes none of the tracker options (--max-shift, --dark-field, --method, --window, --search)")
+        if a.delta is None or a.beta is None or any(v is None for v in phys):
+            ap.error("--propagation needs --delta, --beta, --energy, --pixel-um, --distance and --magnification")
+        params = {'energy_keV': a.energy, 'pixel_um': a.pixel_um, 'distance_m': a.distance, 'magnification': a.magnification}
+        try:
+            paganin_alpha(a.delta, a.beta, a.energy, a.pixel_um, a.distance, a.magnification)
+        except ValueError as exc:
+            ap.error(str(exc))
+        for p in retrieve_propagation_run_dir(a.run_dir, params, a.delta, a.beta, fmt=a.format):
+            print(p)
+        return 0
+    if a.delta is not None or a.beta is not None:
+        ap.error("--delta and --beta are options of --propagation")
+    check_retrieval_options(ap, a)
     if any(v is not None for v in phys) and any(v is None for v in phys):
         ap.error("--energy, --pixel-um, --distance and --magnification go together")
     params = None if phys[0] is None else {'energy_keV': a.energy, 'pixel_um': a.pixel_um, 'distance_m': a.distance,

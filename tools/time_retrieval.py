@@ -1,6 +1,6 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
@@ -14,6 +14,10 @@ per wave64 instruction and SIMD).  Its cases end with time(w = 4)/time(w = 1): t
 direct ones would give about 9.  k_umpa_df (its dark-field variant, ops.umpa_df with the means given, so that nothing
 synchronises) writes 5 maps and is timed in the same process, alternating with k_umpa launch by launch on the same inputs: two
 box passes more in the prologue against (2s+1)^2 in the search, and a 2 x 2 solve per candidate.
+
+--paganin times psx_paganin_f32 alone (B images of one shape with their flat fields, both maps): per pair of images the pack
+reads 4 n x m float32 images and writes the extended grid, the filter reads and writes it, the crop reads its corner and writes
+4 maps; the two rocFFT transforms are the integration's.
 """
 import argparse
 import ctypes
@@ -122,12 +126,45 @@ def umpa_case(n, m, K, w, s, reps):
     return t
 
 
+def paganin_case(n, m, B, reps):
+    g = torch.Generator(device="cuda").manual_seed(n + B)
+    W = 1e4 * (1 + 0.1 * torch.rand((B, n, m), device="cuda", generator=g))
+    I = W * (1 + 0.3 * (torch.rand((B, n, m), device="cuda", generator=g) - 0.5))
+    outs = (torch.empty((B, n, m), device="cuda"), torch.empty((B, n, m), device="cuda"))
+    plan = retrieval._plan(I.device, n, m)
+    for _ in range(3):
+        ops.paganin(I, W, 3.0, 22.0, plan, out=outs)
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        ops.paganin(I, W, 3.0, 22.0, plan, out=outs)
+    torch.cuda.synchronize()
+    s = summary()
+    lib().psx_profile_enable(0)
+    pairs = (B + 1) // 2
+    per = {k: v[1] / (reps * pairs) * 1e3 for k, v in s.items()}       # us per pair of images
+    grid = 4.0 * n * m * 8
+    price = {"k_pag_pack": 16.0 * n * m + grid, "k_pag_filter": 2 * grid, "k_pag_crop": grid / 4 + 16.0 * n * m}
+    kern = sum(per[k] for k in price)
+    fft = sum(v for k, v in per.items() if k.startswith("rocfft_paganin"))
+    print("%dx%d B=%d  paganin per pair %.1f us = kernels %.1f us + rocFFT %.1f us (%s)"
+          % (n, m, B, kern + fft, kern, fft, ", ".join("%s %.1f" % (k, v) for k, v in per.items() if k.startswith("rocfft"))))
+    for k, b in price.items():
+        print("    %s %.1f us  price %.1f MB (%.1f us at 8 TB/s) = %.2f of 8 TB/s" % (k, per[k], b / 1e6, b / PEAK * 1e6,
+                                                                                        b / (per[k] * 1e-6) / PEAK))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--umpa-only", action="store_true")
+    ap.add_argument("--paganin", action="store_true", help="time psx_paganin_f32 only")
     a = ap.parse_args()
+    if a.paganin:
+        for n, m, B in ((2048, 2048, 2), (2048, 2048, 8), (200, 200, 2)):
+            paganin_case(n, m, B, a.reps)
+        return
     for n, m, K in () if a.umpa_only else ((2048, 2048, 16), (2048, 2048, 64), (200, 200, 12)):
         case(n, m, K, a.reps, a.host)
     umpa_case(2048, 2048, 16, 2, 3, a.reps)

@@ -460,6 +460,39 @@ int psx_integrate_f32(psx_integrate_plan *plan, const float *gx, const float *gy
 int psx_paganin_f32(psx_integrate_plan *plan, int B, const float *const *image, const float *const *white,
                     const double *alpha, const double *mu, float *const *contact, float *const *thickness, void *stream);
 
+/* ---- filtered back-projection (parallel beam) of a stack of projections: sinogram -> volume ----------------------------
+ * sino [A][n][m] float32: A projections, each an n x m map; axis 0 (n) runs along the rotation axis, so detector row r of all
+ * projections is one slice, axis 1 (m) across it.  theta: HOST array of A finite angles in degrees (any values: negative,
+ * >= 180, repeated); center: the detector column of the rotation axis (m / 2 rounded down is skimage radon's).
+ * vol [n][m][m] float32, vol[r][i][j]: slice row i, slice column j, the orientation of the slice radon projects.
+ * Filter, per line sino[a][r][:], P = max(64, 2^ceil(log2(2m))):
+ *   f[0] = 1/4, f[j] = -1/(pi*jj)^2 for odd jj = min(j, P - j), 0 otherwise;  H = 2*Re FFT_P(f), formed in float64 on the host;
+ *   PSX_FBP_HANN multiplies H by fftshift(hanning(P)), hanning(P)[n] = 0.5 - 0.5*cos(2 pi n/(P-1)); PSX_FBP_NONE: H = 1;
+ *   q = Re IFFT_P( FFT_P(line zero-padded to P) * H )[:m].  Two lines share one complex transform (rocFFT, single
+ *   precision): the real part of the filtered pair is that of a filter with the even part (H[k] + H[P-k])/2, which is what
+ *   the device multiplies by, so the two lines do not mix.  PSX_FBP_NONE copies the lines and runs no transform.
+ * Back-projection, h = m / 2 rounded down, c_a = cos(theta_a*pi/180), s_a = sin(theta_a*pi/180) in float64 on the host:
+ *   u = (j - h)*c_a - (i - h)*s_a + center in float64;  q(u) by linear interpolation between the samples with
+ *   q[-1] = q[m] = 0, and 0 for u <= -1 or u >= m (continuous in u, unlike np.interp(left=0, right=0));
+ *   vol[r][i][j] = pi/(2A) * sum_a q_{a,r}(u), accumulated in float32 in ascending a;
+ *   circle != 0: voxels with (i - h)^2 + (j - h)^2 > h^2 are 0.
+ * A plan fixes (A, m, theta, center, filter, circle) and owns the tables, the transform and the filtered sinogram of
+ * max_rows detector rows (0: as many as fit 256 MiB, at least 2, at most 64; otherwise rounded up to an even count):
+ * psx_fbp_f32 walks the n rows in blocks of that many, so the work buffer is bounded whatever n is;
+ * psx_fbp_plan_bytes reports it with rocFFT's.  A in [1, PSX_FBP_MAX_ANGLES], m in [2, PSX_FBP_MAX_M], n >= 1,
+ * |center| <= 2^20.  Calls on one plan are ordered on one stream: they share its buffer. */
+#define PSX_FBP_RAMP 0
+#define PSX_FBP_HANN 1
+#define PSX_FBP_NONE 2
+#define PSX_FBP_MAX_ANGLES 4096
+#define PSX_FBP_MAX_M 8192
+typedef struct psx_fbp_plan psx_fbp_plan;
+int psx_fbp_plan_create(int A, int m, const double *theta_deg, double center, int filter, int circle, int max_rows,
+                        psx_fbp_plan **plan);
+int psx_fbp_plan_destroy(psx_fbp_plan *plan);
+size_t psx_fbp_plan_bytes(const psx_fbp_plan *plan);
+int psx_fbp_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *stream);
+
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------------------------------------
  * psx_profile_enable(1) clears the log and makes every kernel launch of the library record a HIP event pair on the
  * stream it is launched on; psx_profile_summary() waits for the recorded events and writes one line per kernel,

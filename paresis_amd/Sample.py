@@ -81,6 +81,8 @@ class AnalyticalSample(Sample):
         self.beta = []
         self._dev_geometry = None
         self._dev_src = None
+        self.myAngle = 30          # projection angle (degrees) of generateContrastPhantom: the reference's constant (SAM:221);
+                                   # tomography.project / scan turn the phantom by setting it before getMyGeometry
 
     # ------------------------------------------------------------------------------------------ geometry
     def getMyGeometry(self, studyDimensions, studyPixelSize, oversamp, pointNum=0, number_of_positions=0):
@@ -109,7 +111,8 @@ class AnalyticalSample(Sample):
                 return
             if fn == "generateContrastPhantom":                                 # SAM:220-221, on the GPU
                 from .Samples.generateContrastPhantom import generateContrastPhantom
-                self.myGeometry, self.geom_parameters = generateContrastPhantom(dimX, dimY, studyPixelSize, angle=30)
+                self.myGeometry, self.geom_parameters = generateContrastPhantom(dimX, dimY, studyPixelSize,
+                                                                                   angle=getattr(self, "myAngle", 30))
                 return
             if fn == "loadSampleGeometryFromImages":                            # SAM:222-225
                 geom, self.geom_parameters = geometry.load_sample_geometry_from_images(self.myGeometryFolder, dimX, dimY,

@@ -16,6 +16,8 @@ PSX_MAX_LCS = 64
 PSX_MAX_UMPA_WINDOW = 8
 PSX_MAX_UMPA_SEARCH = 8
 PSX_MAX_PAGANIN = 64
+PSX_FBP_MAX_ANGLES, PSX_FBP_MAX_M = 4096, 8192
+FBP_FILTERS = {"ramp": 0, "hann": 1, "none": 2}      # PSX_FBP_RAMP / _HANN / _NONE
 PSX_PHANTOM_TUBES = 12
 PSX_MAX_DIST = 8
 PSX_MAX_POISSON = 8
@@ -24,7 +26,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class PsxError(RuntimeError):
@@ -109,6 +111,10 @@ PROTOTYPES = {
     "psx_integrate_plan_bytes": (c_size_t, [_vp]),
     "psx_integrate_f32": (c_int, [_vp, _vp, _vp, c_double, _vp, _vp]),
     "psx_paganin_f32": (c_int, [_vp, c_int, _vpp, _vpp, _dp, _dp, _vpp, _vpp, _vp]),
+    "psx_fbp_plan_create": (c_int, [c_int, c_int, _dp, c_double, c_int, c_int, c_int, _vpp]),
+    "psx_fbp_plan_destroy": (c_int, [_vp]),
+    "psx_fbp_plan_bytes": (c_size_t, [_vp]),
+    "psx_fbp_f32": (c_int, [_vp, _vp, c_int, _vp, _vp]),
     "psx_debug_stamps": (c_int, [_vp]),
     "psx_debug_switch": (c_int, [c_char_p, c_int]),
     "psx_debug_switches_active": (c_int, [ctypes.c_char_p, c_size_t]),

@@ -5,6 +5,7 @@
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
                                [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa|umpa-df --window W --search M]]
                                [--retrieve-propagation [--material NAME]]
+                               [--tomography A [--tomography-modality attenuation|phase]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
@@ -16,7 +17,12 @@ residual_<expID><fmt>; it takes neither --dark-field nor --max-shift.  --method 
 dark-field term and adds visibility_<expID><fmt>.  --retrieve-propagation (independent of --retrieve; any number of
 positions) runs Paganin's single-material retrieval of each bin's propagation image over its flat field on rank 0 and writes
 propag/retrieval/{contact,thickness,phi}_<expID><fmt> under the bin's directory; --material names the sample material whose
-delta and beta the filter takes (default: the sample of interest's first).
+delta and beta the filter takes (default: the sample of interest's first).  --tomography A (contrast-phantom samples only)
+then turns the phantom through A angles on [0, 180) degrees, runs the chain at each (paresis_amd/tomography.py scan),
+reconstructs by filtered back-projection on rank 0 and writes tomography/mu_<expID> (--tomography-modality attenuation,
+the default: 1/m, from -ln(Propag/White), any --points) or tomography/delta_<expID> (phase: from the retrieved phi, the
+rules and options of --retrieve) under each bin's directory: one [n, m, m] file for --format .npy, else a directory of
+slices.
 """
 import argparse
 import datetime
@@ -27,7 +33,7 @@ import numpy as np
 
 
 def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
-        method='lcs', window=2, search=3, propagation=False, material=None):
+        method='lcs', window=2, search=3, propagation=False, material=None, tomography=0, tomography_modality='attenuation'):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
@@ -41,7 +47,24 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     propagation image over its flat field with Paganin's filter (retrieval.retrieve_propagation with the experiment's
     parameters and the delta, beta of `material` -- retrieval.propagation_material: by default the sample of interest's
     first); with save, contact, thickness and phi go to <bin dir>/propag/retrieval/.  exp_dict['propagationParams'] then
-    holds the parameters, the material and the delta, beta, alpha and mu it used."""
+    holds the parameters, the material and the delta, beta, alpha and mu it used.
+
+    tomography = A > 0 (extension; the sample of interest must be the contrast phantom): after the run, rank 0 turns the
+    phantom through A angles on [0, 180), runs the chain at each (tomography.scan with tomography_modality; 'phase'
+    retrieves with method, max_shift, dark_field, window, search and needs their positions), reconstructs every bin
+    (tomography.reconstruct) and, with save, writes <bin dir>/tomography/{mu|delta}_<expID> (tomography.save_volume).
+    exp_dict['tomographyParams'] then holds the angles, the centre, the voxel size and the modality, and
+    exp_dict['tomographyVolumes'] the {bin: [n, m, m] device tensor} volumes."""
+    from . import tomography as tomo
+    if tomography_modality not in tomo.MODALITIES:
+        raise ValueError("tomography_modality must be one of %s, got %r" % (", ".join(tomo.MODALITIES), tomography_modality))
+    if tomography_modality != 'attenuation' and not tomography:
+        raise ValueError("tomography_modality is an option of tomography")
+    if int(tomography) < 0 or int(tomography) > _lib_max_angles():
+        raise ValueError("tomography takes 1 to %d angles, got %r" % (_lib_max_angles(), tomography))
+    if tomography and tomography_modality == 'phase':
+        from .retrieval import check_method
+        check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
     if material is not None and not propagation:
         raise ValueError("material is an option of propagation")
     if retrieve and method != "lcs":
@@ -74,6 +97,8 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     if propagation:
         from .retrieval import propagation_material
         material = propagation_material(experiment, material)       # a wrong name fails before the images are computed
+    if tomography:
+        tomo._phantom(experiment.mySampleofInterest)                # another sample fails before the images are computed
     sim = exp_dict['simulation_type']
     root = exp_dict['filepath'] + ('Fresnel_' if sim == "Fresnel" else 'RayTracing_') + str(exp_dict['expID']) + '/'
     if save:
@@ -182,9 +207,33 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
         if save:
             for ibin in sorted(propagated):
                 retrieval.save_propagation(propagated[ibin], paths[ibin], exp_dict['expID'], saving_format)
+    if rank == 0 and tomography:
+        angles = [180.0 * a / int(tomography) for a in range(int(tomography))]
+        options = {}
+        if tomography_modality == 'phase':
+            from .retrieval import TRACKERS
+            options = {'method': method, 'max_shift': max_shift, 'dark_field': dark_field, 'window': window, 'search': search}
+            keep = TRACKERS[(method, bool(dark_field))].options + ('method', 'dark_field')
+            options = {k: v for k, v in options.items() if k in keep}
+        scanned = tomo.scan(experiment, angles, modality=tomography_modality, **options)
+        volumes = tomo.reconstruct(scanned)
+        exp_dict['tomographyParams'] = {k: scanned[k] for k in ('angles', 'center', 'voxel_m', 'modality', 'energy_keV')}
+        if save:
+            nbin = len(volumes)
+            thresholds = [experiment.mySource.mySpectrum[0][0]] + list(experiment.myDetector.det_param['myBinsThersholds'])
+            for ibin in sorted(volumes):
+                p = root if nbin == 1 else f'{root}{"%2.2d" % thresholds[ibin]}_{"%2.2d" % thresholds[ibin + 1]}kev/'
+                tomo.save_volume(volumes[ibin], p + 'tomography/' + tomo.volume_name(tomography_modality) + '_' +
+                                 str(exp_dict['expID']), saving_format)
+        exp_dict['tomographyVolumes'] = volumes
     dist.finish()
     print("\nfini")
     return gathered
+
+
+def _lib_max_angles():
+    from ._lib import PSX_FBP_MAX_ANGLES
+    return PSX_FBP_MAX_ANGLES
 
 
 def main(argv=None):
@@ -215,6 +264,12 @@ def main(argv=None):
                          "propag/retrieval/{contact,thickness,phi}_<expID><fmt> under each bin's directory")
     ap.add_argument("--material", default=None,
                     help="--retrieve-propagation: the sample material the filter assumes (default: the sample's first)")
+    ap.add_argument("--tomography", type=int, default=0, metavar="A",
+                    help="contrast-phantom samples: scan A angles on [0, 180) after the run and write the filtered "
+                         "back-projection, tomography/{mu|delta}_<expID> under each bin's directory")
+    ap.add_argument("--tomography-modality", default="attenuation", choices=["attenuation", "phase"],
+                    help="--tomography: mu from -ln(Propag/White) (default), or delta from the retrieved phi (the rules and "
+                         "options of --retrieve)")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -222,8 +277,8 @@ def main(argv=None):
     if a.xml:
         exp_dict['xmlDir'] = a.xml
     os.makedirs(exp_dict['filepath'], exist_ok=True)
-    if a.method != "lcs" and not a.retrieve:
-        ap.error("--method is an option of --retrieve")
+    if a.method != "lcs" and not a.retrieve and a.tomography_modality != "phase":
+        ap.error("--method is an option of --retrieve and of --tomography-modality phase")
     retrieval.check_retrieval_options(ap, a)
     floor = {df: t.min_positions for (m, df), t in retrieval.TRACKERS.items() if m == a.method}
     if a.retrieve and a.points < floor[False]:
@@ -234,9 +289,13 @@ def main(argv=None):
         ap.error("--dark-field needs --points %d or more" % floor[True])
     if a.material is not None and not a.retrieve_propagation:
         ap.error("--material is an option of --retrieve-propagation")
+    if a.tomography < 0:
+        ap.error("--tomography takes a number of angles >= 1")
+    if a.tomography_modality != "attenuation" and not a.tomography:
+        ap.error("--tomography-modality is an option of --tomography")
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
-        material=a.material)
+        material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality)
 
 
 if __name__ == "__main__":

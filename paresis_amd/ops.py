@@ -1209,3 +1209,58 @@ def paganin(images, whites, alpha, mu, plan, out=None):
                                     (c_double * B)(*mu), None if lists[0] is None else _ptrs(lists[0]),
                                     None if lists[1] is None else _ptrs(lists[1]), _stream()), "psx_paganin_f32")
     return out
+
+
+# --------------------------------------------------------------------------------------- filtered back-projection
+class FbpPlan(_Plan):
+    """psx_fbp_plan (the contract is in include/paresis_hip.h): parallel-beam filtered back-projection of [A, n, m] sinograms
+    at the A angles `theta_deg` (degrees, any values) about detector column `center` (None: m // 2, radon's), with filter
+    'ramp', 'hann' or 'none', onto [n, m, m] volumes, zero outside the inscribed circle when `circle`.  The plan owns the
+    angle and filter tables, the rocFFT plans and the filtered sinogram of max_rows detector rows (0: the library's
+    choice), so n may differ from call to call; `bytes` reports them."""
+    _destroy = "psx_fbp_plan_destroy"
+
+    def __init__(self, theta_deg, m, center=None, filter="ramp", circle=True, max_rows=0, device=None):
+        try:
+            theta = [float(v) for v in theta_deg]
+        except (TypeError, ValueError):
+            raise PsxError("theta_deg must be a sequence of angles in degrees, got %r" % (theta_deg,))
+        if filter not in _lib.FBP_FILTERS:
+            raise PsxError("filter must be one of %s, got %r" % (sorted(_lib.FBP_FILTERS), filter))
+        self.theta, self.m, self.filter, self.circle = tuple(theta), int(m), filter, bool(circle)
+        self.center = float(self.m // 2 if center is None else center)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = c_void_p(None)
+        with torch.cuda.device(self.device):
+            check(lib().psx_fbp_plan_create(len(theta), self.m, (c_double * len(theta))(*theta), c_double(self.center),
+                                            _lib.FBP_FILTERS[filter], int(self.circle), int(max_rows), ctypes.byref(self._h)),
+                  "psx_fbp_plan_create")
+        self.bytes = lib().psx_fbp_plan_bytes(self._h)
+
+    def fbp(self, sino, out=None):
+        """ops.fbp on this plan."""
+        return fbp(sino, self, out=out)
+
+
+def fbp(sino, plan, out=None):
+    """Filtered back-projection (psx_fbp_f32): sino, an [A, n, m] float32 tensor in HBM (A, m the plan's; any n >= 1) ->
+    the [n, m, m] float32 volume, vol[r] the slice of detector row r.  out: a caller-owned [n, m, m] float32 tensor to write
+    into.  Calls on one plan are ordered on the current stream (they share its buffer)."""
+    if not isinstance(plan, FbpPlan):
+        raise PsxError("plan must be an ops.FbpPlan, got %r" % type(plan))
+    _need(sino, torch.float32, "sino")
+    if sino.dim() != 3 or sino.shape[0] != len(plan.theta) or sino.shape[2] != plan.m or sino.shape[1] < 1:
+        raise PsxError("sino has shape %s, the plan takes [%d, n >= 1, %d]" % (tuple(sino.shape), len(plan.theta), plan.m))
+    if sino.device != plan.device:
+        raise PsxError("sino is on %s, the plan on %s" % (sino.device, plan.device))
+    n = int(sino.shape[1])
+    shape = (n, plan.m, plan.m)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=plan.device)
+    else:
+        _need(out, torch.float32, "out", shape)
+        if out.device != plan.device:
+            raise PsxError("out is on %s, the plan on %s" % (out.device, plan.device))
+    with torch.cuda.device(plan.device):
+        check(lib().psx_fbp_f32(plan._h, _ptr(sino), n, _ptr(out), _stream()), "psx_fbp_f32")
+    return out

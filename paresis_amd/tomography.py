@@ -1,0 +1,208 @@
+"""Parallel-beam tomography of the contrast phantom: the inverse of the projections the package simulates and retrieves.
+
+    fbp(sinogram, angles_deg, ...)      filtered back-projection on the GPU (csrc/fbp.hip, ops.FbpPlan; the contract is in
+                                        include/paresis_hip.h): [A, n, m] maps, one per angle -> [n, m, m], a slice per
+                                        detector row.  The sinogram holds LINE INTEGRALS IN PIXELS of the slice's voxel: a
+                                        map in physical units (phi in radians, -ln T) gives the quantity per voxel length.
+    delta_volume(vol, energy_keV, voxel_m)   phi = -k * integral(delta) dl  ->  delta = -vol/(k*voxel), k = getk(E)
+    mu_volume(vol, voxel_m)                  -ln T = integral(mu) dl         ->  mu = vol/voxel (1/m)
+    project(sample, energy_keV, angles_deg, dims, pixel_um)   the phantom's ideal sinograms phi and -ln T on the study grid
+    scan(experiment, angles_deg, modality)                    the real chain once per angle -> sinograms per energy bin
+    rotation_center(experiment)                               the detector column of the rotation axis of such a scan
+    save_volume(vol, path, fmt)
+
+The beam is treated as parallel: no fan- or cone-beam weighting.  At the magnification of the shipped experiments
+(M ~ 1.03) that is the synchrotron case.  Only the contrast phantom (Samples/generateContrastPhantom.py) has a
+three-dimensional description -- 13 material discs on a slice, projected at Sample.myAngle -- so project and scan refuse
+every other sample.
+
+    python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase] ...
+"""
+import os
+
+import numpy as np
+
+from .getk import getk
+
+MODALITIES = ("attenuation", "phase")
+PHANTOM_FUNCTION = "generateContrastPhantom"
+_plans = {}
+
+
+def fbp(sinogram, angles_deg, center=None, filter='ramp', circle=True):
+    """Filtered back-projection of an [A, n, m] float32 CUDA tensor (or a sequence of A n x m maps, as retrieval.retrieve and
+    retrieval.paganin return them) taken at angles_deg (A angles in degrees, any values) -> the [n, m, m] float32 volume on
+    the same device: vol[r] is the slice of detector row r in the orientation of contrast_phantom_slices.  center: the
+    detector column of the rotation axis (None: m // 2, scikit-image radon's; rotation_center for a scan).  filter:
+    'ramp', 'hann' or 'none'.  circle: zero outside the inscribed circle.  One plan per (device, A, m, angles, center,
+    filter, circle) is kept for the process's lifetime."""
+    import torch
+    from . import ops
+    if not isinstance(sinogram, torch.Tensor):
+        sinogram = torch.stack(list(sinogram))
+    ops._need(sinogram, torch.float32, "sinogram")
+    if sinogram.dim() != 3:
+        raise ops.PsxError("sinogram must be [A, n, m], got shape %s" % (tuple(sinogram.shape),))
+    angles = tuple(float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel())
+    if len(angles) != sinogram.shape[0]:
+        raise ops.PsxError("sinogram holds %d projections, angles_deg %d" % (sinogram.shape[0], len(angles)))
+    m = int(sinogram.shape[2])
+    dev = sinogram.device
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = (index, len(angles), m, angles, float(m // 2 if center is None else center), str(filter), bool(circle))
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = ops.FbpPlan(angles, m, center=key[4], filter=filter, circle=circle,
+                                         device=torch.device("cuda", index))
+    return ops.fbp(sinogram, plan)
+
+
+def delta_volume(vol_phi, energy_keV, voxel_m):
+    """The refractive index decrement per voxel from the back-projection of a phase sinogram (radians): the chain's phase is
+    phi = -k*sum(delta*t) (Sample.setWaveRT), k = getk(E) with the chain's constants, so delta = -vol/(k*voxel_m)."""
+    return vol_phi * (-1.0 / (getk(float(energy_keV) * 1e3) * float(voxel_m)))
+
+
+def mu_volume(vol_logT, voxel_m):
+    """The linear attenuation coefficient (1/m) per voxel from the back-projection of a -ln T sinogram: vol/voxel_m."""
+    return vol_logT * (1.0 / float(voxel_m))
+
+
+def _phantom(sample):
+    if getattr(sample, "myGeometryFunction", "") != PHANTOM_FUNCTION:
+        raise ValueError("tomography needs a sample whose geometry function is %s (the only one with a three-dimensional "
+                         "description), got %r" % (PHANTOM_FUNCTION, getattr(sample, "myGeometryFunction", "")))
+    return sample
+
+
+def _turn(sample, angle, dims, pixel_um, ov=1):
+    sample.myAngle = float(angle)
+    sample.getMyGeometry(dims, pixel_um, ov)
+
+
+def project(sample, energy_keV, angles_deg, dims, pixel_um):
+    """The ideal sinograms of the contrast phantom `sample` (an AnalyticalSample with delta / beta at energy_keV) on a
+    dims = (dimX, dimY) grid of pixel_um pixels -> {'phi': [A, dimX, dimY] float32 (radians, -k*sum delta*t),
+    'logT': [A, dimX, dimY] float32 (-ln of the transmitted intensity, 2k*sum beta*t)}.  Per angle the sample is turned
+    (myAngle), its geometry rebuilt (psx_contrast_phantom_f32) and a unit intensity sent through setWaveRT: existing kernels
+    only.  The sample is left at its last angle."""
+    import torch
+    _phantom(sample)
+    dims = (int(dims[0]), int(dims[1]))
+    one = None
+    phi, logT = [], []
+    for angle in np.asarray(angles_deg, dtype=np.float64).ravel():
+        _turn(sample, angle, dims, pixel_um)
+        if one is None:
+            one = torch.ones(dims, dtype=torch.float32, device=sample.geometry_dev().device)
+        I, p, _ = sample.setWaveRT(one, energy_keV)
+        phi.append(p.to(torch.float32))
+        logT.append(-torch.log(I))
+    return {'phi': torch.stack(phi), 'logT': torch.stack(logT)}
+
+
+def rotation_center(experiment):
+    """The detector column of the rotation axis of a scan of `experiment`: (dimY // 2 - (ov - 1)/2)/ov, dimY the study
+    grid's axis-1 length.  Needs no GPU.
+
+    The phantom is projected with scikit-image radon's convention, whose axis is study column c0 = dimY // 2
+    (phantom_scalars' center).  The chains keep the study grid up to the detector, which reflect-pads it by 15*ov pixels,
+    sums ov x ov blocks and crops 15 detector pixels (Detector.detection): study column x sits at padded column x + 15*ov,
+    in block (x + 15*ov) // ov = x // ov + 15, which the crop brings back to x // ov -- pad and crop cancel, and the study
+    grid is ov times the detector's, so nothing else is cut.  Detector pixel c therefore covers study columns
+    ov*c ... ov*c + ov - 1, whose centre is ov*c + (ov - 1)/2: a point at study coordinate x is at detector coordinate
+    (x - (ov - 1)/2)/ov.  With ov = 2 and dimY = 2*m that is m/2 - 0.25: a quarter of a pixel off m // 2."""
+    ov = int(experiment.exp_dict['overSampling'])
+    dimY = int(experiment.exp_dict['studyDimensions'][1])
+    return (dimY // 2 - (ov - 1) / 2.0) / ov
+
+
+def voxel_size(experiment):
+    """The voxel of a scan's volume in metres: the detector pixel demagnified to the object, p/M."""
+    return float(experiment.myDetector.det_param['myPixelSize']) * 1e-6 / float(experiment.exp_dict['magnification'])
+
+
+def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
+    """Run the chain of `experiment` (an Experiment, or the exp_dict of one) once per angle of angles_deg, all of its
+    nbExpPoints membrane positions each time, and collect one map per angle and energy bin ->
+    {'sinograms': {bin: [A, n, m] float32 tensor}, 'angles': the angles, 'center': rotation_center(experiment),
+     'voxel_m': voxel_size(experiment), 'modality': modality, 'energy_keV': the run's mean detected energy}.
+    modality='attenuation': -ln(Propag/White) of position 0 (the propagation image over its flat field; any number of
+    positions), for mu_volume.  modality='phase': 'phi' of retrieval.retrieve on the angle's positions (retrieve_options:
+    method, max_shift, dark_field, window, search -- bound by retrieval.check_method's rules), for delta_volume.
+    The sample of interest must be the contrast phantom (ValueError otherwise): per angle its myAngle is set and its
+    geometry rebuilt on the study grid.  A membrane that has a geometry function gets its geometry per position as main.run
+    does; an injected one keeps the geometry it has."""
+    import torch
+    from . import retrieval
+    if modality not in MODALITIES:
+        raise ValueError("modality must be one of %s, got %r" % (", ".join(MODALITIES), modality))
+    if isinstance(experiment, dict):
+        from .Experiment import Experiment
+        experiment = Experiment(experiment)
+    ed = experiment.exp_dict
+    sample = _phantom(experiment.mySampleofInterest)
+    npos = int(ed['nbExpPoints'])
+    if modality == 'phase':
+        retrieval.check_method(retrieve_options.get('method', 'lcs'), npos, retrieve_options.get('max_shift'),
+                               retrieve_options.get('dark_field', False))
+    elif retrieve_options:
+        raise ValueError("%s are options of modality='phase'" % ", ".join(sorted(retrieve_options)))
+    angles = [float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel()]
+    membrane = experiment.myMembrane
+    sinos = {}
+    for angle in angles:
+        _turn(sample, angle, ed['studyDimensions'], ed['studyPixelSize'], ed['overSampling'])
+        ed['meanEnergy'] = 0                       # every angle is a run of its own (the chain folds the positions' means into it)
+        results = {}
+        for pointNum in range(npos if modality == 'phase' else 1):
+            if getattr(membrane, "myGeometryFunction", ""):
+                membrane.myGeometry = []
+                membrane.getMyGeometry(ed['studyDimensions'], membrane.membranePixelSize, ed['overSampling'], pointNum, npos)
+            results[pointNum] = experiment.computeSampleAndReferenceImages(pointNum)
+        experiment.resolve_mean_energy()
+        if modality == 'attenuation':
+            P, W = results[0][2], results[0][3]
+            maps = {b: -torch.log(P[b] / W[b]) for b in range(P.shape[0])}
+        else:
+            params = retrieval.params_from_experiment(experiment)
+            maps = {b: r['phi'].clone() for b, r in retrieval.retrieve(results, params, **retrieve_options).items()}
+        for b, v in maps.items():
+            sinos.setdefault(b, []).append(v)
+    return {'sinograms': {b: torch.stack(v) for b, v in sinos.items()}, 'angles': angles,
+            'center': rotation_center(experiment), 'voxel_m': voxel_size(experiment), 'modality': modality,
+            'energy_keV': float(ed['meanEnergy'])}
+
+
+def reconstruct(scanned, filter='ramp', circle=True):
+    """A scan's volumes in physical units -> {bin: [n, m, m] float32 tensor}: mu (1/m) for modality 'attenuation', delta for
+    'phase' (at the scan's mean detected energy: right for one bin only, as retrieval.retrieve's default)."""
+    out = {}
+    for b, s in scanned['sinograms'].items():
+        vol = fbp(s, scanned['angles'], center=scanned['center'], filter=filter, circle=circle)
+        out[b] = (mu_volume(vol, scanned['voxel_m']) if scanned['modality'] == 'attenuation'
+                  else delta_volume(vol, scanned['energy_keV'], scanned['voxel_m']))
+    return out
+
+
+def volume_name(modality):
+    return "mu" if modality == 'attenuation' else "delta"
+
+
+def save_volume(vol, path, fmt=".npy"):
+    """Write an [n, m, m] volume (tensor or array): fmt '.npy' -> the one file path + '.npy' (float32 [n, m, m]); '.tif' /
+    '.edf' -> the directory `path` with one image per slice, slice_<rrrr><fmt>.  -> the paths written."""
+    from .InputOutput.pagailleIO import save_image
+    v = np.ascontiguousarray(vol.detach().cpu().numpy() if hasattr(vol, "detach") else np.asarray(vol), dtype=np.float32)
+    if v.ndim != 3:
+        raise ValueError("a volume is [n, m, m], got shape %s" % (v.shape,))
+    if fmt == ".npy":
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        np.save(path + fmt, v)
+        return [path + fmt]
+    os.makedirs(path, exist_ok=True)
+    paths = []
+    for r in range(v.shape[0]):
+        paths.append(os.path.join(path, "slice_%04d%s" % (r, fmt)))
+        save_image(v[r], paths[-1])
+    return paths

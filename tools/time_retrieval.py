@@ -1,6 +1,6 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
@@ -18,6 +18,10 @@ box passes more in the prologue against (2s+1)^2 in the search, and a 2 x 2 solv
 --paganin times psx_paganin_f32 alone (B images of one shape with their flat fields, both maps): per pair of images the pack
 reads 4 n x m float32 images and writes the extended grid, the filter reads and writes it, the crop reads its corner and writes
 4 maps; the two rocFFT transforms are the integration's.
+
+--fbp times psx_fbp_f32 alone at (A, n, m) = (720, 64, 1024): the filter (pack, two rocFFT passes per row pair, the multiply)
+against the bytes it moves, and k_fbp_backproject against its two prices per voxel, angle and detector row: two 4-byte LDS
+reads (as half of two ds_read_b128 that serve four rows) at 256 B per clock and CU, and two float32 FMAs.
 """
 import argparse
 import ctypes
@@ -154,13 +158,59 @@ def paganin_case(n, m, B, reps):
                                                                                         b / (per[k] * 1e-6) / PEAK))
 
 
+LDS_PEAK = 256 * 256 * CLOCK                            # bytes per second: 256 B per clock and CU
+FMA32_PEAK = SIMDS * 64 / 2.0 * CLOCK                   # float32 FMAs per second: a wave64 v_fma_f32 takes 2 cycles of a SIMD
+
+
+def fbp_case(A, n, m, reps):
+    g = torch.Generator(device="cuda").manual_seed(A + n)
+    sino = 1.0 + torch.rand((A, n, m), device="cuda", generator=g)
+    plan = ops.FbpPlan([180.0 * a / A for a in range(A)], m)
+    vol = torch.empty((n, m, m), device="cuda")
+    for _ in range(2):
+        ops.fbp(sino, plan, out=vol)
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        ops.fbp(sino, plan, out=vol)
+    torch.cuda.synchronize()
+    s = summary()
+    lib().psx_profile_enable(0)
+    per = {k: v[1] / reps * 1e3 for k, v in s.items()}       # us per call (all launches of a kernel in one call)
+    P = 64
+    while P < 2 * m:
+        P *= 2
+    pairs = (n + 1) // 2
+    grid = 8.0 * pairs * A * P
+    price = {"k_fbp_pack": 4.0 * A * n * m + grid, "k_fbp_filter": 2 * grid}
+    fft = sum(v for k, v in per.items() if k.startswith("rocfft_fbp"))
+    print("A=%d n=%d m=%d  plan %.0f MiB  filter per call %.1f us = kernels %.1f us + rocFFT %.1f us (%s, %d launches each)"
+          % (A, n, m, plan.bytes / 2 ** 20, per["k_fbp_pack"] + per["k_fbp_filter"] + fft, per["k_fbp_pack"] + per["k_fbp_filter"],
+             fft, ", ".join("%s %.1f" % (k, v) for k, v in per.items() if k.startswith("rocfft")), pairs))
+    for k, b in price.items():
+        print("    %s %.1f us  price %.1f MB (%.1f us at 8 TB/s) = %.2f of 8 TB/s" % (k, per[k], b / 1e6, b / PEAK * 1e6,
+                                                                                        b / (per[k] * 1e-6) / PEAK))
+    t = per["k_fbp_backproject"] * 1e-6
+    work = float(m) * m * A * n
+    lds, fma = 8.0 * work, 2.0 * work
+    print("    k_fbp_backproject %.1f us per call (%d launches)  LDS reads %.1f GB (%.1f us at %.0f TB/s) = %.2f of the LDS rate;  "
+          "%.1f G FMA32 (%.1f us at %.1f T FMA/s) = %.2f of the float32 FMA rate"
+          % (t * 1e6, s["k_fbp_backproject"][0] // reps, lds / 1e9, lds / LDS_PEAK * 1e6, LDS_PEAK / 1e12, lds / t / LDS_PEAK,
+             fma / 1e9, fma / FMA32_PEAK * 1e6, FMA32_PEAK / 1e12, fma / t / FMA32_PEAK))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--umpa-only", action="store_true")
     ap.add_argument("--paganin", action="store_true", help="time psx_paganin_f32 only")
+    ap.add_argument("--fbp", action="store_true", help="time psx_fbp_f32 only")
     a = ap.parse_args()
+    if a.fbp:
+        fbp_case(720, 64, 1024, max(a.reps // 4, 2))
+        fbp_case(90, 24, 64, a.reps)
+        return
     if a.paganin:
         for n, m, B in ((2048, 2048, 2), (2048, 2048, 8), (200, 200, 2)):
             paganin_case(n, m, B, a.reps)

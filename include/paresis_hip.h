@@ -493,6 +493,26 @@ int psx_fbp_plan_destroy(psx_fbp_plan *plan);
 size_t psx_fbp_plan_bytes(const psx_fbp_plan *plan);
 int psx_fbp_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *stream);
 
+/* ---- the matched projector pair of a plan: B (back-projection without filter and scale) and its transpose ---------------
+ * B is the interpolation operator of the back-projection above, per angle a and voxel (i, j):
+ *   u = fma(j - h, c_a, fma(-(i - h), s_a, center)) in float64;  fl = floor(u);  w1 = (float)(u - fl);  w0 = 1.0f - w1;
+ *   (B q)[r][i][j] = sum_a w0*q[a][r][fl] + w1*q[a][r][fl + 1], q[-1] = q[m] = 0, in float32 in ascending a;
+ *   circle != 0: (B q) is 0 on the voxels with (i - h)^2 + (j - h)^2 > h^2.
+ * psx_fbp_adjoint_f32: vol [n][m][m] = B sino, sino [A][n][m]: unfiltered and with scale 1 on any plan (the plan's filter
+ *   is ignored); it uses the plan's buffer in the row blocks of psx_fbp_f32.  On a PSX_FBP_NONE plan psx_fbp_f32 is
+ *   float32(pi/(2A)) times it, bit for bit.
+ * psx_fbp_project_f32: sino [A][n][m] = B^T vol, vol [n][m][m], the exact transpose:
+ *   sino[a][r][k] = sum over the voxels (i, j) (the lit ones when circle != 0) of t*vol[r][i][j],
+ *   t = w0 if k == fl, w1 if k == fl + 1, else 0: the weights are bit for bit B's, never formed from an inverted
+ *   coordinate.  Unscaled: a line integral in pixels, the unit psx_fbp_f32 consumes.  The plan's filter is ignored.
+ *   Summation order, float32 fused multiply-adds: the slice is walked in lines of its major axis -- lines of constant i
+ *   when |c_a| >= |s_a|, of constant j otherwise -- line L goes to partial sum L & 3, each partial takes its lines in
+ *   ascending L and the voxels of a line in ascending minor index, and the sample is (p0 + p1) + (p2 + p3).  No atomics:
+ *   two calls return the same bits, whatever n and the plan's max_rows are.
+ * Both refuse a null plan, null pointers and n < 1, and are asynchronous on the stream. */
+int psx_fbp_project_f32(psx_fbp_plan *plan, const float *vol, int n, float *sino, void *stream);
+int psx_fbp_adjoint_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *stream);
+
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------------------------------------
  * psx_profile_enable(1) clears the log and makes every kernel launch of the library record a HIP event pair on the
  * stream it is launched on; psx_profile_summary() waits for the recorded events and writes one line per kernel,

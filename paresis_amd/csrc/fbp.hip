@@ -7,6 +7,9 @@
 //   k_fbp_backproject   one workgroup per 16 x 16 tile of the slice and block of 4 detector rows (two row pairs)
 // The filtered sinogram is never cropped or copied: the back-projector reads the float2 lines of Z as they are, and a row
 // pair of Z is the (row, row + 1) interleave its LDS image wants.
+//   k_fbp_project  the back-projector's exact transpose, volume -> sinogram, in the gather form: one workgroup per angle,
+//                  run of 64 samples and block of 4 detector rows (psx_fbp_project_f32; psx_fbp_adjoint_f32 is pack +
+//                  back-projection at scale 1)
 #include "fresnel_plan.hpp"
 
 #include <complex>
@@ -128,6 +131,132 @@ __global__ __launch_bounds__(256) void k_fbp_backproject(FbpArgs p) {
 #pragma unroll
     for (int r = 0; r < FBP_ROWS; ++r)
         if (rb + r < p.n) p.vol[((int64_t)(rb + r) * p.m + i) * p.m + j] = lit ? acc[r] * p.scale : 0.f;
+}
+
+// ---- forward projection: sino = B^T vol, the gather form ---------------------------------------------------------------
+// Per angle the slice is walked along its major axis: lines of constant i when |cos| >= |sin| (u moves by cos per step of
+// the minor index j), lines of constant j otherwise (u moves by -sin per step of i).  |g| = |du/dq| >= 1/sqrt(2), so on
+// one line the voxels with a weight on sample k -- those with |u - k| < 1 -- lie in the open interval
+// (lo, lo + 2/|g|) of the minor index, lo = q* - 1/|g|, at most 2 sqrt(2) long: at most 3 integers.  lo comes from the
+// inverted coordinate, affine in the line index and good to ~2e-9 (|center| <= 2^20, m <= 8192); the candidates are
+// floor(lo - 1e-6) + {1, 2, 3}: every integer above lo - 1e-6 and below lo + 2.8285 is among them (1e-6 to spare below,
+// 0.17 above).  Each candidate's u, floor and weights are the back-projector's expressions on (i, j); a candidate outside
+// the interval gets the weight 0.  The inverted coordinate only chooses where to look.
+constexpr int PRJ_KS = 64;       // samples per workgroup: one per lane
+constexpr int PRJ_LINES = 16;    // major-axis lines staged per piece: four per wave
+constexpr int PRJ_PARTS = 4;     // partial sums per sample: line L goes to partial L & 3, one wave each
+constexpr int PRJ_CAND = 3;      // candidates per line and sample
+// Minor indices one staged line holds: floor(lo - 1e-6) of the 64 samples spans at most ceil(63/|g|) + 1 values from the
+// base (the smallest) on, the first candidate is one above it and two more follow: ceil(63/|g|) + 4 <= 94.  97 keeps the
+// lines of a piece on different LDS banks when they are filled line-fastest; a fill takes 6 rounds of 16 or 32 indices.
+constexpr int PRJ_W = 97;
+
+struct PrjArgs {
+    const float *vol;         // [n][m][m]
+    const double *cs;         // [A] cos, then [A] sin
+    float *sino;              // [A][n][m]
+    double center;
+    int A, n, m, r0, circle, runs;
+};
+
+__global__ __launch_bounds__(256) void k_fbp_project(PrjArgs p) {
+    __shared__ float4 seg[PRJ_LINES][PRJ_W];         // seg[l][x] = the four rows' voxel (line L0 + l, minor sbase[l] + x), 0 if unlit
+    __shared__ float4 part[PRJ_PARTS][PRJ_KS];
+    __shared__ int sbase[2][PRJ_LINES];
+
+    const int tid = threadIdx.x;
+    const int ks = tid & (PRJ_KS - 1), wv = tid >> 6;
+    const int a = blockIdx.x / p.runs, k0 = (blockIdx.x % p.runs) * PRJ_KS;
+    const int rb = p.r0 + blockIdx.y * FBP_ROWS;
+    const int m = p.m, h = m / 2;
+    const double c = p.cs[a], s = p.cs[p.A + a];
+    const bool alongj = fabs(c) >= fabs(s);          // the minor index is j (lines of constant i); 45 degrees goes here
+    // lo(k, L) = h + (k - center + (L - h) s)/c - 1/|c| along j, h + (k - center - (L - h) c)/(-s) - 1/|s| along i
+    const double inv = 1.0 / (alongj ? c : -s), reach = fabs(inv), slope = (alongj ? s : -c) * inv;
+    const double off = (double)h - (double)h * slope - reach - 1e-6 - p.center * inv;
+    const double kd = (double)(k0 + ks);
+    const double lo_k = fma(kd, inv, off);                                          // the thread's lo at L = 0
+    const double lo_a = fma((double)k0, inv, off), lo_b = fma((double)(k0 + PRJ_KS - 1), inv, off);
+    const int wneed = (int)ceil((double)(PRJ_KS - 1) * reach) + 4;                  // <= 94
+    const int64_t mm = (int64_t)m * m;
+    // rows of the block that exist: the others are read from row 0 and zeroed
+    const int nr = p.n - rb;
+    const float *const vol0 = p.vol + (int64_t)rb * mm;
+    const int64_t o1 = nr > 1 ? mm : 0, o2 = nr > 2 ? 2 * mm : 0, o3 = nr > 3 ? 3 * mm : 0;
+
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int piece = 0;
+    for (int L0 = 0; L0 < m; L0 += PRJ_LINES, ++piece) {
+        int *const base = sbase[piece & 1];
+        int live = 0;
+        if (tid < PRJ_LINES) {
+            const int L = L0 + tid;
+            const double Ld = (double)L;
+            const int b = (int)floor(fmin(fma(Ld, slope, lo_a), fma(Ld, slope, lo_b)));
+            base[tid] = b;
+            if (L < m) {
+                // the lit voxels of the line: |q - h| <= sqrt(h^2 - (L - h)^2), one more on either side for the root's rounding
+                const double dl = (double)(L - h);
+                const double half = p.circle ? sqrt(fmax((double)h * h - dl * dl, 0.0)) + 1.0 : (double)m;
+                const double lo = fmax(0.0, (double)h - half), hi = fmin((double)(m - 1), (double)h + half);
+                live = (double)(b + wneed) > lo && (double)b <= hi;
+            }
+        }
+        if (!__syncthreads_or(live)) continue;       // no voxel of these lines can reach the samples: the same for the whole workgroup
+
+        // fill: six rounds, the slice's j fastest whichever axis is major; every load is in bounds (clamped) and
+        // unconditional, so that the 24 of a thread are in flight together, and what is outside or unlit is zeroed after
+#pragma unroll
+        for (int it = 0; it < 6; ++it) {
+            const int l = alongj ? (tid >> 5) + 8 * (it & 1) : tid & 15;
+            const int x = alongj ? (tid & 31) + 32 * (it >> 1) : (tid >> 4) + 16 * it;
+            const int L = L0 + l, q = base[l] + x;
+            const int Lc = L < m ? L : m - 1, qc = q < 0 ? 0 : q < m ? q : m - 1;
+            const bool ok = L < m && q >= 0 && q < m && (!p.circle || (Lc - h) * (Lc - h) + (qc - h) * (qc - h) <= h * h);
+            const float *src = vol0 + (alongj ? (int64_t)Lc * m + qc : (int64_t)qc * m + Lc);
+            float4 v = make_float4(src[0], src[o1], src[o2], src[o3]);
+            if (nr < 4) {
+                if (nr < 2) v.y = 0.f;
+                if (nr < 3) v.z = 0.f;
+                v.w = 0.f;
+            }
+            if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (x < wneed) seg[l][x] = v;
+        }
+        __syncthreads();
+
+#pragma unroll
+        for (int t = 0; t < PRJ_LINES / PRJ_PARTS; ++t) {
+            const int l = wv + PRJ_PARTS * t, L = L0 + l;
+            const double dl = (double)(L - h);
+            int x = (int)floor(fma((double)L, slope, lo_k)) + 1 - base[l];
+            x = x < 0 ? 0 : x > wneed - PRJ_CAND ? wneed - PRJ_CAND : x;   // never taken: keeps the reads inside the filled line whatever the arithmetic did
+            const int q = base[l] + x;
+#pragma unroll
+            for (int e = 0; e < PRJ_CAND; ++e) {
+                const double dq = (double)(q + e - h);
+                const double u = alongj ? fma(dq, c, fma(-dl, s, p.center)) : fma(dl, c, fma(-dq, s, p.center));
+                const double fl = floor(u);
+                const float w1 = (float)(u - fl), w0 = 1.0f - w1;
+                const float wt = fl == kd ? w0 : fl + 1.0 == kd ? w1 : 0.f;
+                const float4 v = seg[l][x + e];
+                acc.x = fmaf(wt, v.x, acc.x);
+                acc.y = fmaf(wt, v.y, acc.y);
+                acc.z = fmaf(wt, v.z, acc.z);
+                acc.w = fmaf(wt, v.w, acc.w);
+            }
+        }
+    }
+    part[wv][ks] = acc;
+    __syncthreads();
+    const int k = k0 + ks;
+    if (wv != 0 || k >= m) return;
+    const float4 p0 = part[0][ks], p1 = part[1][ks], p2 = part[2][ks], p3 = part[3][ks];
+    float *const dst = p.sino + ((int64_t)a * p.n + rb) * m + k;
+    dst[0] = (p0.x + p1.x) + (p2.x + p3.x);
+    if (nr > 1) dst[m] = (p0.y + p1.y) + (p2.y + p3.y);
+    if (nr > 2) dst[2 * (int64_t)m] = (p0.z + p1.z) + (p2.z + p3.z);
+    if (nr > 3) dst[3 * (int64_t)m] = (p0.w + p1.w) + (p2.w + p3.w);
 }
 
 // in-place radix-2 transform of a power-of-two length in float64 (the filter table: once per plan)
@@ -264,6 +393,54 @@ int psx_fbp_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *
         FbpArgs a;
         a.Z = Z; a.cs = plan->cs.get(); a.vol = vol; a.center = plan->center;
         a.scale = (float)(M_PI / (2.0 * (double)A));
+        a.A = A; a.n = n; a.m = m; a.L = L; a.r0 = r0; a.npairs = npairs; a.circle = plan->circle;
+        const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)cdiv(rows, FBP_ROWS));
+        PSX_TIMED("k_fbp_backproject", st, k_fbp_backproject<<<grid, 256, 0, st>>>(a));
+        if (int rc = launch_check("k_fbp_backproject")) return rc;
+    }
+    return 0;
+}
+
+int psx_fbp_project_f32(psx_fbp_plan *plan, const float *vol, int n, float *sino, void *stream) {
+    PSX_REQUIRE(plan != nullptr, "psx_fbp_project_f32: null plan");
+    PSX_REQUIRE(vol != nullptr && sino != nullptr, "psx_fbp_project_f32: null volume or sinogram");
+    PSX_REQUIRE(n >= 1 && (int64_t)n * plan->A * plan->m <= (int64_t)1 << 40 && (int64_t)n * plan->m * plan->m <= (int64_t)1 << 40,
+                "psx_fbp_project_f32: n=%d detector rows outside [1, 2^40 elements]", n);
+    hipStream_t st = (hipStream_t)stream;
+    PrjArgs a;
+    a.vol = vol; a.cs = plan->cs.get(); a.sino = sino; a.center = plan->center;
+    a.A = plan->A; a.n = n; a.m = plan->m; a.circle = plan->circle; a.runs = (int)cdiv(plan->m, PRJ_KS);
+    const int step = FBP_ROWS * 32768;               // rows per launch: grid.y stays below 65536
+    for (int r0 = 0; r0 < n; r0 += step) {
+        const int rows = n - r0 < step ? n - r0 : step;
+        a.r0 = r0;
+        // x: the sample runs of one angle, then the angles; y: the blocks of four rows -- every angle of a block runs
+        // before the next block starts, so its four slices are read from cache
+        const dim3 grid((unsigned)(a.runs * a.A), (unsigned)cdiv(rows, FBP_ROWS));
+        PSX_TIMED("k_fbp_project", st, k_fbp_project<<<grid, 256, 0, st>>>(a));
+        if (int rc = launch_check("k_fbp_project")) return rc;
+    }
+    return 0;
+}
+
+int psx_fbp_adjoint_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *stream) {
+    PSX_REQUIRE(plan != nullptr, "psx_fbp_adjoint_f32: null plan");
+    PSX_REQUIRE(sino != nullptr && vol != nullptr, "psx_fbp_adjoint_f32: null sinogram or volume");
+    PSX_REQUIRE(n >= 1 && (int64_t)n * plan->A * plan->m <= (int64_t)1 << 40 && (int64_t)n * plan->m * plan->m <= (int64_t)1 << 40,
+                "psx_fbp_adjoint_f32: n=%d detector rows outside [1, 2^40 elements]", n);
+    hipStream_t st = (hipStream_t)stream;
+    const int A = plan->A, m = plan->m, L = plan->L;
+    float2 *const Z = plan->Z.get();
+    const int tiles = (int)cdiv(m, FBP_TILE);
+    for (int r0 = 0; r0 < n; r0 += plan->max_rows) {
+        const int rows = n - r0 < plan->max_rows ? n - r0 : plan->max_rows;
+        const int npairs = (rows + 1) / 2;
+        const int64_t N = (int64_t)npairs * A * L;
+        PSX_TIMED("k_fbp_pack", st, k_fbp_pack<<<ew_grid(N, 256), 256, 0, st>>>(sino, Z, A, n, m, L, r0, npairs));
+        if (int rc = launch_check("k_fbp_pack")) return rc;
+        FbpArgs a;
+        a.Z = Z; a.cs = plan->cs.get(); a.vol = vol; a.center = plan->center;
+        a.scale = 1.0f;
         a.A = A; a.n = n; a.m = m; a.L = L; a.r0 = r0; a.npairs = npairs; a.circle = plan->circle;
         const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)cdiv(rows, FBP_ROWS));
         PSX_TIMED("k_fbp_backproject", st, k_fbp_backproject<<<grid, 256, 0, st>>>(a));

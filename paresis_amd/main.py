@@ -5,7 +5,8 @@
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
                                [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa|umpa-df --window W --search M]]
                                [--retrieve-propagation [--material NAME]]
-                               [--tomography A [--tomography-modality attenuation|phase]]
+                               [--tomography A [--tomography-modality attenuation|phase]
+                                [--tomography-method fbp|sirt|cgls --tomography-iterations K]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
@@ -22,7 +23,8 @@ then turns the phantom through A angles on [0, 180) degrees, runs the chain at e
 reconstructs by filtered back-projection on rank 0 and writes tomography/mu_<expID> (--tomography-modality attenuation,
 the default: 1/m, from -ln(Propag/White), any --points) or tomography/delta_<expID> (phase: from the retrieved phi, the
 rules and options of --retrieve) under each bin's directory: one [n, m, m] file for --format .npy, else a directory of
-slices.
+slices.  --tomography-method sirt|cgls reconstructs with --tomography-iterations K >= 1 steps of SIRT or CGLS on the matched
+projector pair instead (tomography.sirt / cgls): the methods for few angles.
 """
 import argparse
 import datetime
@@ -33,7 +35,8 @@ import numpy as np
 
 
 def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
-        method='lcs', window=2, search=3, propagation=False, material=None, tomography=0, tomography_modality='attenuation'):
+        method='lcs', window=2, search=3, propagation=False, material=None, tomography=0, tomography_modality='attenuation',
+        tomography_method='fbp', tomography_iterations=0):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
@@ -53,13 +56,18 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     phantom through A angles on [0, 180), runs the chain at each (tomography.scan with tomography_modality; 'phase'
     retrieves with method, max_shift, dark_field, window, search and needs their positions), reconstructs every bin
     (tomography.reconstruct) and, with save, writes <bin dir>/tomography/{mu|delta}_<expID> (tomography.save_volume).
-    exp_dict['tomographyParams'] then holds the angles, the centre, the voxel size and the modality, and
-    exp_dict['tomographyVolumes'] the {bin: [n, m, m] device tensor} volumes."""
+    tomography_method 'sirt' or 'cgls' with tomography_iterations >= 1 reconstructs iteratively instead of by filtered
+    back-projection ('fbp', which takes no iterations).  exp_dict['tomographyParams'] then holds the angles, the centre, the
+    voxel size, the modality, the method and its iterations, and exp_dict['tomographyVolumes'] the {bin: [n, m, m] device
+    tensor} volumes."""
     from . import tomography as tomo
     if tomography_modality not in tomo.MODALITIES:
         raise ValueError("tomography_modality must be one of %s, got %r" % (", ".join(tomo.MODALITIES), tomography_modality))
     if tomography_modality != 'attenuation' and not tomography:
         raise ValueError("tomography_modality is an option of tomography")
+    if (tomography_method != 'fbp' or tomography_iterations) and not tomography:
+        raise ValueError("tomography_method and tomography_iterations are options of tomography")
+    tomo.check_reconstruction(tomography_method, tomography_iterations or None)
     if int(tomography) < 0 or int(tomography) > _lib_max_angles():
         raise ValueError("tomography takes 1 to %d angles, got %r" % (_lib_max_angles(), tomography))
     if tomography and tomography_modality == 'phase':
@@ -216,8 +224,9 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
             keep = TRACKERS[(method, bool(dark_field))].options + ('method', 'dark_field')
             options = {k: v for k, v in options.items() if k in keep}
         scanned = tomo.scan(experiment, angles, modality=tomography_modality, **options)
-        volumes = tomo.reconstruct(scanned)
+        volumes = tomo.reconstruct(scanned, method=tomography_method, iterations=tomography_iterations or None)
         exp_dict['tomographyParams'] = {k: scanned[k] for k in ('angles', 'center', 'voxel_m', 'modality', 'energy_keV')}
+        exp_dict['tomographyParams'].update(method=tomography_method, iterations=int(tomography_iterations))
         if save:
             nbin = len(volumes)
             thresholds = [experiment.mySource.mySpectrum[0][0]] + list(experiment.myDetector.det_param['myBinsThersholds'])
@@ -270,6 +279,10 @@ def main(argv=None):
     ap.add_argument("--tomography-modality", default="attenuation", choices=["attenuation", "phase"],
                     help="--tomography: mu from -ln(Propag/White) (default), or delta from the retrieved phi (the rules and "
                          "options of --retrieve)")
+    ap.add_argument("--tomography-method", default="fbp", choices=["fbp", "sirt", "cgls"],
+                    help="--tomography: filtered back-projection (default), or --tomography-iterations steps of SIRT or CGLS")
+    ap.add_argument("--tomography-iterations", type=int, default=0, metavar="K",
+                    help="--tomography-method sirt|cgls: the number of iterations (>= 1)")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -293,9 +306,16 @@ def main(argv=None):
         ap.error("--tomography takes a number of angles >= 1")
     if a.tomography_modality != "attenuation" and not a.tomography:
         ap.error("--tomography-modality is an option of --tomography")
+    if a.tomography_method != "fbp" and not a.tomography:
+        ap.error("--tomography-method is an option of --tomography")
+    if a.tomography_iterations != 0 and not a.tomography:
+        ap.error("--tomography-iterations is an option of --tomography")
+    if a.tomography_iterations < 0 or (a.tomography_method == "fbp") != (a.tomography_iterations == 0):
+        ap.error("--tomography-iterations K >= 1 goes with --tomography-method sirt or cgls, and only with them")
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
-        material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality)
+        material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality,
+        tomography_method=a.tomography_method, tomography_iterations=a.tomography_iterations)
 
 
 if __name__ == "__main__":

@@ -1241,20 +1241,41 @@ class FbpPlan(_Plan):
         """ops.fbp on this plan."""
         return fbp(sino, self, out=out)
 
+    def project(self, vol, out=None):
+        """ops.fbp_project on this plan."""
+        return fbp_project(vol, self, out=out)
+
+    def adjoint(self, sino, out=None):
+        """ops.fbp_adjoint on this plan."""
+        return fbp_adjoint(sino, self, out=out)
+
 
 def fbp(sino, plan, out=None):
     """Filtered back-projection (psx_fbp_f32): sino, an [A, n, m] float32 tensor in HBM (A, m the plan's; any n >= 1) ->
     the [n, m, m] float32 volume, vol[r] the slice of detector row r.  out: a caller-owned [n, m, m] float32 tensor to write
     into.  Calls on one plan are ordered on the current stream (they share its buffer)."""
+    return _fbp_call("psx_fbp_f32", plan, sino, "sino", out, False)
+
+
+def _fbp_call(name, plan, x, what, out, to_sino):
+    """One of the plan's three operators: x is a sinogram [A, n, m] (-> a volume [n, m, m]) or, with to_sino, a volume
+    (-> a sinogram).  Every check comes before the device is touched."""
     if not isinstance(plan, FbpPlan):
         raise PsxError("plan must be an ops.FbpPlan, got %r" % type(plan))
-    _need(sino, torch.float32, "sino")
-    if sino.dim() != 3 or sino.shape[0] != len(plan.theta) or sino.shape[2] != plan.m or sino.shape[1] < 1:
-        raise PsxError("sino has shape %s, the plan takes [%d, n >= 1, %d]" % (tuple(sino.shape), len(plan.theta), plan.m))
-    if sino.device != plan.device:
-        raise PsxError("sino is on %s, the plan on %s" % (sino.device, plan.device))
-    n = int(sino.shape[1])
-    shape = (n, plan.m, plan.m)
+    A, m = len(plan.theta), plan.m
+    _need(x, torch.float32, what)
+    if to_sino:
+        ok = x.dim() == 3 and x.shape[0] >= 1 and x.shape[1] == m and x.shape[2] == m
+        takes, n = "[n >= 1, %d, %d]" % (m, m), int(x.shape[0]) if ok else 0
+        shape = (A, n, m)
+    else:
+        ok = x.dim() == 3 and x.shape[0] == A and x.shape[2] == m and x.shape[1] >= 1
+        takes, n = "[%d, n >= 1, %d]" % (A, m), int(x.shape[1]) if ok else 0
+        shape = (n, m, m)
+    if not ok:
+        raise PsxError("%s has shape %s, the plan takes %s" % (what, tuple(x.shape), takes))
+    if x.device != plan.device:
+        raise PsxError("%s is on %s, the plan on %s" % (what, x.device, plan.device))
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=plan.device)
     else:
@@ -1262,5 +1283,21 @@ def fbp(sino, plan, out=None):
         if out.device != plan.device:
             raise PsxError("out is on %s, the plan on %s" % (out.device, plan.device))
     with torch.cuda.device(plan.device):
-        check(lib().psx_fbp_f32(plan._h, _ptr(sino), n, _ptr(out), _stream()), "psx_fbp_f32")
+        check(getattr(lib(), name)(plan._h, _ptr(x), n, _ptr(out), _stream()), name)
     return out
+
+
+def fbp_project(vol, plan, out=None):
+    """The plan's forward projector (psx_fbp_project_f32; the contract is in include/paresis_hip.h): vol, an [n, m, m]
+    float32 tensor in HBM -> the [A, n, m] float32 sinogram B^T vol, the exact transpose of the back-projector's
+    interpolation (the lit voxels only when the plan has `circle`), unscaled: line integrals in pixels, what ops.fbp
+    consumes.  The plan's filter is ignored.  Deterministic: two calls return the same bits.  out: a caller-owned
+    [A, n, m] float32 tensor to write into."""
+    return _fbp_call("psx_fbp_project_f32", plan, vol, "vol", out, True)
+
+
+def fbp_adjoint(sino, plan, out=None):
+    """The plan's back-projector without filter and scale (psx_fbp_adjoint_f32): sino [A, n, m] -> B sino, [n, m, m]; on a
+    'none' plan ops.fbp is float32(pi/(2A)) times it.  The plan's filter is ignored.  out: a caller-owned [n, m, m]
+    float32 tensor.  Calls on one plan are ordered on the current stream (they share its buffer)."""
+    return _fbp_call("psx_fbp_adjoint_f32", plan, sino, "sino", out, False)

@@ -4,6 +4,10 @@
                                         include/paresis_hip.h): [A, n, m] maps, one per angle -> [n, m, m], a slice per
                                         detector row.  The sinogram holds LINE INTEGRALS IN PIXELS of the slice's voxel: a
                                         map in physical units (phi in radians, -ln T) gives the quantity per voxel length.
+    forward_project(vol, angles_deg, ...)    the matched pair behind the iterative methods (ops.fbp_project / fbp_adjoint):
+    back_project(sinogram, angles_deg, ...)  B^T vol, the exact transpose of fbp's interpolation, and B sinogram, unscaled
+    sirt(sinogram, angles_deg, iterations, ..., nonneg)   SIRT and CGLS on min |B^T x - b|: what few angles call for,
+    cgls(sinogram, angles_deg, iterations, ...)           where filtered back-projection streaks
     delta_volume(vol, energy_keV, voxel_m)   phi = -k * integral(delta) dl  ->  delta = -vol/(k*voxel), k = getk(E)
     mu_volume(vol, voxel_m)                  -ln T = integral(mu) dl         ->  mu = vol/voxel (1/m)
     project(sample, energy_keV, angles_deg, dims, pixel_um)   the phantom's ideal sinograms phi and -ln T on the study grid
@@ -16,7 +20,8 @@ The beam is treated as parallel: no fan- or cone-beam weighting.  At the magnifi
 three-dimensional description -- 13 material discs on a slice, projected at Sample.myAngle -- so project and scan refuse
 every other sample.
 
-    python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase] ...
+    python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase]
+                               [--tomography-method fbp|sirt|cgls --tomography-iterations K] ...
 """
 import os
 
@@ -29,13 +34,8 @@ PHANTOM_FUNCTION = "generateContrastPhantom"
 _plans = {}
 
 
-def fbp(sinogram, angles_deg, center=None, filter='ramp', circle=True):
-    """Filtered back-projection of an [A, n, m] float32 CUDA tensor (or a sequence of A n x m maps, as retrieval.retrieve and
-    retrieval.paganin return them) taken at angles_deg (A angles in degrees, any values) -> the [n, m, m] float32 volume on
-    the same device: vol[r] is the slice of detector row r in the orientation of contrast_phantom_slices.  center: the
-    detector column of the rotation axis (None: m // 2, scikit-image radon's; rotation_center for a scan).  filter:
-    'ramp', 'hann' or 'none'.  circle: zero outside the inscribed circle.  One plan per (device, A, m, angles, center,
-    filter, circle) is kept for the process's lifetime."""
+def _sinogram(sinogram, angles_deg):
+    """-> (the [A, n, m] tensor, the angles as a tuple of floats), checked on the host."""
     import torch
     from . import ops
     if not isinstance(sinogram, torch.Tensor):
@@ -46,15 +46,136 @@ def fbp(sinogram, angles_deg, center=None, filter='ramp', circle=True):
     angles = tuple(float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel())
     if len(angles) != sinogram.shape[0]:
         raise ops.PsxError("sinogram holds %d projections, angles_deg %d" % (sinogram.shape[0], len(angles)))
-    m = int(sinogram.shape[2])
-    dev = sinogram.device
+    return sinogram, angles
+
+
+def _plan(dev, angles, m, center, filter, circle):
+    """The module's plan of (device, A, m, angles, center, filter, circle), made on first use."""
+    import torch
+    from . import ops
     index = dev.index if dev.index is not None else torch.cuda.current_device()
     key = (index, len(angles), m, angles, float(m // 2 if center is None else center), str(filter), bool(circle))
     plan = _plans.get(key)
     if plan is None:
         plan = _plans[key] = ops.FbpPlan(angles, m, center=key[4], filter=filter, circle=circle,
                                          device=torch.device("cuda", index))
-    return ops.fbp(sinogram, plan)
+    return plan
+
+
+def fbp(sinogram, angles_deg, center=None, filter='ramp', circle=True):
+    """Filtered back-projection of an [A, n, m] float32 CUDA tensor (or a sequence of A n x m maps, as retrieval.retrieve and
+    retrieval.paganin return them) taken at angles_deg (A angles in degrees, any values) -> the [n, m, m] float32 volume on
+    the same device: vol[r] is the slice of detector row r in the orientation of contrast_phantom_slices.  center: the
+    detector column of the rotation axis (None: m // 2, scikit-image radon's; rotation_center for a scan).  filter:
+    'ramp', 'hann' or 'none'.  circle: zero outside the inscribed circle.  One plan per (device, A, m, angles, center,
+    filter, circle) is kept for the process's lifetime."""
+    from . import ops
+    sinogram, angles = _sinogram(sinogram, angles_deg)
+    return ops.fbp(sinogram, _plan(sinogram.device, angles, int(sinogram.shape[2]), center, filter, circle))
+
+
+def forward_project(vol, angles_deg, center=None, circle=True):
+    """The [A, n, m] float32 sinogram of an [n, m, m] float32 CUDA volume at angles_deg: B^T vol, the exact transpose of the
+    interpolation fbp back-projects with (ops.fbp_project), unscaled -- line integrals in pixels, what fbp consumes.
+    circle: only the voxels inside the inscribed circle are projected.  Uses the module's plan with filter 'none'."""
+    from . import ops
+    import torch
+    ops._need(vol, torch.float32, "vol")
+    if vol.dim() != 3 or vol.shape[1] != vol.shape[2]:
+        raise ops.PsxError("vol must be [n, m, m], got shape %s" % (tuple(vol.shape),))
+    angles = tuple(float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel())
+    return ops.fbp_project(vol, _plan(vol.device, angles, int(vol.shape[2]), center, 'none', circle))
+
+
+def back_project(sinogram, angles_deg, center=None, circle=True):
+    """B sinogram: the [n, m, m] back-projection of an [A, n, m] sinogram without filter and without the pi/(2A) scale
+    (ops.fbp_adjoint), the transpose of forward_project.  Uses the module's plan with filter 'none'."""
+    from . import ops
+    sinogram, angles = _sinogram(sinogram, angles_deg)
+    return ops.fbp_adjoint(sinogram, _plan(sinogram.device, angles, int(sinogram.shape[2]), center, 'none', circle))
+
+
+def _iterations(iterations):
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise ValueError("iterations must be an integer >= 0, got %r" % (iterations,))
+    return int(iterations)
+
+
+def _start(x0, sinogram):
+    import torch
+    from . import ops
+    n, m = int(sinogram.shape[1]), int(sinogram.shape[2])
+    if x0 is None:
+        return torch.zeros((n, m, m), dtype=torch.float32, device=sinogram.device)
+    ops._need(x0, torch.float32, "x0", (n, m, m))
+    return x0.clone()
+
+
+def _reciprocal(t):
+    """1/t where t > 1e-6, 0 elsewhere."""
+    import torch
+    return torch.where(t > 1e-6, 1.0 / t, torch.zeros_like(t))
+
+
+def sirt(sinogram, angles_deg, iterations, center=None, circle=True, nonneg=False, x0=None):
+    """`iterations` steps of SIRT on min |B^T x - b| for the [A, n, m] sinogram b (line integrals in pixels, as fbp takes
+    them) -> the [n, m, m] float32 volume:  x <- x + Cinv * B(Rinv * (b - B^T x)), then max(x, 0) if nonneg, with
+    R = B^T 1 (the ray lengths, with the circle), C = B 1 and Rinv, Cinv their reciprocals where they exceed 1e-6, 0
+    elsewhere -- computed once per call.  The two projections are ops.fbp_project and ops.fbp_adjoint on the module's
+    'none' plan; the element-wise steps are torch's.  x0: the start, zeros by default (not modified)."""
+    import torch
+    from . import ops
+    iterations = _iterations(iterations)
+    b, angles = _sinogram(sinogram, angles_deg)
+    plan = _plan(b.device, angles, int(b.shape[2]), center, 'none', circle)
+    x = _start(x0, b)
+    Rinv = _reciprocal(ops.fbp_project(torch.ones_like(x), plan))
+    Cinv = _reciprocal(ops.fbp_adjoint(torch.ones_like(b), plan))
+    res, upd = torch.empty_like(b), torch.empty_like(x)
+    for _ in range(iterations):
+        ops.fbp_project(x, plan, out=res)
+        torch.sub(b, res, out=res)
+        res.mul_(Rinv)
+        ops.fbp_adjoint(res, plan, out=upd)
+        x.addcmul_(Cinv, upd)
+        if nonneg:
+            x.clamp_(min=0)
+    return x
+
+
+def cgls(sinogram, angles_deg, iterations, center=None, circle=True, x0=None):
+    """`iterations` steps of CGLS on min |B^T x - b| -> the [n, m, m] float32 volume.  With K = B^T:
+    r = b - K x, s = B r, p = s, gamma = |s|^2; per step q = K p, alpha = gamma/|q|^2, x += alpha p, r -= alpha q, s = B r,
+    beta = |s|^2/gamma, p = s + beta p.  gamma and |q|^2 are taken PER DETECTOR ROW in float64, so every row is its own
+    two-dimensional problem and reconstructs the same alone or in a stack, to rounding; a row whose gamma or |q|^2 is 0
+    gets alpha = beta = 0, so a zero sinogram row stays exactly 0.  x0: the start, zeros by default (not modified)."""
+    import torch
+    from . import ops
+    iterations = _iterations(iterations)
+    b, angles = _sinogram(sinogram, angles_deg)
+    plan = _plan(b.device, angles, int(b.shape[2]), center, 'none', circle)
+    x = _start(x0, b)
+
+    def ratio(num, den):                               # float64 [n] -> float32 [n], 0 where either is 0
+        ok = (num != 0) & (den != 0)
+        return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(num)).float()
+
+    r = b.clone() if x0 is None else b - ops.fbp_project(x, plan)
+    s = ops.fbp_adjoint(r, plan)
+    p = s.clone()
+    gamma = s.double().pow(2).sum(dim=(1, 2))
+    q = torch.empty_like(b)
+    for _ in range(iterations):
+        ops.fbp_project(p, plan, out=q)
+        alpha = ratio(gamma, q.double().pow(2).sum(dim=(0, 2)))
+        x.addcmul_(alpha[:, None, None], p)
+        r.addcmul_(alpha[None, :, None], q, value=-1.0)
+        ops.fbp_adjoint(r, plan, out=s)
+        gamma_new = s.double().pow(2).sum(dim=(1, 2))
+        beta = ratio(gamma_new, gamma)
+        p.mul_(beta[:, None, None]).add_(s)
+        gamma = gamma_new
+    return x
 
 
 def delta_volume(vol_phi, energy_keV, voxel_m):
@@ -174,12 +295,38 @@ def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
             'energy_keV': float(ed['meanEnergy'])}
 
 
-def reconstruct(scanned, filter='ramp', circle=True):
+METHODS = ("fbp", "sirt", "cgls")
+
+
+def check_reconstruction(method, iterations, nonneg=False):
+    """The rules of reconstruct's method options (ValueError): needs no GPU."""
+    if method not in METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
+    if method == 'fbp':
+        if iterations is not None:
+            raise ValueError("iterations is an option of the iterative methods (sirt, cgls), not of fbp")
+    elif iterations is None:
+        raise ValueError("method %r needs iterations" % method)
+    else:
+        _iterations(iterations)
+    if nonneg and method != 'sirt':
+        raise ValueError("nonneg is an option of method 'sirt'")
+
+
+def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=None, nonneg=False):
     """A scan's volumes in physical units -> {bin: [n, m, m] float32 tensor}: mu (1/m) for modality 'attenuation', delta for
-    'phase' (at the scan's mean detected energy: right for one bin only, as retrieval.retrieve's default)."""
+    'phase' (at the scan's mean detected energy: right for one bin only, as retrieval.retrieve's default).  method: 'fbp'
+    (with `filter`), or 'sirt' / 'cgls' with `iterations` steps from zero (required for them, refused for 'fbp'; `filter`
+    is not used); nonneg: sirt's clamp."""
+    check_reconstruction(method, iterations, nonneg)
     out = {}
     for b, s in scanned['sinograms'].items():
-        vol = fbp(s, scanned['angles'], center=scanned['center'], filter=filter, circle=circle)
+        if method == 'fbp':
+            vol = fbp(s, scanned['angles'], center=scanned['center'], filter=filter, circle=circle)
+        elif method == 'sirt':
+            vol = sirt(s, scanned['angles'], iterations, center=scanned['center'], circle=circle, nonneg=nonneg)
+        else:
+            vol = cgls(s, scanned['angles'], iterations, center=scanned['center'], circle=circle)
         out[b] = (mu_volume(vol, scanned['voxel_m']) if scanned['modality'] == 'attenuation'
                   else delta_volume(vol, scanned['energy_keV'], scanned['voxel_m']))
     return out

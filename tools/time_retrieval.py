@@ -1,6 +1,6 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
@@ -22,6 +22,12 @@ reads 4 n x m float32 images and writes the extended grid, the filter reads and 
 --fbp times psx_fbp_f32 alone at (A, n, m) = (720, 64, 1024): the filter (pack, two rocFFT passes per row pair, the multiply)
 against the bytes it moves, and k_fbp_backproject against its two prices per voxel, angle and detector row: two 4-byte LDS
 reads (as half of two ds_read_b128 that serve four rows) at 256 B per clock and CU, and two float32 FMAs.
+
+--project times the matched pair at (720, 64, 1024) and (90, 24, 64): k_fbp_project (psx_fbp_project_f32) and
+psx_fbp_adjoint_f32 (k_fbp_pack + k_fbp_backproject at scale 1).  The projector's prices per voxel, angle and detector row: the
+bytes it stages (every angle re-reads the slice: 4 B, from cache), three 4-byte LDS reads (three candidates, each a quarter
+of a ds_read_b128 that serves four rows), two useful float32 FMAs out of the three it issues, and the float64 chain of a
+candidate (two FMAs, floor, two additions, two comparisons, one conversion: 8 quarter-rate instructions) shared by four rows.
 """
 import argparse
 import ctypes
@@ -199,6 +205,40 @@ def fbp_case(A, n, m, reps):
              fma / 1e9, fma / FMA32_PEAK * 1e6, FMA32_PEAK / 1e12, fma / t / FMA32_PEAK))
 
 
+def project_case(A, n, m, reps):
+    g = torch.Generator(device="cuda").manual_seed(A + n)
+    vol = 1.0 + torch.rand((n, m, m), device="cuda", generator=g)
+    plan = ops.FbpPlan([180.0 * a / A for a in range(A)], m, filter="none")
+    sino = torch.empty((A, n, m), device="cuda")
+    back = torch.empty_like(vol)
+    for _ in range(2):
+        ops.fbp_project(vol, plan, out=sino)
+        ops.fbp_adjoint(sino, plan, out=back)
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        ops.fbp_project(vol, plan, out=sino)
+        ops.fbp_adjoint(sino, plan, out=back)
+    torch.cuda.synchronize()
+    s = summary()
+    lib().psx_profile_enable(0)
+    per = {k: v[1] / reps * 1e3 for k, v in s.items()}       # us per call
+    work = float(m) * m * A * n
+    t = per["k_fbp_project"] * 1e-6
+    staged, lds, fma, f64 = 4.0 * work, 12.0 * work, 2.0 * work, 6.0 * work
+    print("A=%d n=%d m=%d  k_fbp_project %.1f us per call (%d launches)  staged %.1f GB (%.1f us at 8 TB/s) = %.2f of 8 TB/s;  "
+          "LDS reads %.1f GB (%.1f us at %.0f TB/s) = %.2f of the LDS rate;  %.1f G useful FMA32 (%.1f us) = %.2f of the float32 "
+          "FMA rate;  %.1f G float64 instructions (%.1f us at %.1f T/s) = %.2f of the float64 rate"
+          % (A, n, m, t * 1e6, s["k_fbp_project"][0] // reps, staged / 1e9, staged / PEAK * 1e6, staged / t / PEAK,
+             lds / 1e9, lds / LDS_PEAK * 1e6, LDS_PEAK / 1e12, lds / t / LDS_PEAK, fma / 1e9, fma / FMA32_PEAK * 1e6,
+             fma / t / FMA32_PEAK, f64 / 1e9, f64 / FMA64_PEAK * 1e6, FMA64_PEAK / 1e12, f64 / t / FMA64_PEAK))
+    tb = per["k_fbp_backproject"] * 1e-6
+    print("    psx_fbp_adjoint_f32 %.1f us per call = k_fbp_pack %.1f us + k_fbp_backproject %.1f us (%d launches): LDS reads "
+          "%.2f of the LDS rate, %.2f of the float32 FMA rate;  k_fbp_project / k_fbp_backproject = %.2f"
+          % (per["k_fbp_pack"] + per["k_fbp_backproject"], per["k_fbp_pack"], per["k_fbp_backproject"],
+             s["k_fbp_backproject"][0] // reps, 8.0 * work / tb / LDS_PEAK, 2.0 * work / tb / FMA32_PEAK, t / tb))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
@@ -206,7 +246,12 @@ def main():
     ap.add_argument("--umpa-only", action="store_true")
     ap.add_argument("--paganin", action="store_true", help="time psx_paganin_f32 only")
     ap.add_argument("--fbp", action="store_true", help="time psx_fbp_f32 only")
+    ap.add_argument("--project", action="store_true", help="time psx_fbp_project_f32 and psx_fbp_adjoint_f32 only")
     a = ap.parse_args()
+    if a.project:
+        project_case(720, 64, 1024, max(a.reps // 4, 2))
+        project_case(90, 24, 64, a.reps)
+        return
     if a.fbp:
         fbp_case(720, 64, 1024, max(a.reps // 4, 2))
         fbp_case(90, 24, 64, a.reps)

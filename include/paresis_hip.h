@@ -513,6 +513,26 @@ int psx_fbp_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *
 int psx_fbp_project_f32(psx_fbp_plan *plan, const float *vol, int n, float *sino, void *stream);
 int psx_fbp_adjoint_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *stream);
 
+/* ---- the voxel step of total-variation reconstruction on the pair ------------------------------------------------------
+ * min 0.5*|B^T x - b|^2 + lambda*TV(x) per detector row by the primal-dual hybrid gradient method with Pock and
+ * Chambolle's diagonal preconditioners (alpha = 1): TV the isotropic total variation of the slice by forward differences.
+ * The caller projects (q = B^T xbar), updates the data dual y and back-projects it (u = B y); this call does the rest of an
+ * iteration for the n slices in one launch.  With lit(i, j) the plan's circle mask (every voxel of the slice without
+ * circle), ax(i, j) = lit(i, j) and lit(i + 1, j) (i + 1 < m) the active difference along i, ay(i, j) along j, and
+ * deg(i, j) = ax(i, j) + ax(i - 1, j) + ay(i, j) + ay(i, j - 1), per voxel in float32:
+ *   gx = ax ? xbar[i+1][j] - xbar[i][j] : 0, gy likewise;  tx = fma(0.5, gx, px), ty = fma(0.5, gy, py);
+ *   nr = sqrt(fma(tx, tx, ty*ty));  (px', py') = nr > lambda ? (tx*s, ty*s), s = lambda/nr : (tx, ty);
+ *   d = ((ax(i-1,j) ? px'[i-1][j] : 0) - (ax(i,j) ? px'[i][j] : 0) + (ay(i,j-1) ? py'[i][j-1] : 0)) - (ay(i,j) ? py'[i][j] : 0);
+ *   tau = c + deg > 1e-6 ? 1/(c + deg) : 0;  x' = fma(-tau, u + d, x), then max(x', 0) if nonneg;  xbar' = fma(2, x', -x).
+ * u, c (= B 1), x, xbar, px, py are [n][m][m]; x is updated in place, xbar and p go from their _in to their _out buffers
+ * (a tile reads its neighbours' xbar and forms their p' again, the same bits), which the caller swaps.  lambda is rounded
+ * to float32; with lambda = 0 the dual comes out exactly 0.  No atomics: the same input gives the same bits, and a slice
+ * gives the bits it gives alone.  PSX_E_ARG, before any launch: a null plan or pointer, n < 1, lambda negative or not
+ * finite, xbar_out == xbar_in, px_out == px_in, py_out == py_in, xbar_out == x.  Asynchronous on the stream. */
+int psx_fbp_tv_step_f32(psx_fbp_plan *plan, int n, double lambda, int nonneg, const float *u, const float *c, float *x,
+                        const float *xbar_in, float *xbar_out, const float *px_in, const float *py_in, float *px_out,
+                        float *py_out, void *stream);
+
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------------------------------------
  * psx_profile_enable(1) clears the log and makes every kernel launch of the library record a HIP event pair on the
  * stream it is launched on; psx_profile_summary() waits for the recorded events and writes one line per kernel,

@@ -26,7 +26,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class PsxError(RuntimeError):
@@ -117,6 +117,7 @@ PROTOTYPES = {
     "psx_fbp_f32": (c_int, [_vp, _vp, c_int, _vp, _vp]),
     "psx_fbp_project_f32": (c_int, [_vp, _vp, c_int, _vp, _vp]),
     "psx_fbp_adjoint_f32": (c_int, [_vp, _vp, c_int, _vp, _vp]),
+    "psx_fbp_tv_step_f32": (c_int, [_vp, c_int, c_double, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "psx_debug_stamps": (c_int, [_vp]),
     "psx_debug_switch": (c_int, [c_char_p, c_int]),
     "psx_debug_switches_active": (c_int, [ctypes.c_char_p, c_size_t]),

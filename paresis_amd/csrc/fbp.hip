@@ -10,6 +10,8 @@
 //   k_fbp_project  the back-projector's exact transpose, volume -> sinogram, in the gather form: one workgroup per angle,
 //                  run of 64 samples and block of 4 detector rows (psx_fbp_project_f32; psx_fbp_adjoint_f32 is pack +
 //                  back-projection at scale 1)
+//   k_fbp_tv_step  the voxel step of total-variation reconstruction on the pair (psx_fbp_tv_step_f32): dual projection,
+//                  divergence, primal step, clamp and over-relaxation in one launch
 #include "fresnel_plan.hpp"
 
 #include <complex>
@@ -259,6 +261,115 @@ __global__ __launch_bounds__(256) void k_fbp_project(PrjArgs p) {
     if (nr > 3) dst[3 * (int64_t)m] = (p0.w + p1.w) + (p2.w + p3.w);
 }
 
+// ---- the total-variation step of the primal-dual solver (psx_fbp_tv_step_f32; the contract is in include/paresis_hip.h) --
+// One workgroup per 8 x 32 tile of one slice, one voxel per thread.  xbar is staged with a one-voxel halo; the projected
+// dual p' is then formed for the tile plus the row above and the column to the left -- the two neighbours whose p' enter a
+// voxel's divergence -- by ONE loop, so a value a neighbouring workgroup also forms comes from the same instructions on the
+// same inputs: the same bits.  Each voxel then reads u, c, x, xbar, px, py once (the halo comes from cache) and writes x,
+// xbar, px, py: 40 bytes.
+constexpr int TV_TW = 32;        // tile width (slice columns j): a wave covers two rows of 128 bytes
+constexpr int TV_TH = 8;         // tile height (slice rows i)
+
+struct TvArgs {
+    const float *u, *c;       // [n][m][m]: B y, and C = B 1
+    float *x;                 // in place
+    const float *xbar_in, *px_in, *py_in;
+    float *xbar_out, *px_out, *py_out;
+    float lambda;
+    int m, r0, circle, nonneg;
+};
+
+__global__ __launch_bounds__(256) void k_fbp_tv_step(TvArgs p) {
+    __shared__ float sx[TV_TH + 2][TV_TW + 2];       // xbar of (i0 - 1 + li, j0 - 1 + lj), 0 outside the slice
+    __shared__ float spx[TV_TH + 1][TV_TW + 1];      // p' of (i0 - 1 + li, j0 - 1 + lj)
+    __shared__ float spy[TV_TH + 1][TV_TW + 1];
+    __shared__ unsigned char sact[TV_TH + 1][TV_TW + 1];   // bit 0: the difference along i is active, bit 1: along j
+
+    const int tid = threadIdx.x;
+    const int m = p.m, h = m / 2;
+    const int j0 = blockIdx.x * TV_TW, i0 = blockIdx.y * TV_TH;
+    const int64_t slice = (int64_t)(p.r0 + (int)blockIdx.z) * m * m;
+    const int circle = p.circle;
+    auto lit = [m, h, circle](int i, int j) {
+        return i >= 0 && i < m && j >= 0 && j < m &&
+               (!circle || (int64_t)(i - h) * (i - h) + (int64_t)(j - h) * (j - h) <= (int64_t)h * h);
+    };
+
+    // every global load of the workgroup is issued before the first barrier, so that all of them are in flight together:
+    // two elements of the staged xbar and of the p' region per thread (340 and 297 elements), then the thread's own voxel
+    constexpr int NX = (TV_TH + 2) * (TV_TW + 2), NP = (TV_TH + 1) * (TV_TW + 1);
+    float xb_ld[2], px_ld[2], py_ld[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int e = tid + 256 * r;
+        const int xi = i0 - 1 + e / (TV_TW + 2), xj = j0 - 1 + e % (TV_TW + 2);
+        const bool xin = e < NX && xi >= 0 && xi < m && xj >= 0 && xj < m;
+        xb_ld[r] = xin ? p.xbar_in[slice + (int64_t)xi * m + xj] : 0.f;
+        const int pi = i0 - 1 + e / (TV_TW + 1), pj = j0 - 1 + e % (TV_TW + 1);
+        const bool pin = e < NP && pi >= 0 && pi < m && pj >= 0 && pj < m;
+        px_ld[r] = pin ? p.px_in[slice + (int64_t)pi * m + pj] : 0.f;
+        py_ld[r] = pin ? p.py_in[slice + (int64_t)pi * m + pj] : 0.f;
+    }
+    const int li = tid / TV_TW, lj = tid % TV_TW;
+    const int i = i0 + li, j = j0 + lj;
+    const bool own = i < m && j < m;
+    const int64_t q = slice + (int64_t)(own ? i : 0) * m + (own ? j : 0);
+    const float u = own ? p.u[q] : 0.f, c = own ? p.c[q] : 0.f, x = own ? p.x[q] : 0.f;
+
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int e = tid + 256 * r;
+        if (e < NX) sx[e / (TV_TW + 2)][e % (TV_TW + 2)] = xb_ld[r];
+    }
+    __syncthreads();
+
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int e = tid + 256 * r;
+        if (e >= NP) break;
+        const int pl = e / (TV_TW + 1), pc = e % (TV_TW + 1);
+        const int pi = i0 - 1 + pl, pj = j0 - 1 + pc;
+        float px = 0.f, py = 0.f;
+        unsigned act = 0;
+        if (pi >= 0 && pi < m && pj >= 0 && pj < m) {
+            const bool here = lit(pi, pj);
+            const bool ax = here && lit(pi + 1, pj), ay = here && lit(pi, pj + 1);
+            act = (ax ? 1u : 0u) | (ay ? 2u : 0u);
+            const float xb = sx[pl][pc];
+            const float gx = ax ? sx[pl + 1][pc] - xb : 0.f, gy = ay ? sx[pl][pc + 1] - xb : 0.f;
+            px = fmaf(0.5f, gx, px_ld[r]);
+            py = fmaf(0.5f, gy, py_ld[r]);
+            const float nr = sqrtf(fmaf(px, px, __fmul_rn(py, py)));
+            if (nr > p.lambda) {                     // nr > lambda >= 0: no division by zero
+                const float s = p.lambda / nr;
+                px = __fmul_rn(px, s);
+                py = __fmul_rn(py, s);
+            }
+        }
+        spx[pl][pc] = px;
+        spy[pl][pc] = py;
+        sact[pl][pc] = (unsigned char)act;
+    }
+    __syncthreads();
+
+    if (!own) return;
+    const unsigned here = sact[li + 1][lj + 1], up = sact[li][lj + 1] & 1u, left = sact[li + 1][lj] & 2u;
+    const float pxc = spx[li + 1][lj + 1], pyc = spy[li + 1][lj + 1];
+    p.px_out[q] = pxc;
+    p.py_out[q] = pyc;
+    // d = px'[i-1][j] - px'[i][j] + py'[i][j-1] - py'[i][j], the inactive differences' terms 0, summed left to right
+    float d = (up ? spx[li][lj + 1] : 0.f) - ((here & 1u) ? pxc : 0.f);
+    d = __fadd_rn(d, left ? spy[li + 1][lj] : 0.f);
+    d = __fsub_rn(d, (here & 2u) ? pyc : 0.f);
+    const int deg = (int)(here & 1u) + (int)(here >> 1) + (int)up + (int)(left >> 1);
+    const float cd = c + (float)deg;
+    const float tau = cd > 1e-6f ? 1.0f / cd : 0.f;
+    float xn = fmaf(-tau, __fadd_rn(u, d), x);
+    if (p.nonneg) xn = fmaxf(xn, 0.f);
+    p.x[q] = xn;
+    p.xbar_out[q] = fmaf(2.0f, xn, -x);
+}
+
 // in-place radix-2 transform of a power-of-two length in float64 (the filter table: once per plan)
 void fft_f64(std::vector<std::complex<double>> &x) {
     const size_t n = x.size();
@@ -445,6 +556,33 @@ int psx_fbp_adjoint_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol
         const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)cdiv(rows, FBP_ROWS));
         PSX_TIMED("k_fbp_backproject", st, k_fbp_backproject<<<grid, 256, 0, st>>>(a));
         if (int rc = launch_check("k_fbp_backproject")) return rc;
+    }
+    return 0;
+}
+
+int psx_fbp_tv_step_f32(psx_fbp_plan *plan, int n, double lambda, int nonneg, const float *u, const float *c, float *x,
+                        const float *xbar_in, float *xbar_out, const float *px_in, const float *py_in, float *px_out,
+                        float *py_out, void *stream) {
+    PSX_REQUIRE(plan != nullptr, "psx_fbp_tv_step_f32: null plan");
+    PSX_REQUIRE(u != nullptr && c != nullptr && x != nullptr && xbar_in != nullptr && xbar_out != nullptr && px_in != nullptr &&
+                py_in != nullptr && px_out != nullptr && py_out != nullptr, "psx_fbp_tv_step_f32: null volume pointer");
+    PSX_REQUIRE(n >= 1, "psx_fbp_tv_step_f32: n=%d slices, at least 1", n);
+    PSX_REQUIRE(std::isfinite(lambda) && lambda >= 0.0, "psx_fbp_tv_step_f32: lambda=%g is not a finite weight >= 0", lambda);
+    PSX_REQUIRE(xbar_out != xbar_in && px_out != px_in && py_out != py_in,
+                "psx_fbp_tv_step_f32: xbar_out, px_out and py_out must not be their own inputs (neighbouring tiles read them)");
+    PSX_REQUIRE(xbar_out != x, "psx_fbp_tv_step_f32: xbar_out must not be x");
+    PSX_REQUIRE((int64_t)n * plan->m * plan->m <= (int64_t)1 << 40, "psx_fbp_tv_step_f32: n=%d slices outside [1, 2^40 elements]", n);
+    hipStream_t st = (hipStream_t)stream;
+    TvArgs a;
+    a.u = u; a.c = c; a.x = x; a.xbar_in = xbar_in; a.px_in = px_in; a.py_in = py_in;
+    a.xbar_out = xbar_out; a.px_out = px_out; a.py_out = py_out;
+    a.lambda = (float)lambda; a.m = plan->m; a.circle = plan->circle; a.nonneg = nonneg != 0;
+    const int step = 32768;                          // slices per launch: grid.z stays below 65536
+    for (int r0 = 0; r0 < n; r0 += step) {
+        a.r0 = r0;
+        const dim3 grid((unsigned)cdiv(plan->m, TV_TW), (unsigned)cdiv(plan->m, TV_TH), (unsigned)(n - r0 < step ? n - r0 : step));
+        PSX_TIMED("k_fbp_tv_step", st, k_fbp_tv_step<<<grid, 256, 0, st>>>(a));
+        if (int rc = launch_check("k_fbp_tv_step")) return rc;
     }
     return 0;
 }

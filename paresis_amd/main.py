@@ -6,7 +6,7 @@
                                [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa|umpa-df --window W --search M]]
                                [--retrieve-propagation [--material NAME]]
                                [--tomography A [--tomography-modality attenuation|phase]
-                                [--tomography-method fbp|sirt|cgls --tomography-iterations K]]
+                                [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
@@ -24,7 +24,9 @@ reconstructs by filtered back-projection on rank 0 and writes tomography/mu_<exp
 the default: 1/m, from -ln(Propag/White), any --points) or tomography/delta_<expID> (phase: from the retrieved phi, the
 rules and options of --retrieve) under each bin's directory: one [n, m, m] file for --format .npy, else a directory of
 slices.  --tomography-method sirt|cgls reconstructs with --tomography-iterations K >= 1 steps of SIRT or CGLS on the matched
-projector pair instead (tomography.sirt / cgls): the methods for few angles.
+projector pair instead (tomography.sirt / cgls): the methods for few angles.  --tomography-method tv takes K steps of
+total-variation reconstruction (tomography.tv) with --tomography-weight W >= 0, relative to the sinogram's largest value: the
+model of the phantom's piecewise constant slices, for fewer angles still.
 """
 import argparse
 import datetime
@@ -36,7 +38,7 @@ import numpy as np
 
 def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
         method='lcs', window=2, search=3, propagation=False, material=None, tomography=0, tomography_modality='attenuation',
-        tomography_method='fbp', tomography_iterations=0):
+        tomography_method='fbp', tomography_iterations=0, tomography_weight=None):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
@@ -57,9 +59,11 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     retrieves with method, max_shift, dark_field, window, search and needs their positions), reconstructs every bin
     (tomography.reconstruct) and, with save, writes <bin dir>/tomography/{mu|delta}_<expID> (tomography.save_volume).
     tomography_method 'sirt' or 'cgls' with tomography_iterations >= 1 reconstructs iteratively instead of by filtered
-    back-projection ('fbp', which takes no iterations).  exp_dict['tomographyParams'] then holds the angles, the centre, the
-    voxel size, the modality, the method and its iterations, and exp_dict['tomographyVolumes'] the {bin: [n, m, m] device
-    tensor} volumes."""
+    back-projection ('fbp', which takes no iterations); 'tv' with tomography_iterations >= 1 and tomography_weight >= 0
+    (relative to the sinogram's largest value, as tomography.reconstruct takes it; refused for the other methods)
+    reconstructs with total variation.  exp_dict['tomographyParams'] then holds the angles, the centre, the voxel size, the
+    modality, the method, its iterations and its weight (None but for 'tv'), and exp_dict['tomographyVolumes'] the
+    {bin: [n, m, m] device tensor} volumes."""
     from . import tomography as tomo
     if tomography_modality not in tomo.MODALITIES:
         raise ValueError("tomography_modality must be one of %s, got %r" % (", ".join(tomo.MODALITIES), tomography_modality))
@@ -67,7 +71,9 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
         raise ValueError("tomography_modality is an option of tomography")
     if (tomography_method != 'fbp' or tomography_iterations) and not tomography:
         raise ValueError("tomography_method and tomography_iterations are options of tomography")
-    tomo.check_reconstruction(tomography_method, tomography_iterations or None)
+    if tomography_weight is not None and not tomography:
+        raise ValueError("tomography_weight is an option of tomography")
+    tomo.check_reconstruction(tomography_method, tomography_iterations or None, weight=tomography_weight)
     if int(tomography) < 0 or int(tomography) > _lib_max_angles():
         raise ValueError("tomography takes 1 to %d angles, got %r" % (_lib_max_angles(), tomography))
     if tomography and tomography_modality == 'phase':
@@ -224,9 +230,11 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
             keep = TRACKERS[(method, bool(dark_field))].options + ('method', 'dark_field')
             options = {k: v for k, v in options.items() if k in keep}
         scanned = tomo.scan(experiment, angles, modality=tomography_modality, **options)
-        volumes = tomo.reconstruct(scanned, method=tomography_method, iterations=tomography_iterations or None)
+        volumes = tomo.reconstruct(scanned, method=tomography_method, iterations=tomography_iterations or None,
+                                   weight=tomography_weight)
         exp_dict['tomographyParams'] = {k: scanned[k] for k in ('angles', 'center', 'voxel_m', 'modality', 'energy_keV')}
-        exp_dict['tomographyParams'].update(method=tomography_method, iterations=int(tomography_iterations))
+        exp_dict['tomographyParams'].update(method=tomography_method, iterations=int(tomography_iterations),
+                                             weight=None if tomography_weight is None else float(tomography_weight))
         if save:
             nbin = len(volumes)
             thresholds = [experiment.mySource.mySpectrum[0][0]] + list(experiment.myDetector.det_param['myBinsThersholds'])
@@ -279,10 +287,14 @@ def main(argv=None):
     ap.add_argument("--tomography-modality", default="attenuation", choices=["attenuation", "phase"],
                     help="--tomography: mu from -ln(Propag/White) (default), or delta from the retrieved phi (the rules and "
                          "options of --retrieve)")
-    ap.add_argument("--tomography-method", default="fbp", choices=["fbp", "sirt", "cgls"],
-                    help="--tomography: filtered back-projection (default), or --tomography-iterations steps of SIRT or CGLS")
+    ap.add_argument("--tomography-method", default="fbp", choices=["fbp", "sirt", "cgls", "tv"],
+                    help="--tomography: filtered back-projection (default), or --tomography-iterations steps of SIRT, CGLS or "
+                         "total-variation reconstruction (tv, with --tomography-weight)")
     ap.add_argument("--tomography-iterations", type=int, default=0, metavar="K",
-                    help="--tomography-method sirt|cgls: the number of iterations (>= 1)")
+                    help="--tomography-method sirt|cgls|tv: the number of iterations (>= 1)")
+    ap.add_argument("--tomography-weight", type=float, default=None, metavar="W",
+                    help="--tomography-method tv: the weight of the total variation, relative to the sinogram's largest "
+                         "value (>= 0)")
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -310,12 +322,21 @@ def main(argv=None):
         ap.error("--tomography-method is an option of --tomography")
     if a.tomography_iterations != 0 and not a.tomography:
         ap.error("--tomography-iterations is an option of --tomography")
+    if a.tomography_weight is not None and not a.tomography:
+        ap.error("--tomography-weight is an option of --tomography")
+    if (a.tomography_method == "tv") != (a.tomography_weight is not None):
+        ap.error("--tomography-weight W >= 0 goes with --tomography-method tv, and only with it")
+    if a.tomography_weight is not None and not (0 <= a.tomography_weight < float("inf")):
+        ap.error("--tomography-weight takes a finite weight >= 0")
+    if a.tomography_method == "tv" and a.tomography_iterations < 1:
+        ap.error("--tomography-method tv needs --tomography-iterations K >= 1")
     if a.tomography_iterations < 0 or (a.tomography_method == "fbp") != (a.tomography_iterations == 0):
         ap.error("--tomography-iterations K >= 1 goes with --tomography-method sirt or cgls, and only with them")
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
         material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality,
-        tomography_method=a.tomography_method, tomography_iterations=a.tomography_iterations)
+        tomography_method=a.tomography_method, tomography_iterations=a.tomography_iterations,
+        tomography_weight=a.tomography_weight)
 
 
 if __name__ == "__main__":

@@ -1301,3 +1301,41 @@ def fbp_adjoint(sino, plan, out=None):
     'none' plan ops.fbp is float32(pi/(2A)) times it.  The plan's filter is ignored.  out: a caller-owned [n, m, m]
     float32 tensor.  Calls on one plan are ordered on the current stream (they share its buffer)."""
     return _fbp_call("psx_fbp_adjoint_f32", plan, sino, "sino", out, False)
+
+
+def fbp_tv_step(plan, weight, nonneg, u, c, x, xbar_in, xbar_out, px_in, py_in, px_out, py_out):
+    """The voxel step of total-variation reconstruction on the plan's projector pair (psx_fbp_tv_step_f32; the contract is
+    in include/paresis_hip.h), one launch for the n slices: the TV dual (px_in, py_in) takes its step of 1/2 along the
+    forward differences of xbar_in and is projected onto |p| <= weight -> (px_out, py_out); x, in place, takes its step
+    x - tau*(u + grad^T p'), tau = 1/(c + the voxel's number of active differences), and is clamped at 0 with nonneg;
+    xbar_out = 2 x' - x.  u = B y and c = B 1 (ops.fbp_adjoint).  All nine are [n, m, m] float32 tensors in HBM on the
+    plan's device, m the plan's; an _out tensor shares no storage with any other (neighbouring tiles read the _in ones).
+    Every check comes before the device is touched.  -> (x, xbar_out, px_out, py_out)."""
+    if not isinstance(plan, FbpPlan):
+        raise PsxError("plan must be an ops.FbpPlan, got %r" % type(plan))
+    try:
+        weight = float(weight)
+    except (TypeError, ValueError):
+        raise PsxError("weight must be a number, got %r" % (weight,))
+    if not (weight >= 0.0 and weight != float("inf")):
+        raise PsxError("weight must be finite and >= 0, got %r" % (weight,))
+    m = plan.m
+    _need(x, torch.float32, "x")
+    if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] != m or x.shape[2] != m:
+        raise PsxError("x has shape %s, the plan takes [n >= 1, %d, %d]" % (tuple(x.shape), m, m))
+    shape = tuple(x.shape)
+    named = (("u", u), ("c", c), ("x", x), ("xbar_in", xbar_in), ("px_in", px_in), ("py_in", py_in),
+             ("xbar_out", xbar_out), ("px_out", px_out), ("py_out", py_out))
+    for nm, t in named:
+        _need(t, torch.float32, nm, shape)
+        if t.device != plan.device:
+            raise PsxError("%s is on %s, the plan on %s" % (nm, t.device, plan.device))
+    for k, (nm, t) in enumerate(named[6:]):
+        for other, o in named[:6 + k]:
+            if t.data_ptr() == o.data_ptr():
+                raise PsxError("%s shares its storage with %s: the step reads its neighbours' inputs" % (nm, other))
+    with torch.cuda.device(plan.device):
+        check(lib().psx_fbp_tv_step_f32(plan._h, shape[0], c_double(weight), int(bool(nonneg)), _ptr(u), _ptr(c), _ptr(x),
+                                        _ptr(xbar_in), _ptr(xbar_out), _ptr(px_in), _ptr(py_in), _ptr(px_out), _ptr(py_out),
+                                        _stream()), "psx_fbp_tv_step_f32")
+    return x, xbar_out, px_out, py_out

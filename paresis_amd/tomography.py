@@ -8,6 +8,8 @@
     back_project(sinogram, angles_deg, ...)  B^T vol, the exact transpose of fbp's interpolation, and B sinogram, unscaled
     sirt(sinogram, angles_deg, iterations, ..., nonneg)   SIRT and CGLS on min |B^T x - b|: what few angles call for,
     cgls(sinogram, angles_deg, iterations, ...)           where filtered back-projection streaks
+    tv(sinogram, angles_deg, iterations, weight, ..., nonneg)   min 0.5 |B^T x - b|^2 + weight TV(x): the model of a piecewise
+    tv_objective(vol, sinogram, angles_deg, weight, ...)        constant object such as the phantom (ops.fbp_tv_step)
     delta_volume(vol, energy_keV, voxel_m)   phi = -k * integral(delta) dl  ->  delta = -vol/(k*voxel), k = getk(E)
     mu_volume(vol, voxel_m)                  -ln T = integral(mu) dl         ->  mu = vol/voxel (1/m)
     project(sample, energy_keV, angles_deg, dims, pixel_um)   the phantom's ideal sinograms phi and -ln T on the study grid
@@ -21,7 +23,7 @@ three-dimensional description -- 13 material discs on a slice, projected at Samp
 every other sample.
 
     python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase]
-                               [--tomography-method fbp|sirt|cgls --tomography-iterations K] ...
+                               [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]] ...
 """
 import os
 
@@ -178,6 +180,75 @@ def cgls(sinogram, angles_deg, iterations, center=None, circle=True, x0=None):
     return x
 
 
+def _weight(weight):
+    try:
+        w = float(weight)
+    except (TypeError, ValueError):
+        w = float("nan")
+    if isinstance(weight, bool) or not np.isfinite(w) or w < 0:
+        raise ValueError("weight must be a finite number >= 0, got %r" % (weight,))
+    return w
+
+
+def _lit(m, circle, device):
+    """The plan's mask as an [m, m] bool tensor: (i - h)^2 + (j - h)^2 <= h^2, h = m // 2; all true without circle."""
+    import torch
+    d2 = (torch.arange(m, device=device) - m // 2) ** 2
+    return (d2[:, None] + d2[None, :] <= (m // 2) ** 2) if circle else torch.ones((m, m), dtype=torch.bool, device=device)
+
+
+def tv(sinogram, angles_deg, iterations, weight, center=None, circle=True, nonneg=False, x0=None):
+    """`iterations` steps of the primal-dual hybrid gradient method on min 0.5 |B^T x - b|^2 + weight * TV(x) (with x >= 0
+    if nonneg) for the [A, n, m] sinogram b -> the [n, m, m] float32 volume; every detector row is its own problem.  TV is
+    the isotropic total variation of a slice by forward differences between the voxels inside the circle (all, without
+    circle); weight (lambda) is in the sinogram's own unit, finite and >= 0 (ValueError otherwise): 0 leaves least squares.
+    The steps are Pock and Chambolle's diagonal preconditioners (alpha = 1), which need no operator norm: s1 = 1/R for the
+    data dual y, R = B^T 1; 1/2 for the TV dual p; tau = 1/(C + deg) for x, C = B 1 and deg the voxel's number of
+    differences (reciprocals where the sum exceeds 1e-6, 0 elsewhere, so a voxel outside the circle keeps its start).
+    Per iteration: q = B^T xbar (ops.fbp_project); y <- (y + s1 (q - b))/(1 + s1) (torch); u = B y (ops.fbp_adjoint); then
+    ops.fbp_tv_step, one kernel: p <- the projection of p + grad(xbar)/2 onto |p| <= weight, x <- x - tau (u + grad^T p),
+    max(x, 0) if nonneg, xbar <- 2 x_new - x_old.  On the module's 'none' plan.  x0: the start of x and xbar, zeros by
+    default (not modified).  Held for the call: nine volume-sized arrays (x, xbar and p = (px, py) twice each -- the step
+    reads its neighbours, so they go from one buffer to the other --, u and C) and, besides b, four sinogram-sized ones
+    (y, q, s1, 1 + s1)."""
+    import torch
+    from . import ops
+    iterations, weight = _iterations(iterations), _weight(weight)
+    b, angles = _sinogram(sinogram, angles_deg)
+    plan = _plan(b.device, angles, int(b.shape[2]), center, 'none', circle)
+    x = _start(x0, b)
+    xbar, xbar_new = x.clone(), torch.ones_like(x)
+    q = torch.ones_like(b)
+    s1 = _reciprocal(ops.fbp_project(xbar_new, plan))
+    c = ops.fbp_adjoint(q, plan)
+    den = s1 + 1.0
+    y, u = torch.zeros_like(b), torch.empty_like(x)
+    px, py, px_new, py_new = torch.zeros_like(x), torch.zeros_like(x), torch.empty_like(x), torch.empty_like(x)
+    for _ in range(iterations):
+        ops.fbp_project(xbar, plan, out=q)
+        q.sub_(b).mul_(s1)
+        y.add_(q).div_(den)
+        ops.fbp_adjoint(y, plan, out=u)
+        ops.fbp_tv_step(plan, weight, nonneg, u, c, x, xbar, xbar_new, px, py, px_new, py_new)
+        xbar, xbar_new, px, px_new, py, py_new = xbar_new, xbar, px_new, px, py_new, py
+    return x
+
+
+def tv_objective(vol, sinogram, angles_deg, weight, center=None, circle=True):
+    """What tv minimises, per detector row: 0.5 |B^T vol - b|^2 + weight * TV(vol) -> a float64 [n] tensor on the volume's
+    device.  The projection is ops.fbp_project's; the differences and the sums are torch's, in float64."""
+    import torch
+    weight = _weight(weight)
+    b, angles = _sinogram(sinogram, angles_deg)
+    r = forward_project(vol, angles, center=center, circle=circle).double() - b.double()
+    v = vol.double()
+    lit = _lit(int(vol.shape[2]), circle, vol.device)
+    gx, gy = torch.zeros_like(v), torch.zeros_like(v)
+    gx[:, :-1, :] = (v[:, 1:, :] - v[:, :-1, :]) * (lit[:-1, :] & lit[1:, :])
+    gy[:, :, :-1] = (v[:, :, 1:] - v[:, :, :-1]) * (lit[:, :-1] & lit[:, 1:])
+    return 0.5 * r.pow(2).sum(dim=(0, 2)) + weight * torch.sqrt(gx ** 2 + gy ** 2).sum(dim=(1, 2))
+
+
 def delta_volume(vol_phi, energy_keV, voxel_m):
     """The refractive index decrement per voxel from the back-projection of a phase sinogram (radians): the chain's phase is
     phi = -k*sum(delta*t) (Sample.setWaveRT), k = getk(E) with the chain's constants, so delta = -vol/(k*voxel_m)."""
@@ -296,12 +367,13 @@ def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
 
 
 METHODS = ("fbp", "sirt", "cgls")
+REGULARISED_METHODS = ("tv",)
 
 
-def check_reconstruction(method, iterations, nonneg=False):
+def check_reconstruction(method, iterations, nonneg=False, weight=None):
     """The rules of reconstruct's method options (ValueError): needs no GPU."""
-    if method not in METHODS:
-        raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
+    if method not in METHODS + REGULARISED_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS + REGULARISED_METHODS), method))
     if method == 'fbp':
         if iterations is not None:
             raise ValueError("iterations is an option of the iterative methods (sirt, cgls), not of fbp")
@@ -309,22 +381,33 @@ def check_reconstruction(method, iterations, nonneg=False):
         raise ValueError("method %r needs iterations" % method)
     else:
         _iterations(iterations)
-    if nonneg and method != 'sirt':
+    if method in REGULARISED_METHODS:
+        if weight is None:
+            raise ValueError("method %r needs weight" % method)
+        _weight(weight)
+    elif weight is not None:
+        raise ValueError("weight is an option of method 'tv'")
+    if nonneg and method not in ('sirt', 'tv'):
         raise ValueError("nonneg is an option of method 'sirt'")
 
 
-def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=None, nonneg=False):
+def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=None, nonneg=False, weight=None):
     """A scan's volumes in physical units -> {bin: [n, m, m] float32 tensor}: mu (1/m) for modality 'attenuation', delta for
     'phase' (at the scan's mean detected energy: right for one bin only, as retrieval.retrieve's default).  method: 'fbp'
     (with `filter`), or 'sirt' / 'cgls' with `iterations` steps from zero (required for them, refused for 'fbp'; `filter`
-    is not used); nonneg: sirt's clamp."""
-    check_reconstruction(method, iterations, nonneg)
+    is not used), or 'tv' with `iterations` steps and `weight` (both required, weight refused for the others); nonneg: the
+    clamp of sirt and tv.  weight is RELATIVE: tv runs with weight * max|sinogram| per bin, so that scaling a sinogram
+    scales its volume and one weight serves -ln T and radians alike."""
+    check_reconstruction(method, iterations, nonneg, weight)
     out = {}
     for b, s in scanned['sinograms'].items():
         if method == 'fbp':
             vol = fbp(s, scanned['angles'], center=scanned['center'], filter=filter, circle=circle)
         elif method == 'sirt':
             vol = sirt(s, scanned['angles'], iterations, center=scanned['center'], circle=circle, nonneg=nonneg)
+        elif method == 'tv':
+            vol = tv(s, scanned['angles'], iterations, float(weight) * float(s.abs().max()), center=scanned['center'],
+                     circle=circle, nonneg=nonneg)
         else:
             vol = cgls(s, scanned['angles'], iterations, center=scanned['center'], circle=circle)
         out[b] = (mu_volume(vol, scanned['voxel_m']) if scanned['modality'] == 'attenuation'

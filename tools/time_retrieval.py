@@ -1,6 +1,6 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project] [--tv]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
@@ -28,6 +28,12 @@ psx_fbp_adjoint_f32 (k_fbp_pack + k_fbp_backproject at scale 1).  The projector'
 bytes it stages (every angle re-reads the slice: 4 B, from cache), three 4-byte LDS reads (three candidates, each a quarter
 of a ds_read_b128 that serves four rows), two useful float32 FMAs out of the three it issues, and the float64 chain of a
 candidate (two FMAs, floor, two additions, two comparisons, one conversion: 8 quarter-rate instructions) shared by four rows.
+
+--tv times k_fbp_tv_step (psx_fbp_tv_step_f32), the voxel step of total-variation reconstruction, at (n, m) = (8, 512) and
+(2, 2048): per voxel it reads six floats and writes four, 40 B, set against the HBM rate a copy achieves (6.3 TB/s of the
+8 TB/s peak, MI355X_MICROARCH.md).  Beside it: the same step written with torch operations (torch_tv_step below, kept in
+this tool only: the baseline the kernel replaces), timed with a host clock around a synchronised loop, and the share of a
+whole iteration of tomography.tv at 90 angles that the two projector calls take.
 """
 import argparse
 import ctypes
@@ -239,6 +245,96 @@ def project_case(A, n, m, reps):
              s["k_fbp_backproject"][0] // reps, 8.0 * work / tb / LDS_PEAK, 2.0 * work / tb / FMA32_PEAK, t / tb))
 
 
+HBM_ACHIEVABLE = 6.3e12                                 # bytes per second: a float4 copy (MI355X_MICROARCH.md)
+
+
+def torch_tv_step(lam, nonneg, ax, ay, tau, u, x, xbar, px, py):
+    """psx_fbp_tv_step_f32's arithmetic with torch operations -> (x', xbar', px', py').  ax, ay: the active differences as
+    float32 [m, m] masks; tau: the primal step [n, m, m]."""
+    gx, gy = torch.zeros_like(xbar), torch.zeros_like(xbar)
+    gx[:, :-1, :] = xbar[:, 1:, :] - xbar[:, :-1, :]
+    gy[:, :, :-1] = xbar[:, :, 1:] - xbar[:, :, :-1]
+    tx, ty = px + 0.5 * (gx * ax), py + 0.5 * (gy * ay)
+    nr = torch.sqrt(tx * tx + ty * ty)
+    s = torch.where(nr > lam, lam / nr.clamp(min=1e-30), torch.ones_like(nr))
+    pxn, pyn = tx * s, ty * s
+    a, b = pxn * ax, pyn * ay
+    d = -a - b
+    d[:, 1:, :] += a[:, :-1, :]
+    d[:, :, 1:] += b[:, :, :-1]
+    xn = x - tau * (u + d)
+    if nonneg:
+        xn = xn.clamp(min=0)
+    return xn, 2 * xn - x, pxn, pyn
+
+
+def _host_us(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e6
+
+
+def tv_case(n, m, A, reps):
+    from paresis_amd import tomography
+    g = torch.Generator(device="cuda").manual_seed(n + m)
+    rand = lambda: torch.rand((n, m, m), device="cuda", generator=g) - 0.5
+    plan = ops.FbpPlan([180.0 * a / A for a in range(A)], m, filter="none")
+    u, x, xbar, px, py = rand(), rand(), rand(), rand(), rand()
+    c = ops.fbp_adjoint(torch.ones((A, n, m), device="cuda"), plan)
+    xbar2, px2, py2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    lam = 0.3
+    for _ in range(3):
+        ops.fbp_tv_step(plan, lam, True, u, c, x.clone(), xbar, xbar2, px, py, px2, py2)
+    torch.cuda.synchronize()
+    xs = x.clone()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        ops.fbp_tv_step(plan, lam, True, u, c, xs, xbar, xbar2, px, py, px2, py2)
+    torch.cuda.synchronize()
+    t = summary()["k_fbp_tv_step"]
+    lib().psx_profile_enable(0)
+    t = t[1] / t[0] * 1e-3
+    price = 40.0 * n * m * m
+    print("n=%d m=%d  k_fbp_tv_step %.1f us  price %.1f MB (%.1f us at %.1f TB/s) = %.2f of the achievable HBM rate, %.2f of 8 TB/s"
+          % (n, m, t * 1e6, price / 1e6, price / HBM_ACHIEVABLE * 1e6, HBM_ACHIEVABLE / 1e12, price / t / HBM_ACHIEVABLE,
+             price / t / PEAK))
+    lit = tomography._lit(m, True, x.device)
+    ax, ay = torch.zeros((m, m), device="cuda"), torch.zeros((m, m), device="cuda")
+    ax[:-1, :] = (lit[:-1, :] & lit[1:, :]).float()
+    ay[:, :-1] = (lit[:, :-1] & lit[:, 1:]).float()
+    deg = ax + ay
+    deg[1:, :] += ax[:-1, :]
+    deg[:, 1:] += ay[:, :-1]
+    tau = tomography._reciprocal(c + deg)
+    want = ops.fbp_tv_step(plan, lam, True, u, c, x.clone(), xbar, xbar2, px, py, px2, py2)
+    got = torch_tv_step(lam, True, ax, ay, tau, u, x, xbar, px, py)
+    worst = max(float((a - b).abs().max()) for a, b in zip(got, want))
+    t_kernel = _host_us(lambda: ops.fbp_tv_step(plan, lam, True, u, c, xs, xbar, xbar2, px, py, px2, py2), reps)
+    t_torch = _host_us(lambda: torch_tv_step(lam, True, ax, ay, tau, u, x, xbar, px, py), reps)
+    print("    the step with torch operations %.1f us per call (host clock; the kernel the same way %.1f us): %.1f times the kernel; "
+          "largest difference between the two %.1e" % (t_torch, t_kernel, t_torch / t_kernel, worst))
+    b = ops.fbp_project(x, plan)
+    tomography.tv(b, plan.theta, 2, lam, nonneg=True)
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    tomography.tv(b, plan.theta, reps, lam, nonneg=True)
+    torch.cuda.synchronize()
+    s = summary()
+    lib().psx_profile_enable(0)
+    per = {k: v[1] / reps * 1e3 for k, v in s.items()}        # us per iteration (the two set-up projections are in: 2/reps more)
+    proj = per["k_fbp_project"] + per["k_fbp_pack"] + per["k_fbp_backproject"]
+    t_iter = _host_us(lambda: tomography.tv(b, plan.theta, reps, lam, nonneg=True), 1) / reps
+    print("    tomography.tv at %d angles: %.1f us per iteration (host clock) = projectors %.1f us (project %.1f, adjoint %.1f) = %.2f "
+          "of it + k_fbp_tv_step %.1f us = %.3f + torch's dual update and launches"
+          % (A, t_iter, proj, per["k_fbp_project"], per["k_fbp_pack"] + per["k_fbp_backproject"], proj / t_iter,
+             per["k_fbp_tv_step"], per["k_fbp_tv_step"] / t_iter))
+    plan.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
@@ -247,7 +343,12 @@ def main():
     ap.add_argument("--paganin", action="store_true", help="time psx_paganin_f32 only")
     ap.add_argument("--fbp", action="store_true", help="time psx_fbp_f32 only")
     ap.add_argument("--project", action="store_true", help="time psx_fbp_project_f32 and psx_fbp_adjoint_f32 only")
+    ap.add_argument("--tv", action="store_true", help="time psx_fbp_tv_step_f32 and an iteration of tomography.tv only")
     a = ap.parse_args()
+    if a.tv:
+        tv_case(8, 512, 90, a.reps)
+        tv_case(2, 2048, 90, max(a.reps // 2, 2))
+        return
     if a.project:
         project_case(720, 64, 1024, max(a.reps // 4, 2))
         project_case(90, 24, 64, a.reps)

@@ -360,6 +360,37 @@ int psx_contrast_phantom_f32(const psx_phantom_desc *desc, double *lines, float 
 /* Debug/test: the 13 slices as bytes (0/1), [13][dimY][dimY] device buffer.  Small grids only. */
 int psx_contrast_phantom_slices_u8(const psx_phantom_desc *desc, uint8_t *slices, void *stream);
 
+/* ---- labelled voxel volume: the phantom's projection model fed from memory ----------------------------------------------
+ * labels [n][m][m] uint8, DEVICE: labels[z] is the slice of height z in the orientation of the phantom's slices and of
+ * psx_fbp_f32's volume.  Label 0 is empty, label k + 1 is material k < nmat (a label above nmat counts as empty).
+ * geom [nmat][dimX][dimY] float32 (metres) and, unless NULL, lines [nmat][dimX][dimY] float64 (voxels), DEVICE, written.
+ * The host passes cos and sin of np.deg2rad(angle), c = m / 2 (integer), off_x = -c (cos + sin - 1),
+ * off_y = -c (cos - sin - 1), s = study pixel / voxel and the voxel in metres.
+ *   Row of study pixel (x, y):  z = n / 2 + (int)floor((double)(x - dimX / 2) * s + 0.5); outside [0, n) every material is 0.
+ *   Line integral, in float64 with every product and sum rounded on its own:  cpos = (double)(y - dimY / 2) * s + (double)c,
+ *   and for r = 0 .. m - 1 in ascending order  X = cos*cpos + sin*r + off_x,  Y = (-sin*cpos) + cos*r + off_y,
+ *   minr, minc their floors and maxr, maxc their ceils, dr = Y - minr, dc = X - minc, tl, tr, bl, br the indicator of
+ *   material k at (minr, minc), (minr, maxc), (maxr, minc), (maxr, maxc), 0 outside the slice:
+ *     acc_k += (1 - dr) * ((1 - dc) * tl + dc * tr) + dr * ((1 - dc) * bl + dc * br)
+ *   -- the phantom's expressions term for term (scikit-image radon of the slice, circle=True).
+ *   lines[k][x][y] = acc_k,  geom[k][x][y] = (float)(acc_k * voxel_m).
+ * At s = 1, m = dimY, n = dimX, cpos is exactly y and z exactly x.  The kernel applies no mask: radon's circle is the
+ * loader's job, which refuses a label where (i - c)^2 + (j - c)^2 > c^2; the rotation axis is then study column dimY / 2.
+ * box: DEVICE [n][4] int32 (row0, row1, col0, col1), half-open, outside of which slice z holds only label 0 (row1 <= row0:
+ * an empty slice), or NULL.  It only spares steps whose four labels are empty: exact zeros.
+ * Limits: 1 <= m <= 8192, 1 <= n <= 65535, 1 <= nmat <= PSX_VOLUME_MAX_MAT, 1 <= dimY <= 2^20, 1 <= dimX <= 2^24,
+ * nmat*dimX*dimY <= 2^40, s finite in [1/64, 64], voxel_m finite. */
+#define PSX_VOLUME_MAX_MAT 16
+typedef struct {
+    int n, m, nmat;
+    int dimX, dimY;
+    double cos_a, sin_a, off_x, off_y;   /* radon's inverse map about c = m / 2 */
+    double s;                            /* study pixel / voxel */
+    double voxel_m;
+    const int32_t *box;                  /* DEVICE [n][4], or NULL */
+} psx_volume_desc;
+int psx_volume_project_u8(const psx_volume_desc *desc, const uint8_t *labels, double *lines_or_null, float *geom, void *stream);
+
 /* ---- phase retrieval of speckle image stacks (no counterpart in the reference: its images' consumer) -----------------
  * LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021) over K positions of one energy bin: per pixel,
  *   R_k ~ x0*S_k + x1*g0_k + x2*g1_k,  (g0, g1) = np.gradient(R_k) (unit spacing, edge_order=1, float32 differences),

@@ -52,6 +52,10 @@ class Sample:
             self.mySampleFile = _xml.child_text(node, "mySampleFile")
         if fn == "loadSampleGeometryFromImages":
             self.myGeometryFolder = _xml.child_text(node, "myGeometryFolder")
+        if fn == "getVolumeFromFile":                    # extension: a labelled voxel volume (Samples/getVolumeFromFile.py)
+            self.myVoxelSize = float(_xml.child_text(node, "myVoxelSize"))
+            if _xml.has_child(node, "myVolumeFile"):     # or myVolume set in memory
+                self.myVolumeFile = _xml.child_text(node, "myVolumeFile")
         for tag in ("myRadius", "myOrientation"):
             if _xml.has_child(node, tag):
                 setattr(self, tag, float(_xml.child_text(node, tag)))
@@ -83,6 +87,9 @@ class AnalyticalSample(Sample):
         self._dev_src = None
         self.myAngle = 30          # projection angle (degrees) of generateContrastPhantom: the reference's constant (SAM:221);
                                    # tomography.project / scan turn the phantom by setting it before getMyGeometry
+        self.myVolume = None       # getVolumeFromFile: uint8 labels [n, m, m], a numpy array or a CUDA tensor (else myVolumeFile)
+        self._dev_volume = None
+        self._dev_volume_src = None
 
     # ------------------------------------------------------------------------------------------ geometry
     def getMyGeometry(self, studyDimensions, studyPixelSize, oversamp, pointNum=0, number_of_positions=0):
@@ -114,6 +121,12 @@ class AnalyticalSample(Sample):
                 self.myGeometry, self.geom_parameters = generateContrastPhantom(dimX, dimY, studyPixelSize,
                                                                                    angle=getattr(self, "myAngle", 30))
                 return
+            if fn == "getVolumeFromFile":                                       # extension, on the GPU
+                from .Samples.getVolumeFromFile import getVolumeFromFile
+                self.myGeometry, self.geom_parameters = getVolumeFromFile(self.volume_dev(), len(self.myMaterials),
+                                                                             self.myVoxelSize, dimX, dimY, studyPixelSize,
+                                                                             angle=getattr(self, "myAngle", 30))
+                return
             if fn == "loadSampleGeometryFromImages":                            # SAM:222-225
                 geom, self.geom_parameters = geometry.load_sample_geometry_from_images(self.myGeometryFolder, dimX, dimY,
                                                                                        studyPixelSize)
@@ -136,6 +149,20 @@ class AnalyticalSample(Sample):
             self.myGeometry = np.full((1, dimX, dimY), self.myThickness * 1e-6, dtype=np.float32)   # SAM:239-243
             return
         raise ValueError("Could not define sample geometry")
+
+    def volume_dev(self):
+        """The label volume of getVolumeFromFile, checked and uploaded once per myVolume object (read from myVolumeFile
+        when none is set) and per number of materials: every angle of a scan projects the same upload."""
+        from .Samples.getVolumeFromFile import upload_volume
+        if getattr(self, "myVolume", None) is None:
+            if not getattr(self, "myVolumeFile", ""):
+                raise ValueError("sample %r has neither myVolume nor myVolumeFile" % self.myName)
+            self.myVolume = np.load(self.myVolumeFile)
+        v = self.__dict__.get("_dev_volume")
+        if v is None or self.__dict__.get("_dev_volume_src") is not self.myVolume or v.nmat != len(self.myMaterials):
+            v = self._dev_volume = upload_volume(self.myVolume, len(self.myMaterials))
+            self._dev_volume_src = self.myVolume
+        return v
 
     def geometry_dev(self):
         """The thickness stack as a float32 tensor in HBM (uploaded once per myGeometry object)."""

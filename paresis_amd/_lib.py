@@ -19,6 +19,7 @@ PSX_MAX_PAGANIN = 64
 PSX_FBP_MAX_ANGLES, PSX_FBP_MAX_M = 4096, 8192
 FBP_FILTERS = {"ramp": 0, "hann": 1, "none": 2}      # PSX_FBP_RAMP / _HANN / _NONE
 PSX_PHANTOM_TUBES = 12
+PSX_VOLUME_MAX_MAT = 16
 PSX_MAX_DIST = 8
 PSX_MAX_POISSON = 8
 PSX_MAX_DETECT = 4
@@ -26,7 +27,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class PsxError(RuntimeError):
@@ -102,6 +103,7 @@ PROTOTYPES = {
                                         _vp, _vp, c_float, _vp]),
     "psx_contrast_phantom_f32": (c_int, [_vp, _vp, _vp, _vp]),
     "psx_contrast_phantom_slices_u8": (c_int, [_vp, _vp, _vp]),
+    "psx_volume_project_u8": (c_int, [_vp, _vp, _vp, _vp, _vp]),
     "psx_lcs_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp]),
     "psx_lcs_df_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp, _vp]),
     "psx_umpa_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, _vp]),

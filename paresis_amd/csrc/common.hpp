@@ -183,6 +183,33 @@ inline void map_table(const float *(&T)[PSX_MAX_MAT], const Mats &m) {
         default: { constexpr int NM = 8; __VA_ARGS__; } break; \
     }
 
+// ---- the rows of a projected line that can reach a window (phantom.hip, volume.hip) ------------------------------------
+// Rows r of [0, dimY) where lo - 1 < a + b r < hi + 1 may hold, widened by 2 rows; r0 <= r1, both in [0, dimY].  The
+// sample points of the rows outside are more than a pixel outside (lo, hi), which no rounding of the loop's own
+// (a' + b r) + off (a few ulps of a value of ~1e4) can close: their four neighbours lie outside the window, and the terms
+// skipped are exact zeros.  A slope of ~1e-16 (a multiple of 90 degrees) gives bounds of ~1e17: clamped before any cast.
+__device__ inline void row_span(double a, double b, double lo, double hi, double dimY, double &r0, double &r1) {
+    lo -= 1.0;
+    hi += 1.0;
+    if (b == 0.0) {
+        if (lo < a && a < hi) {
+            r0 = 0.0;
+            r1 = dimY;
+        } else {
+            r0 = r1 = 0.0;
+        }
+        return;
+    }
+    double u = (lo - a) / b, v = (hi - a) / b;
+    if (u > v) {
+        const double w = u;
+        u = v;
+        v = w;
+    }
+    r0 = fmin(fmax(0.0, floor(u) - 2.0), dimY);
+    r1 = fmax(fmin(dimY, ceil(v) + 3.0), 0.0);
+}
+
 // diagnostic phase-timestamp buffer (psx_debug_stamps); null in every timed run
 extern unsigned long long *g_stamps;
 

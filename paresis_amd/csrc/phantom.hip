@@ -34,32 +34,6 @@ __device__ double slice_value(const psx_phantom_desc &d, int m, int64_t i, int64
     return 1.0;
 }
 
-// Rows r of [0, dimY) where lo - 1 < a + b r < hi + 1 may hold, widened by 2 rows; r0 <= r1, both in [0, dimY].  The
-// sample points of the rows outside are more than a pixel outside (lo, hi), which no rounding of the loop's own
-// (a' + b r) + off (a few ulps of a value of ~1e4) can close: their four neighbours lie outside the window, and the terms
-// skipped are exact zeros.  A slope of ~1e-16 (a multiple of 90 degrees) gives bounds of ~1e17: clamped before any cast.
-__device__ void row_span(double a, double b, double lo, double hi, double dimY, double &r0, double &r1) {
-    lo -= 1.0;
-    hi += 1.0;
-    if (b == 0.0) {
-        if (lo < a && a < hi) {
-            r0 = 0.0;
-            r1 = dimY;
-        } else {
-            r0 = r1 = 0.0;
-        }
-        return;
-    }
-    double u = (lo - a) / b, v = (hi - a) / b;
-    if (u > v) {
-        const double w = u;
-        u = v;
-        v = w;
-    }
-    r0 = fmin(fmax(0.0, floor(u) - 2.0), dimY);
-    r1 = fmax(fmin(dimY, ceil(v) + 3.0), 0.0);
-}
-
 // One thread per (slice m, output column c): lines[m][c] = sum over rows r in order of the bilinear sample of slice m at
 // column x = cos c + sin r + off_x, row y = -sin c + cos r + off_y -- skimage 0.18 radon: warp(..., order=1, mode='constant',
 // clip=False) of the slice, then sum(0).  Only the rows whose sample points can reach slice m's window are visited.

@@ -18,8 +18,9 @@ residual_<expID><fmt>; it takes neither --dark-field nor --max-shift.  --method 
 dark-field term and adds visibility_<expID><fmt>.  --retrieve-propagation (independent of --retrieve; any number of
 positions) runs Paganin's single-material retrieval of each bin's propagation image over its flat field on rank 0 and writes
 propag/retrieval/{contact,thickness,phi}_<expID><fmt> under the bin's directory; --material names the sample material whose
-delta and beta the filter takes (default: the sample of interest's first).  --tomography A (contrast-phantom samples only)
-then turns the phantom through A angles on [0, 180) degrees, runs the chain at each (paresis_amd/tomography.py scan),
+delta and beta the filter takes (default: the sample of interest's first).  --tomography A (samples that are the contrast
+phantom or a getVolumeFromFile label volume) then turns the sample through A angles on [0, 180) degrees, runs the chain at
+each (paresis_amd/tomography.py scan),
 reconstructs by filtered back-projection on rank 0 and writes tomography/mu_<expID> (--tomography-modality attenuation,
 the default: 1/m, from -ln(Propag/White), any --points) or tomography/delta_<expID> (phase: from the retrieved phi, the
 rules and options of --retrieve) under each bin's directory: one [n, m, m] file for --format .npy, else a directory of
@@ -54,8 +55,9 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     first); with save, contact, thickness and phi go to <bin dir>/propag/retrieval/.  exp_dict['propagationParams'] then
     holds the parameters, the material and the delta, beta, alpha and mu it used.
 
-    tomography = A > 0 (extension; the sample of interest must be the contrast phantom): after the run, rank 0 turns the
-    phantom through A angles on [0, 180), runs the chain at each (tomography.scan with tomography_modality; 'phase'
+    tomography = A > 0 (extension; the sample of interest must be the contrast phantom or a getVolumeFromFile label
+    volume): after the run, rank 0 turns it through A angles on [0, 180), runs the chain at each (tomography.scan with
+    tomography_modality; 'phase'
     retrieves with method, max_shift, dark_field, window, search and needs their positions), reconstructs every bin
     (tomography.reconstruct) and, with save, writes <bin dir>/tomography/{mu|delta}_<expID> (tomography.save_volume).
     tomography_method 'sirt' or 'cgls' with tomography_iterations >= 1 reconstructs iteratively instead of by filtered
@@ -282,8 +284,8 @@ def main(argv=None):
     ap.add_argument("--material", default=None,
                     help="--retrieve-propagation: the sample material the filter assumes (default: the sample's first)")
     ap.add_argument("--tomography", type=int, default=0, metavar="A",
-                    help="contrast-phantom samples: scan A angles on [0, 180) after the run and write the filtered "
-                         "back-projection, tomography/{mu|delta}_<expID> under each bin's directory")
+                    help="contrast-phantom and label-volume (getVolumeFromFile) samples: scan A angles on [0, 180) after "
+                         "the run and write the filtered back-projection, tomography/{mu|delta}_<expID> under each bin's directory")
     ap.add_argument("--tomography-modality", default="attenuation", choices=["attenuation", "phase"],
                     help="--tomography: mu from -ln(Propag/White) (default), or delta from the retrieved phi (the rules and "
                          "options of --retrieve)")

@@ -1339,3 +1339,52 @@ def fbp_tv_step(plan, weight, nonneg, u, c, x, xbar_in, xbar_out, px_in, py_in, 
                                         _ptr(xbar_in), _ptr(xbar_out), _ptr(px_in), _ptr(py_in), _ptr(px_out), _ptr(py_out),
                                         _stream()), "psx_fbp_tv_step_f32")
     return x, xbar_out, px_out, py_out
+
+
+class VolumeDesc(ctypes.Structure):
+    """psx_volume_desc (include/paresis_hip.h)."""
+    _fields_ = [("n", c_int), ("m", c_int), ("nmat", c_int), ("dimX", c_int), ("dimY", c_int),
+                ("cos_a", c_double), ("sin_a", c_double), ("off_x", c_double), ("off_y", c_double),
+                ("s", c_double), ("voxel_m", c_double), ("box", c_void_p)]
+
+
+def volume_desc(n, m, nmat, angle_deg, dims, scale, voxel_m, box=None):
+    """The kernel's descriptor: the scalars of the contract by the phantom's own expressions (phantom_scalars: skimage
+    radon's inverse map about c = m // 2)."""
+    import numpy as np
+    theta = np.deg2rad(np.asarray([angle_deg], dtype=np.float64))[0]
+    cos_a, sin_a = np.cos(theta), np.sin(theta)
+    center = int(m) // 2
+    d = VolumeDesc()
+    d.n, d.m, d.nmat, d.dimX, d.dimY = int(n), int(m), int(nmat), int(dims[0]), int(dims[1])
+    d.cos_a, d.sin_a = float(cos_a), float(sin_a)
+    d.off_x, d.off_y = float(-center * (cos_a + sin_a - 1)), float(-center * (cos_a - sin_a - 1))
+    d.s, d.voxel_m = float(scale), float(voxel_m)
+    d.box = None if box is None else box.data_ptr()
+    return d
+
+
+def volume_project(labels, nmat, angle_deg, dims, scale, voxel_m, want_lines=False, box=None):
+    """The thickness maps of a labelled voxel volume at one angle (psx_volume_project_u8; the contract is in
+    include/paresis_hip.h): labels [n, m, m] uint8 in HBM, label k + 1 = material k < nmat -> geom [nmat, dimX, dimY]
+    float32 (metres) on the dims = (dimX, dimY) study grid, whose pixel is `scale` voxels of voxel_m metres; with want_lines
+    also the float64 line integrals in voxels, (geom, lines).  box: an [n, 4] int32 tensor of each slice's occupied
+    (row0, row1, col0, col1), half-open, which only spares work; None: the whole slice.  The kernel applies no circle mask
+    and ignores labels above nmat: Samples.getVolumeFromFile.check_volume is the loader's check."""
+    _need(labels, torch.uint8, "labels")
+    if labels.dim() != 3 or labels.shape[1] != labels.shape[2]:
+        raise PsxError("labels must be [n, m, m], got shape %s" % (tuple(labels.shape),))
+    n, m = int(labels.shape[0]), int(labels.shape[1])
+    if box is not None:
+        _need(box, torch.int32, "box", (n, 4))
+        if box.device != labels.device:
+            raise PsxError("box is on %s, labels on %s" % (box.device, labels.device))
+    d = volume_desc(n, m, nmat, angle_deg, dims, scale, voxel_m, box)
+    if d.nmat < 1 or d.dimX < 1 or d.dimY < 1:
+        raise PsxError("volume_project: nmat=%d, study grid %d x %d" % (d.nmat, d.dimX, d.dimY))
+    with torch.cuda.device(labels.device):
+        geom = torch.empty((d.nmat, d.dimX, d.dimY), dtype=torch.float32, device=labels.device)
+        lines = torch.empty((d.nmat, d.dimX, d.dimY), dtype=torch.float64, device=labels.device) if want_lines else None
+        check(lib().psx_volume_project_u8(ctypes.byref(d), _ptr(labels), _ptr(lines), _ptr(geom), _stream()),
+              "psx_volume_project_u8")
+    return (geom, lines) if want_lines else geom

@@ -1,4 +1,4 @@
-"""Parallel-beam tomography of the contrast phantom: the inverse of the projections the package simulates and retrieves.
+"""Parallel-beam tomography of the contrast phantom or of a labelled voxel volume: the inverse of the projections the package simulates and retrieves.
 
     fbp(sinogram, angles_deg, ...)      filtered back-projection on the GPU (csrc/fbp.hip, ops.FbpPlan; the contract is in
                                         include/paresis_hip.h): [A, n, m] maps, one per angle -> [n, m, m], a slice per
@@ -12,15 +12,16 @@
     tv_objective(vol, sinogram, angles_deg, weight, ...)        constant object such as the phantom (ops.fbp_tv_step)
     delta_volume(vol, energy_keV, voxel_m)   phi = -k * integral(delta) dl  ->  delta = -vol/(k*voxel), k = getk(E)
     mu_volume(vol, voxel_m)                  -ln T = integral(mu) dl         ->  mu = vol/voxel (1/m)
-    project(sample, energy_keV, angles_deg, dims, pixel_um)   the phantom's ideal sinograms phi and -ln T on the study grid
+    project(sample, energy_keV, angles_deg, dims, pixel_um)   the sample's ideal sinograms phi and -ln T on the study grid
     scan(experiment, angles_deg, modality)                    the real chain once per angle -> sinograms per energy bin
     rotation_center(experiment)                               the detector column of the rotation axis of such a scan
     save_volume(vol, path, fmt)
 
 The beam is treated as parallel: no fan- or cone-beam weighting.  At the magnification of the shipped experiments
-(M ~ 1.03) that is the synchrotron case.  Only the contrast phantom (Samples/generateContrastPhantom.py) has a
-three-dimensional description -- 13 material discs on a slice, projected at Sample.myAngle -- so project and scan refuse
-every other sample.
+(M ~ 1.03) that is the synchrotron case.  Two samples have a three-dimensional description, projected at Sample.myAngle by
+the same model (scikit-image radon of a slice): the contrast phantom (Samples/generateContrastPhantom.py: 13 material
+discs on a slice) and a volume of material labels the user brings (Samples/getVolumeFromFile.py: uint8 [n, m, m], from
+the sample's myVolumeFile or set as myVolume).  project and scan refuse every other sample.
 
     python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase]
                                [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]] ...
@@ -33,6 +34,8 @@ from .getk import getk
 
 MODALITIES = ("attenuation", "phase")
 PHANTOM_FUNCTION = "generateContrastPhantom"
+VOLUME_FUNCTION = "getVolumeFromFile"
+ROTATABLE_FUNCTIONS = (PHANTOM_FUNCTION, VOLUME_FUNCTION)
 _plans = {}
 
 
@@ -261,9 +264,10 @@ def mu_volume(vol_logT, voxel_m):
 
 
 def _phantom(sample):
-    if getattr(sample, "myGeometryFunction", "") != PHANTOM_FUNCTION:
-        raise ValueError("tomography needs a sample whose geometry function is %s (the only one with a three-dimensional "
-                         "description), got %r" % (PHANTOM_FUNCTION, getattr(sample, "myGeometryFunction", "")))
+    """The sample, if it can be turned: the contrast phantom or a labelled voxel volume."""
+    if getattr(sample, "myGeometryFunction", "") not in ROTATABLE_FUNCTIONS:
+        raise ValueError("tomography needs a sample whose geometry function is %s (the only ones with a three-dimensional "
+                         "description), got %r" % (" or ".join(ROTATABLE_FUNCTIONS), getattr(sample, "myGeometryFunction", "")))
     return sample
 
 
@@ -273,11 +277,11 @@ def _turn(sample, angle, dims, pixel_um, ov=1):
 
 
 def project(sample, energy_keV, angles_deg, dims, pixel_um):
-    """The ideal sinograms of the contrast phantom `sample` (an AnalyticalSample with delta / beta at energy_keV) on a
-    dims = (dimX, dimY) grid of pixel_um pixels -> {'phi': [A, dimX, dimY] float32 (radians, -k*sum delta*t),
-    'logT': [A, dimX, dimY] float32 (-ln of the transmitted intensity, 2k*sum beta*t)}.  Per angle the sample is turned
-    (myAngle), its geometry rebuilt (psx_contrast_phantom_f32) and a unit intensity sent through setWaveRT: existing kernels
-    only.  The sample is left at its last angle."""
+    """The ideal sinograms of `sample` (an AnalyticalSample with delta / beta at energy_keV whose geometry function is the
+    contrast phantom's or getVolumeFromFile) on a dims = (dimX, dimY) grid of pixel_um pixels ->
+    {'phi': [A, dimX, dimY] float32 (radians, -k*sum delta*t), 'logT': [A, dimX, dimY] float32 (-ln of the transmitted
+    intensity, 2k*sum beta*t)}.  Per angle the sample is turned (myAngle), its geometry rebuilt (psx_contrast_phantom_f32
+    or psx_volume_project_u8) and a unit intensity sent through setWaveRT.  The sample is left at its last angle."""
     import torch
     _phantom(sample)
     dims = (int(dims[0]), int(dims[1]))
@@ -297,7 +301,7 @@ def rotation_center(experiment):
     """The detector column of the rotation axis of a scan of `experiment`: (dimY // 2 - (ov - 1)/2)/ov, dimY the study
     grid's axis-1 length.  Needs no GPU.
 
-    The phantom is projected with scikit-image radon's convention, whose axis is study column c0 = dimY // 2
+    The phantom and a label volume are projected with scikit-image radon's convention, whose axis is study column c0 = dimY // 2
     (phantom_scalars' center).  The chains keep the study grid up to the detector, which reflect-pads it by 15*ov pixels,
     sums ov x ov blocks and crops 15 detector pixels (Detector.detection): study column x sits at padded column x + 15*ov,
     in block (x + 15*ov) // ov = x // ov + 15, which the crop brings back to x // ov -- pad and crop cancel, and the study
@@ -322,8 +326,8 @@ def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
     modality='attenuation': -ln(Propag/White) of position 0 (the propagation image over its flat field; any number of
     positions), for mu_volume.  modality='phase': 'phi' of retrieval.retrieve on the angle's positions (retrieve_options:
     method, max_shift, dark_field, window, search -- bound by retrieval.check_method's rules), for delta_volume.
-    The sample of interest must be the contrast phantom (ValueError otherwise): per angle its myAngle is set and its
-    geometry rebuilt on the study grid.  A membrane that has a geometry function gets its geometry per position as main.run
+    The sample of interest must be the contrast phantom or a label volume (ValueError otherwise): per angle its myAngle is
+    set and its geometry rebuilt on the study grid.  A membrane that has a geometry function gets its geometry per position as main.run
     does; an injected one keeps the geometry it has."""
     import torch
     from . import retrieval

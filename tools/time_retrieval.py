@@ -1,6 +1,6 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project] [--tv]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project] [--tv] [--volume]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
@@ -34,6 +34,12 @@ candidate (two FMAs, floor, two additions, two comparisons, one conversion: 8 qu
 8 TB/s peak, MI355X_MICROARCH.md).  Beside it: the same step written with torch operations (torch_tv_step below, kept in
 this tool only: the baseline the kernel replaces), timed with a host clock around a synchronised loop, and the share of a
 whole iteration of tomography.tv at 90 angles that the two projector calls take.
+
+--volume times k_volume_project (psx_volume_project_u8) on a (dimX, dimY) = (512, 2048) study grid at 30 degrees, voxel =
+study pixel: on contrast_phantom_volume (13 materials, [512, 2048, 2048] labels) with and without the slices' occupied
+boxes, and on a random 8-material volume of the same size (every voxel inside the circle its own label: four different
+labels at most steps).  The baseline is psx_contrast_phantom_f32 at that grid (k_phantom_lines + k_phantom_maps), which is
+how the same maps are made from the 13 analytic discs.  The byte price is one read of the labels and one write of the maps.
 """
 import argparse
 import ctypes
@@ -335,6 +341,54 @@ def tv_case(n, m, A, reps):
     plan.close()
 
 
+def _kernel_us(names, fn, reps):
+    """Mean HIP-event time in us of the kernels `names` over `reps` calls of fn, after two warm-up calls."""
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    s = summary()
+    lib().psx_profile_enable(0)
+    return [s[k][1] / s[k][0] * 1e3 for k in names]
+
+
+def volume_case(dimX, dimY, pix_um, reps):
+    from paresis_amd.Samples.generateContrastPhantom import contrast_phantom_lines
+    from paresis_amd.Samples.getVolumeFromFile import contrast_phantom_volume, upload_volume
+    angle, voxel_m = 30.0, pix_um * 1e-6
+    t_lines, t_maps = _kernel_us(("k_phantom_lines", "k_phantom_maps"),
+                                 lambda: contrast_phantom_lines(dimX, dimY, pix_um, angle), reps)
+    base = t_lines + t_maps
+    print("dimX=%d dimY=%d  psx_contrast_phantom_f32 %.1f us (k_phantom_lines %.1f + k_phantom_maps %.1f)"
+          % (dimX, dimY, base, t_lines, t_maps))
+    want = contrast_phantom_lines(dimX, dimY, pix_um, angle)[0]
+
+    def run(name, v, nmat, box):
+        (t,) = _kernel_us(("k_volume_project",), lambda: ops.volume_project(v.labels, nmat, angle, (dimX, dimY), 1.0, voxel_m,
+                                                                            box=v.box if box else None), reps)
+        price = v.labels.numel() + 4.0 * nmat * dimX * dimY
+        print("    %-34s k_volume_project %9.1f us = %7.1f x the phantom's kernels; price %.0f MB (%.0f us at 8 TB/s) = %.3f of peak"
+              % (name, t, t / base, price / 1e6, price / PEAK * 1e6, price / (t * 1e-6) / PEAK))
+        return t
+
+    v = upload_volume(contrast_phantom_volume(dimX, dimY, pix_um), 13)
+    got = ops.volume_project(v.labels, 13, angle, (dimX, dimY), 1.0, voxel_m, box=v.box)
+    print("    the phantom's volume gives the phantom's maps: largest difference %.1e m of %.1e m"
+          % (float((got - want).abs().max()), float(want.abs().max())))
+    run("phantom volume, occupied boxes", v, 13, True)
+    run("phantom volume, whole slices", v, 13, False)
+    del v, got
+    g = torch.Generator(device="cuda").manual_seed(dimX + dimY)
+    d2 = (torch.arange(dimY, device="cuda") - dimY // 2) ** 2
+    inside = (d2[:, None] + d2[None, :] <= (dimY // 2) ** 2).to(torch.uint8)
+    lab = torch.randint(1, 9, (dimX, dimY, dimY), device="cuda", generator=g, dtype=torch.uint8) * inside
+    v = upload_volume(lab, 8)
+    run("random 8-material volume", v, 8, True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
@@ -344,7 +398,11 @@ def main():
     ap.add_argument("--fbp", action="store_true", help="time psx_fbp_f32 only")
     ap.add_argument("--project", action="store_true", help="time psx_fbp_project_f32 and psx_fbp_adjoint_f32 only")
     ap.add_argument("--tv", action="store_true", help="time psx_fbp_tv_step_f32 and an iteration of tomography.tv only")
+    ap.add_argument("--volume", action="store_true", help="time psx_volume_project_u8 against psx_contrast_phantom_f32 only")
     a = ap.parse_args()
+    if a.volume:
+        volume_case(512, 2048, 20.0, max(a.reps // 4, 2))
+        return
     if a.tv:
         tv_case(8, 512, 90, a.reps)
         tv_case(2, 2048, 90, max(a.reps // 2, 2))

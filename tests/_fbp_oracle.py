@@ -153,6 +153,44 @@ def case_centers(m):
     return (float(m // 2), m / 2 - 0.25)
 
 
+# ---- the edge cases: off-centre axes, sizes about the tiles, every quadrant (tests/test_gpu_tomo_edges.py) --------------
+# the axes and the ties of all four quadrants, negative angles, a hair either side of a tie and of an axis, more than a turn
+# (3645 = 10 * 360 + 45), then three ordinary ones
+EDGE_ANGLES = (0.0, 45.0, 90.0, 135.0, 180.0, 225.0, 270.0, 315.0, 360.0, -45.0, -90.0, -180.0, 44.999999, 45.000001, 1e-9,
+               89.999999999, 3645.0, -30.0, 17.3, 101.9)
+
+
+def edge_angles(A):
+    """The first A of EDGE_ANGLES; a larger A continues over the whole turn, [0, 360)."""
+    th = np.arange(A, dtype=np.float64) * (360.0 / A) + 0.37
+    k = min(A, len(EDGE_ANGLES))
+    th[:k] = EDGE_ANGLES[:k]
+    return th
+
+
+FAR_CENTERS = 3          # the last three of edge_centers: nothing reaches the detector
+
+
+def edge_centers(m):
+    """The two of case_centers, an axis on the first sample, off the detector on either side, on the last sample and well
+    off the middle; then three (FAR_CENTERS) from which no voxel reaches the detector: |u - center| <= sqrt(2) * (m // 2)
+    < m, so every u is beyond m at 3m and far beyond either end at +-2^20, the largest the contract admits."""
+    return (float(m // 2), m / 2 - 0.25, 0.0, -3.5, m - 1.0, m + 2.75, m / 2 + 7.3, 3.0 * m, 2.0 ** 20, -2.0 ** 20)
+
+
+def dense_centers(m):
+    """The three truncating centres of the dense edge cases: off the detector's low end, on its last sample, off the middle."""
+    return (-3.5, m - 1.0, m / 2 + 7.3)
+
+
+# the filtered edge cases: m one below, at and above the pad-length step (P = 64, 64, 128) and the 64-sample run, A one above
+# the 32-angle chunk
+EDGE_FBP_SHAPES = [(33, 7, 31), (33, 7, 32), (33, 7, 33), (9, 7, 64), (9, 7, 65)]
+# max|fbp_f32 - fbp| / max|fbp| per edge shape on case_sino / edge_angles: the worst over the three filters and the three
+# centres of dense_centers, circle off, measured on the CPU as F32_ERROR was (tests/test_fbp_host.py reproduces them)
+EDGE_F32_ERROR = {(33, 7, 31): 2.9e-7, (33, 7, 32): 3.0e-7, (33, 7, 33): 2.9e-7, (9, 7, 64): 1.9e-7, (9, 7, 65): 2.0e-7}
+
+
 # ---- the contrast phantom restated (Samples/generateContrastPhantom.py, csrc/phantom.hip) ----------------------------
 TUBES_CENTERS0 = [[22, 7], [16.4, 4.7], [10, 7], [6, 12.5], [6, 19.5], [10, 25], [16.4, 27], [22, 25], [21, 16], [11, 16],
                   [16, 11], [16, 21]]

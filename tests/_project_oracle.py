@@ -81,6 +81,39 @@ def adjoint(sino, theta_deg, center=None, circle=True):
     return vol * _lit(m, circle)
 
 
+def matrix(m, theta_deg, center=None, circle=True):
+    """The contract's matrix written down directly, in the layout of ops.fbp_project of an identity: [A][m*m][m] float32,
+    entry [a][i*m + j][k] the weight of voxel (i, j) on sample k of angle a.  A lit voxel gives float32(1) - w1 to sample
+    floor(u) and w1 = float32(u - floor(u)) to sample floor(u) + 1; samples outside [0, m) are dropped."""
+    lit = _lit(m, circle).ravel()
+    row = np.arange(m * m)
+    out = np.zeros((len(theta_deg), m * m, m), dtype=np.float32)
+    for a, th in enumerate(theta_deg):
+        u = fo.grid_u(m, th, _center(m, center)).ravel()
+        fl = np.floor(u)
+        w1 = (u - fl).astype(np.float32)
+        k = fl.astype(np.int64)
+        ok = lit & (k >= 0) & (k < m)
+        out[a, row[ok], k[ok]] = np.float32(1) - w1[ok]
+        ok = lit & (k + 1 >= 0) & (k + 1 < m)
+        out[a, row[ok], k[ok] + 1] = w1[ok]
+    return out
+
+
+def impulses(A, m):
+    """[A][A*m][m] float32 with [a][a*m + k][k] = 1: one unit impulse per detector row, so that adjoint's [A*m][m][m]
+    holds the back-projector's whole matrix, row a*m + k the column (a, k)."""
+    s = np.zeros((A, A * m, m), dtype=np.float32)
+    a, k = np.divmod(np.arange(A * m), m)
+    s[a, np.arange(A * m), k] = 1
+    return s
+
+
+def as_matrix(vol, A, m):
+    """adjoint(impulses) [A*m][m][m] in matrix()'s layout [A][m*m][m]."""
+    return np.ascontiguousarray(np.asarray(vol).reshape(A, m, m * m).transpose(0, 2, 1))
+
+
 def _reciprocal(t):
     return np.where(t > 1e-6, 1.0 / np.where(t > 1e-6, t, 1), 0).astype(t.dtype)
 
@@ -226,12 +259,49 @@ SOLVER_CASES = [(12, 2, 64, 0), (5, 3, 33, 1)]
 SOLVER_ITERATIONS = (4, 10)
 SIRT_F32_ERROR = {((12, 2, 64, 0), 4): 2.2e-7, ((12, 2, 64, 0), 10): 2.7e-7, ((5, 3, 33, 1), 4): 1.8e-7, ((5, 3, 33, 1), 10): 2.3e-7}
 CGLS_F32_ERROR = {((12, 2, 64, 0), 4): 6.4e-7, ((12, 2, 64, 0), 10): 8.9e-3, ((5, 3, 33, 1), 4): 7.2e-7, ((5, 3, 33, 1), 10): 1.3e-2}
+# the cases of EDGE_SOLVER_CASES (below): SIRT the worse of the clamp on and off, CGLS at the 4-step count only, the one the
+# GPU is held to there (its 10-step figures are 2.5e-2 and 1.6e-2)
+SIRT_F32_ERROR.update({((12, 2, 64, -3.5), 4): 2.8e-7, ((12, 2, 64, -3.5), 10): 2.6e-7, ((5, 3, 33, -3.5), 4): 1.5e-7,
+                       ((5, 3, 33, -3.5), 10): 2.3e-7})
+CGLS_F32_ERROR.update({((12, 2, 64, -3.5), 4): 1.1e-6, ((5, 3, 33, -3.5), 4): 1.9e-6})
+
+
+# ---- the edge cases (tests/test_gpu_tomo_edges.py; the host tests reproduce every figure) -------------------------------
+# the matrix cases: every angle of fo.EDGE_ANGLES and every centre of fo.edge_centers at the small sizes (about the 16-voxel
+# tile, across the pad-length step); ten angles and four centres at the large ones (about the 64-sample run, three runs)
+MATRIX_M = (2, 5, 15, 16, 17, 33)
+MATRIX_LARGE_M = (63, 64, 65, 129)
+MATRIX_LARGE_ANGLES = fo.EDGE_ANGLES[:8] + (17.3, 44.999999)
+
+
+def matrix_large_centers(m):
+    return (float(m // 2), -3.5, m + 2.75, m / 2 + 7.3)
+
+
+# the dense cases (A, n, m): m about the tile, the pad-length step and the run, A about the 32-angle chunk, n not a multiple
+# of the four-row block; on case_vol / fo.case_sino / fo.edge_angles at the three centres of fo.dense_centers
+EDGE_SHAPES = [(31, 4, 15), (32, 7, 16), (33, 8, 17), (64, 9, 31), (65, 1, 32), (63, 3, 33), (5, 6, 63), (6, 2, 65), (4, 5, 127),
+               (3, 3, 129)]
+# max|project_f32 - project| / max|project| per edge shape: the worst over the three centres and circle on and off
+EDGE_F32_ERROR = {(31, 4, 15): 1.3e-7, (32, 7, 16): 1.4e-7, (33, 8, 17): 1.3e-7, (64, 9, 31): 1.7e-7, (65, 1, 32): 1.4e-7,
+                  (63, 3, 33): 1.5e-7, (5, 6, 63): 1.7e-7, (6, 2, 65): 2.3e-7, (4, 5, 127): 2.3e-7, (3, 3, 129): 1.9e-7}
+# max|adjoint_f32 - adjoint| / max|adjoint|, likewise
+EDGE_ADJ_F32_ERROR = {(31, 4, 15): 1.9e-7, (32, 7, 16): 2.3e-7, (33, 8, 17): 2.3e-7, (64, 9, 31): 3.5e-7, (65, 1, 32): 3.7e-7,
+                      (63, 3, 33): 4.3e-7, (5, 6, 63): 1.5e-7, (6, 2, 65): 1.4e-7, (4, 5, 127): 1.4e-7, (3, 3, 129): 1.3e-7}
+# dot_mismatch of the restatements, likewise and over the seeds 0 and 1
+EDGE_DOT_F32_ERROR = {(31, 4, 15): 7.3e-9, (32, 7, 16): 4.7e-9, (33, 8, 17): 5.1e-9, (64, 9, 31): 1.8e-9, (65, 1, 32): 1.1e-8,
+                      (63, 3, 33): 6.5e-9, (5, 6, 63): 8.0e-9, (6, 2, 65): 8.0e-9, (4, 5, 127): 1.0e-8, (3, 3, 129): 8.9e-9}
+
+# the solver cases where the guards act: the axis 3.5 samples below the detector, the circle on.  Most rays meet no lit
+# voxel (R = 0) and a crescent of lit voxels meets no sample (C = 0); the fourth entry is the centre itself
+EDGE_SOLVER_CASES = [(12, 2, 64, -3.5), (5, 3, 33, -3.5)]
 
 
 def solver_case(A, n, m, which):
-    """-> (angles, centre, the float32 sinogram [A][n][m] whose row 1 is zero)."""
+    """-> (angles, centre, the float32 sinogram [A][n][m] whose row 1 is zero).  which: an index into fo.case_centers, or
+    (a float) the centre itself."""
     theta = np.arange(A) * (180.0 / A)
-    center = fo.case_centers(m)[which]
+    center = fo.case_centers(m)[which] if isinstance(which, int) else float(which)
     sino = project(case_vol(A, n, m), theta, center, True).astype(np.float32)
     sino[:, 1, :] = 0
     return theta, center, sino

@@ -96,6 +96,36 @@ def test_float32_yardstick(shape):
     assert 0 < worst <= 1.25 * F32_ERROR[shape]
 
 
+@pytest.mark.parametrize("shape", fo.EDGE_FBP_SHAPES)
+def test_edge_float32_yardstick(shape):
+    """The same at the edge shapes (m about the pad-length step and the 64-sample run) on edge_angles, at the three
+    truncating centres of dense_centers: the figures of EDGE_F32_ERROR."""
+    A, n, m = shape
+    theta, sino = fo.edge_angles(A), fo.case_sino(A, n, m)
+    worst = 0.0
+    for flt in fo.FILTERS:
+        for c in fo.dense_centers(m):
+            ref = fo.fbp(sino, theta, c, flt, False)
+            worst = max(worst, float(np.abs(fo.fbp_f32(sino, theta, c, flt, False) - ref).max() / np.abs(ref).max()))
+    print("float32 restatement at %s: %.3e (table %.3e)" % (shape, worst, fo.EDGE_F32_ERROR[shape]))
+    assert 0 < worst <= 1.25 * fo.EDGE_F32_ERROR[shape]
+    assert [fo.pad_length(k) for k in (31, 32, 33, 64, 65)] == [64, 64, 128, 128, 256]
+
+
+def test_far_centers_reach_nothing():
+    """From the last three centres of edge_centers no voxel has a sample on the detector, at any angle of EDGE_ANGLES: the
+    oracle's back-projection is exactly zero; from an axis on the detector it is not."""
+    for m in (2, 5, 17, 64):
+        sino = fo.case_sino(len(fo.EDGE_ANGLES), 1, m)
+        centers = fo.edge_centers(m)
+        for c in centers:
+            vol = fo.fbp(sino, fo.EDGE_ANGLES, c, "none", False)
+            if c in centers[-fo.FAR_CENTERS:]:
+                assert not vol.any(), (m, c)
+            elif m >= 17 or c in fo.case_centers(m):            # a short detector is also out of reach of m / 2 + 7.3
+                assert vol.any(), (m, c)
+
+
 def test_case_angles_hold_the_special_ones():
     th = fo.case_angles(90)
     assert list(th[:4]) == [0.0, 90.0, -30.0, 270.0] and len(th) == 90

@@ -120,6 +120,119 @@ def test_float32_solver_yardsticks(case):
             assert np.all(ref[1] == 0) and np.all(got[1] == 0)               # the zero sinogram row
 
 
+@pytest.mark.parametrize("m", [2, 5, 16, 17])
+def test_matrix_builder_is_the_operators_matrix(m):
+    """po.matrix, the yardstick of the GPU's matrices, against the operators on unit impulses at every angle of EDGE_ANGLES
+    and every centre of edge_centers, circle off and on: the bits of project_f32 of an identity and of adjoint_f32 of the
+    impulses (one non-zero term per sum: nothing to round, so the restatements are exact transposes as the kernels must
+    be), within 2^-24 -- one rounding of a weight in [0, 1] -- of the float64 project and adjoint, and all zero from the
+    three far centres."""
+    theta = np.asarray(fo.EDGE_ANGLES)
+    A = len(theta)
+    eye, imp = np.eye(m * m, dtype=np.float32).reshape(m * m, m, m), po.impulses(A, m)
+    assert imp.sum() == A * m and all(imp[a, a * m + k, k] == 1 for a in (0, A - 1) for k in (0, m - 1))
+    centers = fo.edge_centers(m)
+    worst = 0.0
+    for center in centers:
+        for circle in (False, True):
+            M = po.matrix(m, theta, center, circle)
+            assert M.dtype == np.float32 and M.shape == (A, m * m, m)
+            P32 = po.project_f32(eye, theta, center, circle)
+            B32 = po.as_matrix(po.adjoint_f32(imp, theta, center, circle), A, m)
+            assert np.array_equal(P32, B32) and np.array_equal(M, P32), (center, circle)
+            P64 = po.project(eye, theta, center, circle)
+            B64 = po.as_matrix(po.adjoint(imp, theta, center, circle), A, m)
+            assert np.array_equal(P64, B64)
+            worst = max(worst, float(np.abs(M - P64).max()))
+            if center in centers[-fo.FAR_CENTERS:]:
+                assert not M.any() and not P64.any()
+            elif center in fo.case_centers(m):
+                assert M.any()
+    print("matrix m %d: max|float32 - float64| = %.3e (2^-24 = %.3e)" % (m, worst, 2.0 ** -24))
+    assert worst <= 2.0 ** -24
+    # a voxel's weights sum to 1 where both its samples are on the detector; at most two entries per voxel and angle
+    M = po.matrix(m, theta, m // 2, False)
+    assert (np.count_nonzero(M, axis=2) <= 2).all() and np.abs(M.sum(axis=2)[:, (m // 2) * m + m // 2] - 1).max() <= 2.0 ** -23
+
+
+def test_edge_cases_cover_what_they_name():
+    assert len(fo.EDGE_ANGLES) == 20 and list(fo.edge_angles(3)) == [0.0, 45.0, 90.0]
+    th = fo.edge_angles(65)
+    assert tuple(th[:20]) == fo.EDGE_ANGLES and len(th) == 65 and th[20:].min() > 110 and 354 < th[20:].max() < 360
+    assert np.cos(np.deg2rad(fo.EDGE_ANGLES[4])) == -1.0                          # 1 / cos < 0 on the j-major branch
+    assert set(po.MATRIX_LARGE_ANGLES) <= set(fo.EDGE_ANGLES) and len(po.MATRIX_LARGE_ANGLES) == 10
+    for m in po.MATRIX_M + po.MATRIX_LARGE_M:
+        c = fo.edge_centers(m)
+        assert c[:2] == fo.case_centers(m) and len(c) == 10 and c[-3:] == (3.0 * m, 2.0 ** 20, -2.0 ** 20)
+        assert set(fo.dense_centers(m)) <= set(c) and set(po.matrix_large_centers(m)) <= set(c)
+    assert {m for _, _, m in po.EDGE_SHAPES} >= {15, 16, 17, 31, 32, 33, 63, 65, 127, 129}
+    assert {A for A, _, _ in po.EDGE_SHAPES} >= {31, 32, 33, 63, 64, 65}
+    assert set(po.EDGE_SHAPES) == set(po.EDGE_F32_ERROR) == set(po.EDGE_ADJ_F32_ERROR) == set(po.EDGE_DOT_F32_ERROR)
+
+
+@pytest.mark.parametrize("shape", po.EDGE_SHAPES)
+def test_edge_float32_yardsticks(shape):
+    """project_f32, adjoint_f32 and their dot-product mismatch reproduce the three figures the GPU's edge bounds are 8 times
+    of: the worst over the three truncating centres and circle on and off (the mismatch over the seeds 0 and 1 too)."""
+    A, n, m = shape
+    theta = fo.edge_angles(A)
+    wp = wa = wd = 0.0
+    for c in fo.dense_centers(m):
+        for circle in (False, True):
+            for seed in (0, 1):
+                x, y = po.case_vol(A, n, m, seed), fo.case_sino(A, n, m, seed)
+                p32, a32 = po.project_f32(x, theta, c, circle), po.adjoint_f32(y, theta, c, circle)
+                wd = max(wd, po.dot_mismatch(p32, y, x, a32))
+                if seed == 0:
+                    p64, a64 = po.project(x, theta, c, circle), po.adjoint(y, theta, c, circle)
+                    assert po.dot_mismatch(p64, y, x, a64) <= 1e-13               # truncation leaves the oracle's pair adjoint
+                    wp = max(wp, float(np.abs(p32 - p64).max() / np.abs(p64).max()))
+                    wa = max(wa, float(np.abs(a32 - a64).max() / np.abs(a64).max()))
+    print("float32 at %s: projector %.3e (table %.3e), adjoint %.3e (table %.3e), adjointness %.3e (table %.3e)"
+          % (shape, wp, po.EDGE_F32_ERROR[shape], wa, po.EDGE_ADJ_F32_ERROR[shape], wd, po.EDGE_DOT_F32_ERROR[shape]))
+    assert 0 < wp <= 1.25 * po.EDGE_F32_ERROR[shape]
+    assert 0 < wa <= 1.25 * po.EDGE_ADJ_F32_ERROR[shape]
+    assert 0 < wd <= 1.25 * po.EDGE_DOT_F32_ERROR[shape]
+
+
+@pytest.mark.parametrize("case,r0,c0", [((12, 2, 64, -3.5), 409, 300), ((5, 3, 33, -3.5), 95, 167)])
+def test_guarded_solver_cases(case, r0, c0):
+    """The axis 3.5 samples below the detector: r0 entries of R = B^T 1 and c0 lit entries of C = B 1 are exactly 0, so both
+    of the solvers' guards are taken, and -- the condition of the GPU comparison -- no entry of either lies in (0, 1e-5],
+    where a float32 value could fall on the other side of the 1e-6 threshold.  Then the float32 yardsticks."""
+    assert case in po.EDGE_SOLVER_CASES
+    A, n, m, _ = case
+    theta, center, sino = po.solver_case(*case)
+    assert center == -3.5 and np.all(sino[:, 1] == 0) and sino[:, 0].max() > 10
+    R = po.project(np.ones((1, m, m)), theta, center, True)[:, 0]
+    C = po.adjoint(np.ones((A, 1, m)), theta, center, True)[0]
+    lit = fo.circle_mask(m)
+    print("%s: R = 0 at %d of %d, C = 0 at %d of %d lit voxels, smallest positive R %.3g, C %.3g"
+          % (case, (R == 0).sum(), R.size, (C[lit] == 0).sum(), lit.sum(), R[R > 0].min(), C[C > 0].min()))
+    assert (R == 0).sum() == r0 and (C[lit] == 0).sum() == c0
+    assert not ((R > 0) & (R <= 1e-5)).any() and not ((C > 0) & (C <= 1e-5)).any()
+    R32 = po.project_f32(np.ones((1, m, m)), theta, center, True)[:, 0]
+    C32 = po.adjoint_f32(np.ones((A, 1, m)), theta, center, True)[0]
+    assert np.array_equal(R32 == 0, R == 0) and np.array_equal(C32 == 0, C == 0)
+    for it in po.SOLVER_ITERATIONS:
+        e = 0.0
+        for nonneg in (False, True):
+            ref, got = po.sirt(sino, theta, it, center, nonneg=nonneg), po.sirt_f32(sino, theta, it, center, nonneg=nonneg)
+            e = max(e, float(np.abs(got - ref).max() / np.abs(ref).max()))
+            assert np.all(ref[:, C == 0] == 0) and np.all(got[:, C == 0] == 0) and np.all(got[1] == 0)
+        print("float32 sirt at %s, %d iterations: %.3e (table %.3e)" % (case, it, e, po.SIRT_F32_ERROR[(case, it)]))
+        assert 0 < e <= 1.25 * po.SIRT_F32_ERROR[(case, it)]
+    it = min(po.SOLVER_ITERATIONS)
+    ref, got = po.cgls(sino, theta, it, center), po.cgls_f32(sino, theta, it, center)
+    e = float(np.abs(got - ref).max() / np.abs(ref).max())
+    print("float32 cgls at %s, %d iterations: %.3e (table %.3e)" % (case, it, e, po.CGLS_F32_ERROR[(case, it)]))
+    assert 0 < e <= 1.25 * po.CGLS_F32_ERROR[(case, it)]
+    # a sample with R = 0 has no influence on the oracle either
+    loud = sino.copy()
+    loud[np.broadcast_to((R == 0)[:, None, :], loud.shape)] = 1e30
+    assert np.array_equal(po.sirt_f32(loud, theta, 3, center), po.sirt_f32(sino, theta, 3, center))
+
+
 def test_solvers_reduce_the_residual_and_take_a_start():
     """SIRT's residual falls monotonically in the R-weighted norm it descends in; CGLS's falls in the plain norm; a solver
     started from an earlier result continues it (SIRT exactly: it is stationary)."""

@@ -30,6 +30,27 @@ constexpr int FBP_CHUNK = 32;    // angles staged per round
 // 26 = ceil(sqrt(2) * 16) + 3.
 constexpr int FBP_SEG = 26;
 
+// The contract's geometry (include/paresis_hip.h, "the matched projector pair"), stated once: the projector is the
+// back-projector's exact transpose because both take u and its tap from here.  Voxel (i, j), h = m / 2, lies at the detector
+// coordinate u = (j - h) cos - (i - h) sin + center, in float64, the sine's product first: dj = j - h, ndi = -(i - h).
+__device__ __forceinline__ double fbp_u(double dj, double ndi, double c, double s, double center) {
+    return fma(dj, c, fma(ndi, s, center));
+}
+
+// u interpolates between sample fl = floor(u), with the weight w0 = 1 - w1, and fl + 1, with w1 = (float)(u - fl)
+struct FbpTap { double fl; float w0, w1; };
+__device__ __forceinline__ FbpTap fbp_tap(double u) {
+    const double fl = floor(u);
+    const float w1 = (float)(u - fl);
+    return {fl, 1.0f - w1, w1};
+}
+
+// Voxel (i, j) is inside the inscribed circle, or the plan has none.  W, the integer type of the squares, is each caller's
+// own: int is exact for indices inside the slice (m <= PSX_FBP_MAX_M), int64_t for any int.
+template <typename W> __device__ __forceinline__ bool fbp_lit(int i, int j, int h, int circle) {
+    return !circle || (W)(i - h) * (i - h) + (W)(j - h) * (j - h) <= (W)h * h;
+}
+
 __global__ __launch_bounds__(256) void k_fbp_pack(const float *__restrict__ sino, float2 *__restrict__ Z, int A, int n, int m,
                                                   int L, int r0, int npairs) {
     const int64_t N = (int64_t)npairs * A * L;
@@ -77,7 +98,7 @@ __global__ __launch_bounds__(256) void k_fbp_backproject(FbpArgs p) {
     const int rb = p.r0 + blockIdx.z * FBP_ROWS;                // first detector row of this workgroup
     const int pair0 = blockIdx.z * (FBP_ROWS / 2);              // its first row pair in Z
     const bool voxel = i < p.m && j < p.m;
-    const bool lit = voxel && (!p.circle || (int64_t)(i - h) * (i - h) + (int64_t)(j - h) * (j - h) <= (int64_t)h * h);
+    const bool lit = voxel && fbp_lit<int64_t>(i, j, h, p.circle);
 
     // a tile whose nearest point to the axis is outside the circle holds zeros only (the same for the whole workgroup)
     bool dark = false;
@@ -97,8 +118,8 @@ __global__ __launch_bounds__(256) void k_fbp_backproject(FbpArgs p) {
             const int na = min(FBP_CHUNK, p.A - a0);
             if (tid < na) {
                 const double c = p.cs[a0 + tid], s = p.cs[p.A + a0 + tid];
-                const double u00 = fma(cj0, c, fma(ci0, s, p.center)), u01 = fma(cj1, c, fma(ci0, s, p.center));
-                const double u10 = fma(cj0, c, fma(ci1, s, p.center)), u11 = fma(cj1, c, fma(ci1, s, p.center));
+                const double u00 = fbp_u(cj0, ci0, c, s, p.center), u01 = fbp_u(cj1, ci0, c, s, p.center);
+                const double u10 = fbp_u(cj0, ci1, c, s, p.center), u11 = fbp_u(cj1, ci1, c, s, p.center);
                 scos[tid] = c;
                 ssin[tid] = s;
                 sbase[tid] = (int)floor(fmin(fmin(u00, u01), fmin(u10, u11))) - 1;
@@ -115,10 +136,9 @@ __global__ __launch_bounds__(256) void k_fbp_backproject(FbpArgs p) {
             }
             __syncthreads();
             for (int a = 0; a < na; ++a) {
-                const double u = fma(dj, scos[a], fma(ndi, ssin[a], p.center));
-                const double fl = floor(u);
-                const float w1 = (float)(u - fl), w0 = 1.0f - w1;
-                int k = (int)fl - sbase[a];
+                const FbpTap tap = fbp_tap(fbp_u(dj, ndi, scos[a], ssin[a], p.center));
+                const float w0 = tap.w0, w1 = tap.w1;
+                int k = (int)tap.fl - sbase[a];
                 k = k < 0 ? 0 : k > FBP_SEG - 2 ? FBP_SEG - 2 : k;     // never taken inside the tile; keeps an overhanging thread's read inside the segment
                 const float4 q0 = seg[a][k], q1 = seg[a][k + 1];
                 acc[0] = fmaf(w1, q1.x, fmaf(w0, q0.x, acc[0]));
@@ -142,7 +162,7 @@ __global__ __launch_bounds__(256) void k_fbp_backproject(FbpArgs p) {
 // (lo, lo + 2/|g|) of the minor index, lo = q* - 1/|g|, at most 2 sqrt(2) long: at most 3 integers.  lo comes from the
 // inverted coordinate, affine in the line index and good to ~2e-9 (|center| <= 2^20, m <= 8192); the candidates are
 // floor(lo - 1e-6) + {1, 2, 3}: every integer above lo - 1e-6 and below lo + 2.8285 is among them (1e-6 to spare below,
-// 0.17 above).  Each candidate's u, floor and weights are the back-projector's expressions on (i, j); a candidate outside
+// 0.17 above).  Each candidate's u, floor and weights are the back-projector's: fbp_u and fbp_tap on (i, j); a candidate outside
 // the interval gets the weight 0.  The inverted coordinate only chooses where to look.
 constexpr int PRJ_KS = 64;       // samples per workgroup: one per lane
 constexpr int PRJ_LINES = 16;    // major-axis lines staged per piece: four per wave
@@ -214,7 +234,7 @@ __global__ __launch_bounds__(256) void k_fbp_project(PrjArgs p) {
             const int x = alongj ? (tid & 31) + 32 * (it >> 1) : (tid >> 4) + 16 * it;
             const int L = L0 + l, q = base[l] + x;
             const int Lc = L < m ? L : m - 1, qc = q < 0 ? 0 : q < m ? q : m - 1;
-            const bool ok = L < m && q >= 0 && q < m && (!p.circle || (Lc - h) * (Lc - h) + (qc - h) * (qc - h) <= h * h);
+            const bool ok = L < m && q >= 0 && q < m && fbp_lit<int>(Lc, qc, h, p.circle);   // inside the slice: int is exact
             const float *src = vol0 + (alongj ? (int64_t)Lc * m + qc : (int64_t)qc * m + Lc);
             float4 v = make_float4(src[0], src[o1], src[o2], src[o3]);
             if (nr < 4) {
@@ -237,10 +257,9 @@ __global__ __launch_bounds__(256) void k_fbp_project(PrjArgs p) {
 #pragma unroll
             for (int e = 0; e < PRJ_CAND; ++e) {
                 const double dq = (double)(q + e - h);
-                const double u = alongj ? fma(dq, c, fma(-dl, s, p.center)) : fma(dl, c, fma(-dq, s, p.center));
-                const double fl = floor(u);
-                const float w1 = (float)(u - fl), w0 = 1.0f - w1;
-                const float wt = fl == kd ? w0 : fl + 1.0 == kd ? w1 : 0.f;
+                // (i, j) = (L, q + e) along j, (q + e, L) along i: the orientation only chooses u's arguments
+                const FbpTap tap = fbp_tap(alongj ? fbp_u(dq, -dl, c, s, p.center) : fbp_u(dl, -dq, c, s, p.center));
+                const float wt = tap.fl == kd ? tap.w0 : tap.fl + 1.0 == kd ? tap.w1 : 0.f;
                 const float4 v = seg[l][x + e];
                 acc.x = fmaf(wt, v.x, acc.x);
                 acc.y = fmaf(wt, v.y, acc.y);
@@ -291,8 +310,7 @@ __global__ __launch_bounds__(256) void k_fbp_tv_step(TvArgs p) {
     const int64_t slice = (int64_t)(p.r0 + (int)blockIdx.z) * m * m;
     const int circle = p.circle;
     auto lit = [m, h, circle](int i, int j) {
-        return i >= 0 && i < m && j >= 0 && j < m &&
-               (!circle || (int64_t)(i - h) * (i - h) + (int64_t)(j - h) * (j - h) <= (int64_t)h * h);
+        return i >= 0 && i < m && j >= 0 && j < m && fbp_lit<int64_t>(i, j, h, circle);
     };
 
     // every global load of the workgroup is issued before the first barrier, so that all of them are in flight together:
@@ -424,6 +442,45 @@ struct psx_fbp_plan {
     DevBuf<double> He;        // [P]
 };
 
+// What the plan's three operators ask of (plan, the two arrays, n).  NAME and WHAT are literals: each message is the
+// entry point's own text.
+#define FBP_REQUIRE_RANGE(NAME, WHAT, plan, a, b, n)                                                                           \
+    PSX_REQUIRE(plan != nullptr, NAME ": null plan");                                                                          \
+    PSX_REQUIRE(a != nullptr && b != nullptr, NAME ": null " WHAT);                                                            \
+    PSX_REQUIRE(n >= 1 && (int64_t)n * plan->A * plan->m <= (int64_t)1 << 40 && (int64_t)n * plan->m * plan->m <= (int64_t)1 << 40, \
+                NAME ": n=%d detector rows outside [1, 2^40 elements]", n)
+
+// vol = scale * B sino, by row blocks of the plan's max_rows: pack, with `filtered` the plan's filter, back-projection.
+// Inlined into its two entry points, so that the library's symbols stay what they were.
+__attribute__((always_inline)) static inline int fbp_backproject(psx_fbp_plan *plan, const float *sino, int n, float *vol,
+                                                                 bool filtered, float scale, hipStream_t st) {
+    const int A = plan->A, m = plan->m, L = plan->L;
+    float2 *const Z = plan->Z.get();
+    const int tiles = (int)cdiv(m, FBP_TILE);
+    for (int r0 = 0; r0 < n; r0 += plan->max_rows) {
+        const int rows = n - r0 < plan->max_rows ? n - r0 : plan->max_rows;
+        const int npairs = (rows + 1) / 2;
+        const int64_t N = (int64_t)npairs * A * L;
+        PSX_TIMED("k_fbp_pack", st, k_fbp_pack<<<ew_grid(N, 256), 256, 0, st>>>(sino, Z, A, n, m, L, r0, npairs));
+        if (int rc = launch_check("k_fbp_pack")) return rc;
+        if (filtered) {
+            for (int rp = 0; rp < npairs; ++rp)
+                if (int rc = plan->fft.execute(FftPlan::FWD, Z + (size_t)rp * A * L, st, "rocfft_fbp_forward")) return rc;
+            PSX_TIMED("k_fbp_filter", st, k_fbp_filter<<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->He.get(), plan->P, N));
+            if (int rc = launch_check("k_fbp_filter")) return rc;
+            for (int rp = 0; rp < npairs; ++rp)
+                if (int rc = plan->fft.execute(FftPlan::INV, Z + (size_t)rp * A * L, st, "rocfft_fbp_inverse")) return rc;
+        }
+        FbpArgs a;
+        a.Z = Z; a.cs = plan->cs.get(); a.vol = vol; a.center = plan->center; a.scale = scale;
+        a.A = A; a.n = n; a.m = m; a.L = L; a.r0 = r0; a.npairs = npairs; a.circle = plan->circle;
+        const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)cdiv(rows, FBP_ROWS));
+        PSX_TIMED("k_fbp_backproject", st, k_fbp_backproject<<<grid, 256, 0, st>>>(a));
+        if (int rc = launch_check("k_fbp_backproject")) return rc;
+    }
+    return 0;
+}
+
 extern "C" {
 
 int psx_fbp_plan_create(int A, int m, const double *theta_deg, double center, int filter, int circle, int max_rows,
@@ -479,44 +536,13 @@ int psx_fbp_plan_destroy(psx_fbp_plan *plan) {
 size_t psx_fbp_plan_bytes(const psx_fbp_plan *plan) { return plan ? plan->bytes : 0; }
 
 int psx_fbp_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *stream) {
-    PSX_REQUIRE(plan != nullptr, "psx_fbp_f32: null plan");
-    PSX_REQUIRE(sino != nullptr && vol != nullptr, "psx_fbp_f32: null sinogram or volume");
-    PSX_REQUIRE(n >= 1 && (int64_t)n * plan->A * plan->m <= (int64_t)1 << 40 && (int64_t)n * plan->m * plan->m <= (int64_t)1 << 40,
-                "psx_fbp_f32: n=%d detector rows outside [1, 2^40 elements]", n);
-    hipStream_t st = (hipStream_t)stream;
-    const int A = plan->A, m = plan->m, L = plan->L;
-    float2 *const Z = plan->Z.get();
-    const int tiles = (int)cdiv(m, FBP_TILE);
-    for (int r0 = 0; r0 < n; r0 += plan->max_rows) {
-        const int rows = n - r0 < plan->max_rows ? n - r0 : plan->max_rows;
-        const int npairs = (rows + 1) / 2;
-        const int64_t N = (int64_t)npairs * A * L;
-        PSX_TIMED("k_fbp_pack", st, k_fbp_pack<<<ew_grid(N, 256), 256, 0, st>>>(sino, Z, A, n, m, L, r0, npairs));
-        if (int rc = launch_check("k_fbp_pack")) return rc;
-        if (plan->filter != PSX_FBP_NONE) {
-            for (int rp = 0; rp < npairs; ++rp)
-                if (int rc = plan->fft.execute(FftPlan::FWD, Z + (size_t)rp * A * L, st, "rocfft_fbp_forward")) return rc;
-            PSX_TIMED("k_fbp_filter", st, k_fbp_filter<<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->He.get(), plan->P, N));
-            if (int rc = launch_check("k_fbp_filter")) return rc;
-            for (int rp = 0; rp < npairs; ++rp)
-                if (int rc = plan->fft.execute(FftPlan::INV, Z + (size_t)rp * A * L, st, "rocfft_fbp_inverse")) return rc;
-        }
-        FbpArgs a;
-        a.Z = Z; a.cs = plan->cs.get(); a.vol = vol; a.center = plan->center;
-        a.scale = (float)(M_PI / (2.0 * (double)A));
-        a.A = A; a.n = n; a.m = m; a.L = L; a.r0 = r0; a.npairs = npairs; a.circle = plan->circle;
-        const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)cdiv(rows, FBP_ROWS));
-        PSX_TIMED("k_fbp_backproject", st, k_fbp_backproject<<<grid, 256, 0, st>>>(a));
-        if (int rc = launch_check("k_fbp_backproject")) return rc;
-    }
-    return 0;
+    FBP_REQUIRE_RANGE("psx_fbp_f32", "sinogram or volume", plan, sino, vol, n);
+    return fbp_backproject(plan, sino, n, vol, plan->filter != PSX_FBP_NONE, (float)(M_PI / (2.0 * (double)plan->A)),
+                           (hipStream_t)stream);
 }
 
 int psx_fbp_project_f32(psx_fbp_plan *plan, const float *vol, int n, float *sino, void *stream) {
-    PSX_REQUIRE(plan != nullptr, "psx_fbp_project_f32: null plan");
-    PSX_REQUIRE(vol != nullptr && sino != nullptr, "psx_fbp_project_f32: null volume or sinogram");
-    PSX_REQUIRE(n >= 1 && (int64_t)n * plan->A * plan->m <= (int64_t)1 << 40 && (int64_t)n * plan->m * plan->m <= (int64_t)1 << 40,
-                "psx_fbp_project_f32: n=%d detector rows outside [1, 2^40 elements]", n);
+    FBP_REQUIRE_RANGE("psx_fbp_project_f32", "volume or sinogram", plan, vol, sino, n);
     hipStream_t st = (hipStream_t)stream;
     PrjArgs a;
     a.vol = vol; a.cs = plan->cs.get(); a.sino = sino; a.center = plan->center;
@@ -535,29 +561,8 @@ int psx_fbp_project_f32(psx_fbp_plan *plan, const float *vol, int n, float *sino
 }
 
 int psx_fbp_adjoint_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol, void *stream) {
-    PSX_REQUIRE(plan != nullptr, "psx_fbp_adjoint_f32: null plan");
-    PSX_REQUIRE(sino != nullptr && vol != nullptr, "psx_fbp_adjoint_f32: null sinogram or volume");
-    PSX_REQUIRE(n >= 1 && (int64_t)n * plan->A * plan->m <= (int64_t)1 << 40 && (int64_t)n * plan->m * plan->m <= (int64_t)1 << 40,
-                "psx_fbp_adjoint_f32: n=%d detector rows outside [1, 2^40 elements]", n);
-    hipStream_t st = (hipStream_t)stream;
-    const int A = plan->A, m = plan->m, L = plan->L;
-    float2 *const Z = plan->Z.get();
-    const int tiles = (int)cdiv(m, FBP_TILE);
-    for (int r0 = 0; r0 < n; r0 += plan->max_rows) {
-        const int rows = n - r0 < plan->max_rows ? n - r0 : plan->max_rows;
-        const int npairs = (rows + 1) / 2;
-        const int64_t N = (int64_t)npairs * A * L;
-        PSX_TIMED("k_fbp_pack", st, k_fbp_pack<<<ew_grid(N, 256), 256, 0, st>>>(sino, Z, A, n, m, L, r0, npairs));
-        if (int rc = launch_check("k_fbp_pack")) return rc;
-        FbpArgs a;
-        a.Z = Z; a.cs = plan->cs.get(); a.vol = vol; a.center = plan->center;
-        a.scale = 1.0f;
-        a.A = A; a.n = n; a.m = m; a.L = L; a.r0 = r0; a.npairs = npairs; a.circle = plan->circle;
-        const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)cdiv(rows, FBP_ROWS));
-        PSX_TIMED("k_fbp_backproject", st, k_fbp_backproject<<<grid, 256, 0, st>>>(a));
-        if (int rc = launch_check("k_fbp_backproject")) return rc;
-    }
-    return 0;
+    FBP_REQUIRE_RANGE("psx_fbp_adjoint_f32", "sinogram or volume", plan, sino, vol, n);
+    return fbp_backproject(plan, sino, n, vol, false, 1.0f, (hipStream_t)stream);
 }
 
 int psx_fbp_tv_step_f32(psx_fbp_plan *plan, int n, double lambda, int nonneg, const float *u, const float *c, float *x,

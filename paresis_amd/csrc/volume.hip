@@ -36,7 +36,7 @@ __device__ __forceinline__ int wave_min(int v) {
 //
 // The 64 sample points of a step lie on a line across the slice, a voxel or so apart: read from global memory they touch
 // some 40 cache lines per load at 30 degrees (measured: 13.5 ms for 512 slices of 2048^2 on a 2048-column grid, 7.3 ms
-// staged; DESIGN.md section 4.6).  So the wave walks CHUNK steps at a time and first copies the bounding box of their
+// staged; DESIGN.md section 4.7).  So the wave walks CHUNK steps at a time and first copies the bounding box of their
 // sample points into LDS, consecutive lanes on consecutive bytes, STAGE rows' loads in flight together.  A point outside the staged box (a box too large for TILE: s above ~1.4; or, never observed, a
 // rounding that the box's margin of one voxel does not cover) is read from global memory: the box decides speed only.
 __global__ __launch_bounds__(BLOCK) void k_volume_project(psx_volume_desc d, const uint8_t *__restrict__ labels,

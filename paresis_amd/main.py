@@ -67,17 +67,7 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     modality, the method, its iterations and its weight (None but for 'tv'), and exp_dict['tomographyVolumes'] the
     {bin: [n, m, m] device tensor} volumes."""
     from . import tomography as tomo
-    if tomography_modality not in tomo.MODALITIES:
-        raise ValueError("tomography_modality must be one of %s, got %r" % (", ".join(tomo.MODALITIES), tomography_modality))
-    if tomography_modality != 'attenuation' and not tomography:
-        raise ValueError("tomography_modality is an option of tomography")
-    if (tomography_method != 'fbp' or tomography_iterations) and not tomography:
-        raise ValueError("tomography_method and tomography_iterations are options of tomography")
-    if tomography_weight is not None and not tomography:
-        raise ValueError("tomography_weight is an option of tomography")
-    tomo.check_reconstruction(tomography_method, tomography_iterations or None, weight=tomography_weight)
-    if int(tomography) < 0 or int(tomography) > _lib_max_angles():
-        raise ValueError("tomography takes 1 to %d angles, got %r" % (_lib_max_angles(), tomography))
+    tomo.check_run_options(tomography, tomography_modality, tomography_method, tomography_iterations, tomography_weight)
     if tomography and tomography_modality == 'phase':
         from .retrieval import check_method
         check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
@@ -250,13 +240,8 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     return gathered
 
 
-def _lib_max_angles():
-    from ._lib import PSX_FBP_MAX_ANGLES
-    return PSX_FBP_MAX_ANGLES
-
-
 def main(argv=None):
-    from . import retrieval
+    from . import retrieval, tomography as tomo
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--experiment", default="Fil_Nylon_ID17")
     ap.add_argument("--type", default="RayT", choices=["RayT", "Fresnel"])
@@ -283,20 +268,7 @@ def main(argv=None):
                          "propag/retrieval/{contact,thickness,phi}_<expID><fmt> under each bin's directory")
     ap.add_argument("--material", default=None,
                     help="--retrieve-propagation: the sample material the filter assumes (default: the sample's first)")
-    ap.add_argument("--tomography", type=int, default=0, metavar="A",
-                    help="contrast-phantom and label-volume (getVolumeFromFile) samples: scan A angles on [0, 180) after "
-                         "the run and write the filtered back-projection, tomography/{mu|delta}_<expID> under each bin's directory")
-    ap.add_argument("--tomography-modality", default="attenuation", choices=["attenuation", "phase"],
-                    help="--tomography: mu from -ln(Propag/White) (default), or delta from the retrieved phi (the rules and "
-                         "options of --retrieve)")
-    ap.add_argument("--tomography-method", default="fbp", choices=["fbp", "sirt", "cgls", "tv"],
-                    help="--tomography: filtered back-projection (default), or --tomography-iterations steps of SIRT, CGLS or "
-                         "total-variation reconstruction (tv, with --tomography-weight)")
-    ap.add_argument("--tomography-iterations", type=int, default=0, metavar="K",
-                    help="--tomography-method sirt|cgls|tv: the number of iterations (>= 1)")
-    ap.add_argument("--tomography-weight", type=float, default=None, metavar="W",
-                    help="--tomography-method tv: the weight of the total variation, relative to the sinogram's largest "
-                         "value (>= 0)")
+    tomo.add_tomography_options(ap)              # --tomography and its --tomography-modality, -method, -iterations, -weight
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -316,24 +288,7 @@ def main(argv=None):
         ap.error("--dark-field needs --points %d or more" % floor[True])
     if a.material is not None and not a.retrieve_propagation:
         ap.error("--material is an option of --retrieve-propagation")
-    if a.tomography < 0:
-        ap.error("--tomography takes a number of angles >= 1")
-    if a.tomography_modality != "attenuation" and not a.tomography:
-        ap.error("--tomography-modality is an option of --tomography")
-    if a.tomography_method != "fbp" and not a.tomography:
-        ap.error("--tomography-method is an option of --tomography")
-    if a.tomography_iterations != 0 and not a.tomography:
-        ap.error("--tomography-iterations is an option of --tomography")
-    if a.tomography_weight is not None and not a.tomography:
-        ap.error("--tomography-weight is an option of --tomography")
-    if (a.tomography_method == "tv") != (a.tomography_weight is not None):
-        ap.error("--tomography-weight W >= 0 goes with --tomography-method tv, and only with it")
-    if a.tomography_weight is not None and not (0 <= a.tomography_weight < float("inf")):
-        ap.error("--tomography-weight takes a finite weight >= 0")
-    if a.tomography_method == "tv" and a.tomography_iterations < 1:
-        ap.error("--tomography-method tv needs --tomography-iterations K >= 1")
-    if a.tomography_iterations < 0 or (a.tomography_method == "fbp") != (a.tomography_iterations == 0):
-        ap.error("--tomography-iterations K >= 1 goes with --tomography-method sirt or cgls, and only with them")
+    tomo.check_tomography_options(ap, a)
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
         material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality,

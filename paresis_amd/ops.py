@@ -45,6 +45,13 @@ def _need(t, dtype, name, shape=None):
     return t
 
 
+def _on(t, name, device, what="the plan"):
+    """t, when it is on `device`; `what` names who else is there, for the message."""
+    if t.device != device:
+        raise PsxError("%s is on %s, %s on %s" % (name, t.device, what, device))
+    return t
+
+
 class MaterialStack:
     """Thickness maps [nmat, Nx, Ny] float32 in HBM + per-map coefficients (see include/paresis_hip.h, "Materials").
 
@@ -651,15 +658,6 @@ def set_deterministic_scale(scale=0.0):
     check(lib().psx_set_deterministic_scale(c_float(float(scale))), "psx_set_deterministic_scale")
 
 
-def clock_probe():
-    """Shader clock in MHz the device sustains right now (psx_clock_probe: a 30 us spin on every CU behind what is queued on the
-    current stream, which it synchronises).  Diagnostics: the boxes of a pool differ by > 10 % in what they sustain."""
-    import ctypes
-    mhz = ctypes.c_float(0.0)
-    check(lib().psx_clock_probe(ctypes.byref(mhz), _stream()), "psx_clock_probe")
-    return float(mhz.value)
-
-
 def get_deterministic_scale():
     """The calling thread's replay scale (psx_get_deterministic_scale; 0 = the unit comes from each call's measured maximum)."""
     return float(lib().psx_get_deterministic_scale())
@@ -687,6 +685,14 @@ class deterministic:
         return False
 
 
+def clock_probe():
+    """Shader clock in MHz the device sustains right now (psx_clock_probe: a 30 us spin on every CU behind what is queued on the
+    current stream, which it synchronises).  Diagnostics: the boxes of a pool differ by > 10 % in what they sustain."""
+    mhz = c_float(0.0)
+    check(lib().psx_clock_probe(ctypes.byref(mhz), _stream()), "psx_clock_probe")
+    return float(mhz.value)
+
+
 def debug_switch(name, value=1):
     """A diagnostic A/B switch of the library (psx_debug_switch; include/paresis_hip.h lists the names).  Process-wide, off by
     default; for tools and tests -- the library never reads the environment."""
@@ -712,9 +718,17 @@ def fastloop(I, Dx, Dy, I2):
 
 # ---------------------------------------------------------------------------------------------- plan handles
 class _Plan:
-    """A plan of the library: the handle `_h` (set by the subclass's __init__) and `_destroy`, the name of the symbol that
-    frees it.  close() may be called any number of times; a plan that is dropped closes itself."""
+    """A plan of the library: its `device`, the handle `_h` (both set by _create, from the subclass's __init__) and
+    `_destroy`, the name of the symbol that frees it.  close() may be called any number of times; a plan that is dropped
+    closes itself."""
     _destroy = None
+
+    def _create(self, device, symbol, *args):
+        """The plan's device (None: the current one) and, on it, the handle: symbol(*args, &handle)."""
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._h = c_void_p(None)
+        with torch.cuda.device(self.device):
+            check(getattr(lib(), symbol)(*args, ctypes.byref(self._h)), symbol)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -735,11 +749,7 @@ class FresnelPlan(_Plan):
 
     def __init__(self, Nx, Ny, margin=MARGIN_FRESNEL, max_dist=4, engine=_lib.ENGINE_AUTO, device=None):
         self.Nx, self.Ny, self.margin, self.max_dist = int(Nx), int(Ny), int(margin), int(max_dist)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = c_void_p(None)
-        with torch.cuda.device(self.device):
-            check(lib().psx_fresnel_plan_create(self.Nx, self.Ny, self.margin, self.max_dist, int(engine),
-                                                ctypes.byref(self._h)), "psx_fresnel_plan_create")
+        self._create(device, "psx_fresnel_plan_create", self.Nx, self.Ny, self.margin, self.max_dist, int(engine))
         self.engine = lib().psx_fresnel_plan_engine(self._h)
         self.bytes = lib().psx_fresnel_plan_bytes(self._h)
 
@@ -821,12 +831,8 @@ class DetectorPlan(_Plan):
 
     def __init__(self, Nx, Ny, ov, nx, ny, sigma_src, sigma_psf, margin=MARGIN_DETECTOR, device=None):
         self.Nx, self.Ny, self.nx, self.ny = int(Nx), int(Ny), int(nx), int(ny)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = c_void_p(None)
-        with torch.cuda.device(self.device):
-            check(lib().psx_detector_plan_create(self.Nx, self.Ny, int(ov), self.nx, self.ny, int(margin),
-                                                 c_double(sigma_src), c_double(sigma_psf), ctypes.byref(self._h)),
-                  "psx_detector_plan_create")
+        self._create(device, "psx_detector_plan_create", self.Nx, self.Ny, int(ov), self.nx, self.ny, int(margin),
+                     c_double(sigma_src), c_double(sigma_psf))
 
     def detect(self, img, out=None):
         _need(img, torch.float32, "img", (self.Nx, self.Ny))
@@ -1019,8 +1025,7 @@ def _tracker_args(sample, reference, kmin, names, out, max_shift=None, window_se
     for nm, imgs in (("sample", S), ("reference", R)):
         for k, t in enumerate(imgs):
             _need(t, torch.float32, "%s[%d]" % (nm, k))
-            if t.device != dev:
-                raise PsxError("%s[%d] is on %s, sample[0] on %s" % (nm, k, t.device, dev))
+            _on(t, "%s[%d]" % (nm, k), dev, "sample[0]")
     if max_shift is not None and not float(max_shift) > 0.0:
         raise PsxError("max_shift must be > 0 pixels (None: no clamp), got %r" % (max_shift,))
     if out is None:
@@ -1030,8 +1035,7 @@ def _tracker_args(sample, reference, kmin, names, out, max_shift=None, window_se
         _out_count(out, names)
         for nm, t in zip(names, out):
             _need(t, torch.float32, "out " + nm, shape)
-            if t.device != dev:
-                raise PsxError("out %s is on %s, the images on %s" % (nm, t.device, dev))
+            _on(t, "out " + nm, dev, "the images")
     return S, R, dev, out, mean
 
 
@@ -1102,10 +1106,7 @@ class IntegratePlan(_Plan):
 
     def __init__(self, n, m, device=None):
         self.n, self.m = int(n), int(m)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = c_void_p(None)
-        with torch.cuda.device(self.device):
-            check(lib().psx_integrate_plan_create(self.n, self.m, ctypes.byref(self._h)), "psx_integrate_plan_create")
+        self._create(device, "psx_integrate_plan_create", self.n, self.m)
         self.bytes = lib().psx_integrate_plan_bytes(self._h)
 
     def integrate(self, gx, gy, scale=1.0, out=None):
@@ -1114,9 +1115,8 @@ class IntegratePlan(_Plan):
         shape = (self.n, self.m)
         _need(gx, torch.float32, "gx", shape)
         _need(gy, torch.float32, "gy", shape)
-        for nm, t in (("gx", gx), ("gy", gy)):
-            if t.device != self.device:
-                raise PsxError("%s is on %s, the plan on %s" % (nm, t.device, self.device))
+        _on(gx, "gx", self.device)
+        _on(gy, "gy", self.device)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
         else:
@@ -1183,8 +1183,7 @@ def paganin(images, whites, alpha, mu, plan, out=None):
             if t is None and nm == "whites":
                 continue
             _need(t, torch.float32, "%s[%d]" % (nm, b), shape)
-            if t.device != plan.device:
-                raise PsxError("%s[%d] is on %s, the plan on %s" % (nm, b, t.device, plan.device))
+            _on(t, "%s[%d]" % (nm, b), plan.device)
     if out is None:
         out = tuple(torch.empty((B,) + shape, dtype=torch.float32, device=plan.device) for _ in range(2))
     else:
@@ -1201,8 +1200,7 @@ def paganin(images, whites, alpha, mu, plan, out=None):
         lst = _image_list(o, "out " + nm, B)
         for b, t in enumerate(lst):
             _need(t, torch.float32, "out %s[%d]" % (nm, b), shape)
-            if t.device != plan.device:
-                raise PsxError("out %s[%d] is on %s, the plan on %s" % (nm, b, t.device, plan.device))
+            _on(t, "out %s[%d]" % (nm, b), plan.device)
         lists.append(lst)
     with torch.cuda.device(plan.device):
         check(lib().psx_paganin_f32(plan._h, B, _ptrs(I), None if whites is None else _ptrs(W), (c_double * B)(*alpha),
@@ -1229,12 +1227,8 @@ class FbpPlan(_Plan):
             raise PsxError("filter must be one of %s, got %r" % (sorted(_lib.FBP_FILTERS), filter))
         self.theta, self.m, self.filter, self.circle = tuple(theta), int(m), filter, bool(circle)
         self.center = float(self.m // 2 if center is None else center)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._h = c_void_p(None)
-        with torch.cuda.device(self.device):
-            check(lib().psx_fbp_plan_create(len(theta), self.m, (c_double * len(theta))(*theta), c_double(self.center),
-                                            _lib.FBP_FILTERS[filter], int(self.circle), int(max_rows), ctypes.byref(self._h)),
-                  "psx_fbp_plan_create")
+        self._create(device, "psx_fbp_plan_create", len(theta), self.m, (c_double * len(theta))(*theta), c_double(self.center),
+                     _lib.FBP_FILTERS[filter], int(self.circle), int(max_rows))
         self.bytes = lib().psx_fbp_plan_bytes(self._h)
 
     def fbp(self, sino, out=None):
@@ -1257,31 +1251,32 @@ def fbp(sino, plan, out=None):
     return _fbp_call("psx_fbp_f32", plan, sino, "sino", out, False)
 
 
+def _fbp_rows(plan, x, what, volume):
+    """n of x, a float32 tensor in HBM of a shape the plan takes: a volume [n, m, m] or a sinogram [A, n, m]."""
+    A, m = len(plan.theta), plan.m
+    _need(x, torch.float32, what)
+    if volume:
+        ok, axis, takes = x.dim() == 3 and x.shape[1] == m and x.shape[2] == m, 0, "[n >= 1, %d, %d]" % (m, m)
+    else:
+        ok, axis, takes = x.dim() == 3 and x.shape[0] == A and x.shape[2] == m, 1, "[%d, n >= 1, %d]" % (A, m)
+    if not ok or x.shape[axis] < 1:
+        raise PsxError("%s has shape %s, the plan takes %s" % (what, tuple(x.shape), takes))
+    return int(x.shape[axis])
+
+
 def _fbp_call(name, plan, x, what, out, to_sino):
     """One of the plan's three operators: x is a sinogram [A, n, m] (-> a volume [n, m, m]) or, with to_sino, a volume
     (-> a sinogram).  Every check comes before the device is touched."""
     if not isinstance(plan, FbpPlan):
         raise PsxError("plan must be an ops.FbpPlan, got %r" % type(plan))
-    A, m = len(plan.theta), plan.m
-    _need(x, torch.float32, what)
-    if to_sino:
-        ok = x.dim() == 3 and x.shape[0] >= 1 and x.shape[1] == m and x.shape[2] == m
-        takes, n = "[n >= 1, %d, %d]" % (m, m), int(x.shape[0]) if ok else 0
-        shape = (A, n, m)
-    else:
-        ok = x.dim() == 3 and x.shape[0] == A and x.shape[2] == m and x.shape[1] >= 1
-        takes, n = "[%d, n >= 1, %d]" % (A, m), int(x.shape[1]) if ok else 0
-        shape = (n, m, m)
-    if not ok:
-        raise PsxError("%s has shape %s, the plan takes %s" % (what, tuple(x.shape), takes))
-    if x.device != plan.device:
-        raise PsxError("%s is on %s, the plan on %s" % (what, x.device, plan.device))
+    n = _fbp_rows(plan, x, what, to_sino)
+    shape = (len(plan.theta), n, plan.m) if to_sino else (n, plan.m, plan.m)
+    _on(x, what, plan.device)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=plan.device)
     else:
         _need(out, torch.float32, "out", shape)
-        if out.device != plan.device:
-            raise PsxError("out is on %s, the plan on %s" % (out.device, plan.device))
+        _on(out, "out", plan.device)
     with torch.cuda.device(plan.device):
         check(getattr(lib(), name)(plan._h, _ptr(x), n, _ptr(out), _stream()), name)
     return out
@@ -1319,17 +1314,12 @@ def fbp_tv_step(plan, weight, nonneg, u, c, x, xbar_in, xbar_out, px_in, py_in, 
         raise PsxError("weight must be a number, got %r" % (weight,))
     if not (weight >= 0.0 and weight != float("inf")):
         raise PsxError("weight must be finite and >= 0, got %r" % (weight,))
-    m = plan.m
-    _need(x, torch.float32, "x")
-    if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] != m or x.shape[2] != m:
-        raise PsxError("x has shape %s, the plan takes [n >= 1, %d, %d]" % (tuple(x.shape), m, m))
-    shape = tuple(x.shape)
+    shape = (_fbp_rows(plan, x, "x", True), plan.m, plan.m)
     named = (("u", u), ("c", c), ("x", x), ("xbar_in", xbar_in), ("px_in", px_in), ("py_in", py_in),
              ("xbar_out", xbar_out), ("px_out", px_out), ("py_out", py_out))
     for nm, t in named:
         _need(t, torch.float32, nm, shape)
-        if t.device != plan.device:
-            raise PsxError("%s is on %s, the plan on %s" % (nm, t.device, plan.device))
+        _on(t, nm, plan.device)
     for k, (nm, t) in enumerate(named[6:]):
         for other, o in named[:6 + k]:
             if t.data_ptr() == o.data_ptr():
@@ -1377,8 +1367,7 @@ def volume_project(labels, nmat, angle_deg, dims, scale, voxel_m, want_lines=Fal
     n, m = int(labels.shape[0]), int(labels.shape[1])
     if box is not None:
         _need(box, torch.int32, "box", (n, 4))
-        if box.device != labels.device:
-            raise PsxError("box is on %s, labels on %s" % (box.device, labels.device))
+        _on(box, "box", labels.device, "labels")
     d = volume_desc(n, m, nmat, angle_deg, dims, scale, voxel_m, box)
     if d.nmat < 1 or d.dimX < 1 or d.dimY < 1:
         raise PsxError("volume_project: nmat=%d, study grid %d x %d" % (d.nmat, d.dimX, d.dimY))

@@ -26,10 +26,12 @@ the sample's myVolumeFile or set as myVolume).  project and scan refuse every ot
     python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase]
                                [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]] ...
 """
+import collections
 import os
 
 import numpy as np
 
+from . import _lib
 from .getk import getk
 
 MODALITIES = ("attenuation", "phase")
@@ -37,6 +39,11 @@ PHANTOM_FUNCTION = "generateContrastPhantom"
 VOLUME_FUNCTION = "getVolumeFromFile"
 ROTATABLE_FUNCTIONS = (PHANTOM_FUNCTION, VOLUME_FUNCTION)
 _plans = {}
+
+
+def _angles(angles_deg):
+    """Angles in degrees, in any array-like form -> a tuple of floats."""
+    return tuple(float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel())
 
 
 def _sinogram(sinogram, angles_deg):
@@ -48,7 +55,7 @@ def _sinogram(sinogram, angles_deg):
     ops._need(sinogram, torch.float32, "sinogram")
     if sinogram.dim() != 3:
         raise ops.PsxError("sinogram must be [A, n, m], got shape %s" % (tuple(sinogram.shape),))
-    angles = tuple(float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel())
+    angles = _angles(angles_deg)
     if len(angles) != sinogram.shape[0]:
         raise ops.PsxError("sinogram holds %d projections, angles_deg %d" % (sinogram.shape[0], len(angles)))
     return sinogram, angles
@@ -88,8 +95,7 @@ def forward_project(vol, angles_deg, center=None, circle=True):
     ops._need(vol, torch.float32, "vol")
     if vol.dim() != 3 or vol.shape[1] != vol.shape[2]:
         raise ops.PsxError("vol must be [n, m, m], got shape %s" % (tuple(vol.shape),))
-    angles = tuple(float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel())
-    return ops.fbp_project(vol, _plan(vol.device, angles, int(vol.shape[2]), center, 'none', circle))
+    return ops.fbp_project(vol, _plan(vol.device, _angles(angles_deg), int(vol.shape[2]), center, 'none', circle))
 
 
 def back_project(sinogram, angles_deg, center=None, circle=True):
@@ -106,14 +112,18 @@ def _iterations(iterations):
     return int(iterations)
 
 
-def _start(x0, sinogram):
+def _problem(sinogram, angles_deg, center, circle, x0):
+    """What sirt, cgls and tv iterate on -> (b, the checked [A, n, m] sinogram; the module's 'none' plan for it; x, the
+    start: a copy of x0, zeros for None)."""
     import torch
     from . import ops
-    n, m = int(sinogram.shape[1]), int(sinogram.shape[2])
+    b, angles = _sinogram(sinogram, angles_deg)
+    n, m = int(b.shape[1]), int(b.shape[2])
+    plan = _plan(b.device, angles, m, center, 'none', circle)
     if x0 is None:
-        return torch.zeros((n, m, m), dtype=torch.float32, device=sinogram.device)
+        return b, plan, torch.zeros((n, m, m), dtype=torch.float32, device=b.device)
     ops._need(x0, torch.float32, "x0", (n, m, m))
-    return x0.clone()
+    return b, plan, x0.clone()
 
 
 def _reciprocal(t):
@@ -131,9 +141,7 @@ def sirt(sinogram, angles_deg, iterations, center=None, circle=True, nonneg=Fals
     import torch
     from . import ops
     iterations = _iterations(iterations)
-    b, angles = _sinogram(sinogram, angles_deg)
-    plan = _plan(b.device, angles, int(b.shape[2]), center, 'none', circle)
-    x = _start(x0, b)
+    b, plan, x = _problem(sinogram, angles_deg, center, circle, x0)
     Rinv = _reciprocal(ops.fbp_project(torch.ones_like(x), plan))
     Cinv = _reciprocal(ops.fbp_adjoint(torch.ones_like(b), plan))
     res, upd = torch.empty_like(b), torch.empty_like(x)
@@ -157,9 +165,7 @@ def cgls(sinogram, angles_deg, iterations, center=None, circle=True, x0=None):
     import torch
     from . import ops
     iterations = _iterations(iterations)
-    b, angles = _sinogram(sinogram, angles_deg)
-    plan = _plan(b.device, angles, int(b.shape[2]), center, 'none', circle)
-    x = _start(x0, b)
+    b, plan, x = _problem(sinogram, angles_deg, center, circle, x0)
 
     def ratio(num, den):                               # float64 [n] -> float32 [n], 0 where either is 0
         ok = (num != 0) & (den != 0)
@@ -217,9 +223,7 @@ def tv(sinogram, angles_deg, iterations, weight, center=None, circle=True, nonne
     import torch
     from . import ops
     iterations, weight = _iterations(iterations), _weight(weight)
-    b, angles = _sinogram(sinogram, angles_deg)
-    plan = _plan(b.device, angles, int(b.shape[2]), center, 'none', circle)
-    x = _start(x0, b)
+    b, plan, x = _problem(sinogram, angles_deg, center, circle, x0)
     xbar, xbar_new = x.clone(), torch.ones_like(x)
     q = torch.ones_like(b)
     s1 = _reciprocal(ops.fbp_project(xbar_new, plan))
@@ -287,7 +291,7 @@ def project(sample, energy_keV, angles_deg, dims, pixel_um):
     dims = (int(dims[0]), int(dims[1]))
     one = None
     phi, logT = [], []
-    for angle in np.asarray(angles_deg, dtype=np.float64).ravel():
+    for angle in _angles(angles_deg):
         _turn(sample, angle, dims, pixel_um)
         if one is None:
             one = torch.ones(dims, dtype=torch.float32, device=sample.geometry_dev().device)
@@ -344,7 +348,7 @@ def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
                                retrieve_options.get('dark_field', False))
     elif retrieve_options:
         raise ValueError("%s are options of modality='phase'" % ", ".join(sorted(retrieve_options)))
-    angles = [float(a) for a in np.asarray(angles_deg, dtype=np.float64).ravel()]
+    angles = list(_angles(angles_deg))
     membrane = experiment.myMembrane
     sinos = {}
     for angle in angles:
@@ -370,29 +374,96 @@ def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
             'energy_keV': float(ed['meanEnergy'])}
 
 
-METHODS = ("fbp", "sirt", "cgls")
-REGULARISED_METHODS = ("tv",)
+# The reconstruction methods, keyed by what the user says.  Each row: the solver, and whether the method takes (and then
+# needs) iterations, takes (and needs) a weight, takes nonneg.  A new method is a new row.
+Method = collections.namedtuple("Method", "solver iterations weight nonneg")
+RECONSTRUCTIONS = {
+    'fbp': Method(fbp, False, False, False),
+    'sirt': Method(sirt, True, False, True),
+    'cgls': Method(cgls, True, False, False),
+    'tv': Method(tv, True, True, True),
+}
+METHODS = tuple(m for m, row in RECONSTRUCTIONS.items() if not row.weight)
+REGULARISED_METHODS = tuple(m for m, row in RECONSTRUCTIONS.items() if row.weight)
+DEFAULT_METHOD = 'fbp'
 
 
 def check_reconstruction(method, iterations, nonneg=False, weight=None):
     """The rules of reconstruct's method options (ValueError): needs no GPU."""
-    if method not in METHODS + REGULARISED_METHODS:
-        raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS + REGULARISED_METHODS), method))
-    if method == 'fbp':
+    row = RECONSTRUCTIONS.get(method)
+    if row is None:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(RECONSTRUCTIONS), method))
+    if not row.iterations:
         if iterations is not None:
-            raise ValueError("iterations is an option of the iterative methods (sirt, cgls), not of fbp")
+            raise ValueError("iterations is an option of the iterative methods (sirt, cgls), not of %s" % method)
     elif iterations is None:
         raise ValueError("method %r needs iterations" % method)
     else:
         _iterations(iterations)
-    if method in REGULARISED_METHODS:
+    if row.weight:
         if weight is None:
             raise ValueError("method %r needs weight" % method)
         _weight(weight)
     elif weight is not None:
         raise ValueError("weight is an option of method 'tv'")
-    if nonneg and method not in ('sirt', 'tv'):
+    if nonneg and not row.nonneg:
         raise ValueError("nonneg is an option of method 'sirt'")
+
+
+def check_run_options(angles, modality, method, iterations, weight):
+    """The rules of main.run's tomography options (ValueError; needs no GPU): `angles` projections, 0 for no tomography;
+    iterations 0 for none."""
+    if modality not in MODALITIES:
+        raise ValueError("tomography_modality must be one of %s, got %r" % (", ".join(MODALITIES), modality))
+    if modality != MODALITIES[0] and not angles:
+        raise ValueError("tomography_modality is an option of tomography")
+    if (method != DEFAULT_METHOD or iterations) and not angles:
+        raise ValueError("tomography_method and tomography_iterations are options of tomography")
+    if weight is not None and not angles:
+        raise ValueError("tomography_weight is an option of tomography")
+    check_reconstruction(method, iterations or None, weight=weight)
+    if int(angles) < 0 or int(angles) > _lib.PSX_FBP_MAX_ANGLES:
+        raise ValueError("tomography takes 1 to %d angles, got %r" % (_lib.PSX_FBP_MAX_ANGLES, angles))
+
+
+def add_tomography_options(ap):
+    """--tomography and --tomography-modality, -method, -iterations, -weight on an argparse parser: main.py's."""
+    iterative = "|".join(m for m, row in RECONSTRUCTIONS.items() if row.iterations)
+    ap.add_argument("--tomography", type=int, default=0, metavar="A",
+                    help="contrast-phantom and label-volume (getVolumeFromFile) samples: scan A angles (1..%d) on [0, 180) after "
+                         "the run and write the filtered back-projection, tomography/{mu|delta}_<expID> under each bin's directory"
+                    % _lib.PSX_FBP_MAX_ANGLES)
+    ap.add_argument("--tomography-modality", default=MODALITIES[0], choices=MODALITIES,
+                    help="--tomography: mu from -ln(Propag/White) (default), or delta from the retrieved phi (the rules and "
+                         "options of --retrieve)")
+    ap.add_argument("--tomography-method", default=DEFAULT_METHOD, choices=tuple(RECONSTRUCTIONS),
+                    help="--tomography: filtered back-projection (default), or --tomography-iterations steps of SIRT, CGLS or "
+                         "total-variation reconstruction (tv, with --tomography-weight)")
+    ap.add_argument("--tomography-iterations", type=int, default=0, metavar="K",
+                    help="--tomography-method %s: the number of iterations (>= 1)" % iterative)
+    ap.add_argument("--tomography-weight", type=float, default=None, metavar="W",
+                    help="--tomography-method %s: the weight of the total variation, relative to the sinogram's largest "
+                         "value (>= 0)" % "|".join(REGULARISED_METHODS))
+
+
+def check_tomography_options(ap, a):
+    """The rules of add_tomography_options' five, as ap.error: all are options of --tomography, and which of them the method
+    takes."""
+    if a.tomography < 0:
+        ap.error("--tomography takes a number of angles >= 1")
+    for option, given in (("modality", a.tomography_modality != MODALITIES[0]), ("method", a.tomography_method != DEFAULT_METHOD),
+                          ("iterations", a.tomography_iterations != 0), ("weight", a.tomography_weight is not None)):
+        if given and not a.tomography:
+            ap.error("--tomography-%s is an option of --tomography" % option)
+    row = RECONSTRUCTIONS[a.tomography_method]
+    if row.weight != (a.tomography_weight is not None):
+        ap.error("--tomography-weight W >= 0 goes with --tomography-method tv, and only with it")
+    if a.tomography_weight is not None and not (0 <= a.tomography_weight < float("inf")):
+        ap.error("--tomography-weight takes a finite weight >= 0")
+    if row.weight and a.tomography_iterations < 1:
+        ap.error("--tomography-method %s needs --tomography-iterations K >= 1" % a.tomography_method)
+    if a.tomography_iterations < 0 or row.iterations != (a.tomography_iterations != 0):
+        ap.error("--tomography-iterations K >= 1 goes with --tomography-method sirt or cgls, and only with them")
 
 
 def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=None, nonneg=False, weight=None):
@@ -403,17 +474,15 @@ def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=No
     clamp of sirt and tv.  weight is RELATIVE: tv runs with weight * max|sinogram| per bin, so that scaling a sinogram
     scales its volume and one weight serves -ln T and radians alike."""
     check_reconstruction(method, iterations, nonneg, weight)
+    row = RECONSTRUCTIONS[method]
+    options = {'iterations': iterations} if row.iterations else {'filter': filter}
+    if row.nonneg:
+        options['nonneg'] = nonneg
     out = {}
     for b, s in scanned['sinograms'].items():
-        if method == 'fbp':
-            vol = fbp(s, scanned['angles'], center=scanned['center'], filter=filter, circle=circle)
-        elif method == 'sirt':
-            vol = sirt(s, scanned['angles'], iterations, center=scanned['center'], circle=circle, nonneg=nonneg)
-        elif method == 'tv':
-            vol = tv(s, scanned['angles'], iterations, float(weight) * float(s.abs().max()), center=scanned['center'],
-                     circle=circle, nonneg=nonneg)
-        else:
-            vol = cgls(s, scanned['angles'], iterations, center=scanned['center'], circle=circle)
+        if row.weight:
+            options['weight'] = float(weight) * float(s.abs().max())
+        vol = row.solver(s, scanned['angles'], center=scanned['center'], circle=circle, **options)
         out[b] = (mu_volume(vol, scanned['voxel_m']) if scanned['modality'] == 'attenuation'
                   else delta_volume(vol, scanned['energy_keV'], scanned['voxel_m']))
     return out

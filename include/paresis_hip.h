@@ -502,6 +502,21 @@ int psx_paganin_f32(psx_integrate_plan *plan, int B, const float *const *image, 
  *   q = Re IFFT_P( FFT_P(line zero-padded to P) * H )[:m].  Two lines share one complex transform (rocFFT, single
  *   precision): the real part of the filtered pair is that of a filter with the even part (H[k] + H[P-k])/2, which is what
  *   the device multiplies by, so the two lines do not mix.  PSX_FBP_NONE copies the lines and runs no transform.
+ * Differential filters (PSX_FBP_DIFFERENTIAL set): the line holds d(sinogram)/d(column), per detector pixel -- what
+ *   differential phase contrast (speckle tracking, gratings) measures.  The ramp is the derivative followed by a Hilbert
+ *   transform, 2|f| = (i 2 pi f) * (-i sgn f / pi), so such a line takes the Hilbert filter alone:
+ *   g[j] = 2/(pi^2 s) for odd signed lag s (s = j for j < P/2, s = j - P for j > P/2), 0 for even s and at j = P/2;
+ *   G = FFT_P(g), formed in float64 on the host, is purely imaginary and odd; Ho = Im G with Ho[0] = Ho[P/2] = 0 exactly;
+ *   PSX_FBP_HILBERT_HANN multiplies Ho by the window of PSX_FBP_HANN;
+ *   q = Re IFFT_P( FFT_P(line zero-padded to P) * i*Ho )[:m], i.e. q[k] = sum_j g[k - j]*line[j].  The real part is that of
+ *   the filter with the odd part (Ho[k] - Ho[P-k])/2, which is Hermitian as i*Ho: the device multiplies the pair's
+ *   transform Z by it, Z <- (-Z.y*w, Z.x*w) with w the odd part over P in float64, and the two lines do not mix.
+ *   Every lag |k - j| < m <= P/2 is inside the kernel, so the convolution of a line that vanishes off the detector is
+ *   linear, not wrapped.  Ho[0] = 0 removes a constant offset of the padded line, not of the line: an offset c on the m
+ *   samples is a box, whose Hilbert transform grows towards its ends -- it is NOT removed exactly (an offset of 1 % of the
+ *   largest |dp/du| moves the three-blob volume of tests/_hilbert_oracle.py by up to 1.0 % of its peak at m = 64).
+ *   Back-projection and the pi/(2A) scale are the ramp's: with this sign psx_fbp_f32 on dp/du (u the column index)
+ *   reproduces PSX_FBP_RAMP on p, to discretisation.
  * Back-projection, h = m / 2 rounded down, c_a = cos(theta_a*pi/180), s_a = sin(theta_a*pi/180) in float64 on the host:
  *   u = (j - h)*c_a - (i - h)*s_a + center in float64;  q(u) by linear interpolation between the samples with
  *   q[-1] = q[m] = 0, and 0 for u <= -1 or u >= m (continuous in u, unlike np.interp(left=0, right=0));
@@ -515,6 +530,9 @@ int psx_paganin_f32(psx_integrate_plan *plan, int B, const float *const *image, 
 #define PSX_FBP_RAMP 0
 #define PSX_FBP_HANN 1
 #define PSX_FBP_NONE 2
+#define PSX_FBP_DIFFERENTIAL 16            /* the line holds d(sinogram)/d(column), per pixel */
+#define PSX_FBP_HILBERT      (PSX_FBP_DIFFERENTIAL | PSX_FBP_RAMP)   /* 16 */
+#define PSX_FBP_HILBERT_HANN (PSX_FBP_DIFFERENTIAL | PSX_FBP_HANN)   /* 17 */
 #define PSX_FBP_MAX_ANGLES 4096
 #define PSX_FBP_MAX_M 8192
 typedef struct psx_fbp_plan psx_fbp_plan;

@@ -18,6 +18,7 @@ PSX_MAX_UMPA_SEARCH = 8
 PSX_MAX_PAGANIN = 64
 PSX_FBP_MAX_ANGLES, PSX_FBP_MAX_M = 4096, 8192
 FBP_FILTERS = {"ramp": 0, "hann": 1, "none": 2}      # PSX_FBP_RAMP / _HANN / _NONE
+FBP_DIFFERENTIAL_FILTERS = {"hilbert": 16, "hilbert-hann": 17}   # PSX_FBP_HILBERT / _HILBERT_HANN: the line is d/d(column)
 PSX_PHANTOM_TUBES = 12
 PSX_VOLUME_MAX_MAT = 16
 PSX_MAX_DIST = 8
@@ -27,7 +28,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class PsxError(RuntimeError):

@@ -2,7 +2,8 @@
 //   k_fbp_pack     Z[rp][a][k] = (sino[a][r0+2rp][k], sino[a][r0+2rp+1][k]) for k < m, 0 up to the line's length L: two
 //                  detector rows per complex line (L = P with a filter, m without)
 //   rocFFT         P-point forward transforms, A lines per row pair and launch
-//   k_fbp_filter   Z *= He/P, He the even part of the real filter H (float64 table): the pair stays separable
+//   k_fbp_filter   Z *= He/P, He the even part of the real filter H (float64 table): the pair stays separable.  The Hilbert
+//                  filters of a differential sinogram: Z *= i Ho/P, Ho the odd part -- Hermitian too, so the same holds
 //   rocFFT         inverse; Z.x / Z.y are now the filtered lines of the two rows
 //   k_fbp_backproject   one workgroup per 16 x 16 tile of the slice and block of 4 detector rows (two row pairs)
 // The filtered sinogram is never cropped or copied: the back-projector reads the float2 lines of Z as they are, and a row
@@ -69,11 +70,15 @@ __global__ __launch_bounds__(256) void k_fbp_pack(const float *__restrict__ sino
     }
 }
 
-__global__ __launch_bounds__(256) void k_fbp_filter(float2 *__restrict__ Z, const double *__restrict__ He, int P, int64_t N) {
+// Z *= T[k] for the even table of the ramp filters, Z *= i T[k] for the odd table of the Hilbert filters (DIFFERENTIAL):
+// either multiplier is Hermitian, so the two rows of a pair stay in Z.x and Z.y
+template <bool DIFFERENTIAL>
+__global__ __launch_bounds__(256) void k_fbp_filter(float2 *__restrict__ Z, const double *__restrict__ T, int P, int64_t N) {
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (int64_t)gridDim.x * blockDim.x) {
-        const double w = He[p & (P - 1)];
+        const double w = T[p & (P - 1)];
         const float2 z = Z[p];
-        Z[p] = make_float2((float)((double)z.x * w), (float)((double)z.y * w));
+        Z[p] = DIFFERENTIAL ? make_float2((float)(-(double)z.y * w), (float)((double)z.x * w))
+                            : make_float2((float)((double)z.x * w), (float)((double)z.y * w));
     }
 }
 
@@ -409,25 +414,33 @@ void fft_f64(std::vector<std::complex<double>> &x) {
     }
 }
 
-// He[k]/P: the even part of H = 2 Re FFT(f) (times the shifted Hann window), the inverse transform's 1/P folded in
+// The table the filter kernel multiplies by, the inverse transform's 1/P folded in.  Ramp filters: He[k]/P, the even part of
+// H = 2 Re FFT(f).  Hilbert filters (PSX_FBP_DIFFERENTIAL): Ho[k]/P, the odd part of H = Im FFT(g) with H[0] = H[P/2] = 0,
+// g[j] = 2/(pi^2 s) for odd signed lag s.  Either H is first multiplied by the shifted Hann window if the filter has one.
 std::vector<double> filter_table(int P, int filter) {
+    const bool differential = (filter & PSX_FBP_DIFFERENTIAL) != 0;
+    const bool hann = (filter & ~PSX_FBP_DIFFERENTIAL) == PSX_FBP_HANN;
     std::vector<std::complex<double>> f((size_t)P);
     for (int jx = 0; jx < P; ++jx) {
         const int jj = jx < P - jx ? jx : P - jx;
         const double pj = M_PI * (double)jj;
-        f[jx] = jx == 0 ? 0.25 : (jj & 1) ? -1.0 / (pj * pj) : 0.0;
+        if (differential)
+            f[jx] = (jj & 1) ? (jx < P / 2 ? 2.0 : -2.0) / (M_PI * pj) : 0.0;
+        else
+            f[jx] = jx == 0 ? 0.25 : (jj & 1) ? -1.0 / (pj * pj) : 0.0;
     }
     fft_f64(f);
-    std::vector<double> H((size_t)P), He((size_t)P);
+    std::vector<double> H((size_t)P), T((size_t)P);
     for (int k = 0; k < P; ++k) {
-        H[k] = 2.0 * f[k].real();
-        if (filter == PSX_FBP_HANN) {
+        H[k] = differential ? (k == 0 || k == P / 2 ? 0.0 : f[k].imag()) : 2.0 * f[k].real();
+        if (hann) {
             const int nn = (k + P / 2) % P;                       // fftshift of an even length
             H[k] *= 0.5 - 0.5 * std::cos(PSX_TWO_PI * (double)nn / (double)(P - 1));
         }
     }
-    for (int k = 0; k < P; ++k) He[k] = 0.5 * (H[k] + H[(P - k) % P]) / (double)P;
-    return He;
+    const double sign = differential ? -1.0 : 1.0;
+    for (int k = 0; k < P; ++k) T[k] = 0.5 * (H[k] + sign * H[(P - k) % P]) / (double)P;
+    return T;
 }
 
 }  // namespace
@@ -439,7 +452,7 @@ struct psx_fbp_plan {
     FftPlan fft;              // forward + inverse, P points, A lines (one row pair)
     DevBuf<float2> Z;         // [max_rows / 2][A][L]
     DevBuf<double> cs;        // [A] cos, [A] sin
-    DevBuf<double> He;        // [P]
+    DevBuf<double> table;     // [P]: filter_table's
 };
 
 // What the plan's three operators ask of (plan, the two arrays, n).  NAME and WHAT are literals: each message is the
@@ -466,7 +479,10 @@ __attribute__((always_inline)) static inline int fbp_backproject(psx_fbp_plan *p
         if (filtered) {
             for (int rp = 0; rp < npairs; ++rp)
                 if (int rc = plan->fft.execute(FftPlan::FWD, Z + (size_t)rp * A * L, st, "rocfft_fbp_forward")) return rc;
-            PSX_TIMED("k_fbp_filter", st, k_fbp_filter<<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->He.get(), plan->P, N));
+            if (plan->filter & PSX_FBP_DIFFERENTIAL)
+                PSX_TIMED("k_fbp_filter_hilbert", st, k_fbp_filter<true><<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->table.get(), plan->P, N));
+            else
+                PSX_TIMED("k_fbp_filter", st, k_fbp_filter<false><<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->table.get(), plan->P, N));
             if (int rc = launch_check("k_fbp_filter")) return rc;
             for (int rp = 0; rp < npairs; ++rp)
                 if (int rc = plan->fft.execute(FftPlan::INV, Z + (size_t)rp * A * L, st, "rocfft_fbp_inverse")) return rc;
@@ -493,7 +509,8 @@ int psx_fbp_plan_create(int A, int m, const double *theta_deg, double center, in
     for (int a = 0; a < A; ++a)
         PSX_REQUIRE(std::isfinite(theta_deg[a]), "psx_fbp_plan_create: theta[%d]=%g is not finite", a, theta_deg[a]);
     PSX_REQUIRE(std::isfinite(center) && std::fabs(center) <= 1048576.0, "psx_fbp_plan_create: center=%g is not a finite column within 2^20", center);
-    PSX_REQUIRE(filter == PSX_FBP_RAMP || filter == PSX_FBP_HANN || filter == PSX_FBP_NONE, "psx_fbp_plan_create: unknown filter %d", filter);
+    PSX_REQUIRE(filter == PSX_FBP_RAMP || filter == PSX_FBP_HANN || filter == PSX_FBP_NONE || filter == PSX_FBP_HILBERT ||
+                filter == PSX_FBP_HILBERT_HANN, "psx_fbp_plan_create: unknown filter %d", filter);
     PSX_REQUIRE(circle == 0 || circle == 1, "psx_fbp_plan_create: circle=%d is not 0 or 1", circle);
     PSX_REQUIRE(max_rows >= 0 && max_rows <= 4096, "psx_fbp_plan_create: max_rows=%d outside [0,4096]", max_rows);
 
@@ -517,13 +534,13 @@ int psx_fbp_plan_create(int A, int m, const double *theta_deg, double center, in
     }
     if (int rc = p->cs.upload(cs.data(), cs.size())) return rc;
     if (filter != PSX_FBP_NONE) {
-        const std::vector<double> He = filter_table(P, filter);
-        if (int rc = p->He.upload(He.data(), He.size())) return rc;
+        const std::vector<double> table = filter_table(P, filter);
+        if (int rc = p->table.upload(table.data(), table.size())) return rc;
         const size_t lengths[1] = {(size_t)P};
         if (int rc = p->fft.create(FftPlan::BOTH, rocfft_precision_single, 1, lengths, (size_t)A)) return rc;
     }
     if (int rc = p->Z.alloc((size_t)(p->max_rows / 2) * A * p->L)) return rc;
-    p->bytes = p->Z.bytes() + p->cs.bytes() + p->He.bytes() + p->fft.work_bytes();
+    p->bytes = p->Z.bytes() + p->cs.bytes() + p->table.bytes() + p->fft.work_bytes();
     *plan = p.release();
     return 0;
 }

@@ -5,7 +5,7 @@
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
                                [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa|umpa-df --window W --search M]]
                                [--retrieve-propagation [--material NAME]]
-                               [--tomography A [--tomography-modality attenuation|phase]
+                               [--tomography A [--tomography-modality attenuation|phase [--tomography-differential]]
                                 [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
@@ -27,7 +27,9 @@ rules and options of --retrieve) under each bin's directory: one [n, m, m] file 
 slices.  --tomography-method sirt|cgls reconstructs with --tomography-iterations K >= 1 steps of SIRT or CGLS on the matched
 projector pair instead (tomography.sirt / cgls): the methods for few angles.  --tomography-method tv takes K steps of
 total-variation reconstruction (tomography.tv) with --tomography-weight W >= 0, relative to the sinogram's largest value: the
-model of the phantom's piecewise constant slices, for fewer angles still.
+model of the phantom's piecewise constant slices, for fewer angles still.  --tomography-differential (with
+--tomography-modality phase and --tomography-method fbp only) skips the phase integration: the tracked gradient across the
+rotation axis is back-projected through a Hilbert filter, and tomography/delta_<expID> is written as before.
 """
 import argparse
 import datetime
@@ -39,7 +41,7 @@ import numpy as np
 
 def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
         method='lcs', window=2, search=3, propagation=False, material=None, tomography=0, tomography_modality='attenuation',
-        tomography_method='fbp', tomography_iterations=0, tomography_weight=None):
+        tomography_method='fbp', tomography_iterations=0, tomography_weight=None, tomography_differential=False):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
@@ -63,11 +65,14 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     tomography_method 'sirt' or 'cgls' with tomography_iterations >= 1 reconstructs iteratively instead of by filtered
     back-projection ('fbp', which takes no iterations); 'tv' with tomography_iterations >= 1 and tomography_weight >= 0
     (relative to the sinogram's largest value, as tomography.reconstruct takes it; refused for the other methods)
-    reconstructs with total variation.  exp_dict['tomographyParams'] then holds the angles, the centre, the voxel size, the
-    modality, the method, its iterations and its weight (None but for 'tv'), and exp_dict['tomographyVolumes'] the
-    {bin: [n, m, m] device tensor} volumes."""
+    reconstructs with total variation.  tomography_differential (modality 'phase' and method 'fbp' only): the scan keeps
+    the tracked gradient across the rotation axis instead of the integrated phase (tomography.scan(..., differential=True))
+    and the reconstruction goes through the Hilbert filter.  exp_dict['tomographyParams'] then holds the angles, the centre,
+    the voxel size, the modality, whether the scan was differential, the method, its iterations and its weight (None but for
+    'tv'), and exp_dict['tomographyVolumes'] the {bin: [n, m, m] device tensor} volumes."""
     from . import tomography as tomo
-    tomo.check_run_options(tomography, tomography_modality, tomography_method, tomography_iterations, tomography_weight)
+    tomo.check_run_options(tomography, tomography_modality, tomography_method, tomography_iterations, tomography_weight,
+                           differential=tomography_differential)
     if tomography and tomography_modality == 'phase':
         from .retrieval import check_method
         check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
@@ -221,10 +226,12 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
             options = {'method': method, 'max_shift': max_shift, 'dark_field': dark_field, 'window': window, 'search': search}
             keep = TRACKERS[(method, bool(dark_field))].options + ('method', 'dark_field')
             options = {k: v for k, v in options.items() if k in keep}
+            if tomography_differential:
+                options['differential'] = True
         scanned = tomo.scan(experiment, angles, modality=tomography_modality, **options)
         volumes = tomo.reconstruct(scanned, method=tomography_method, iterations=tomography_iterations or None,
                                    weight=tomography_weight)
-        exp_dict['tomographyParams'] = {k: scanned[k] for k in ('angles', 'center', 'voxel_m', 'modality', 'energy_keV')}
+        exp_dict['tomographyParams'] = {k: scanned[k] for k in ('angles', 'center', 'voxel_m', 'modality', 'differential', 'energy_keV')}
         exp_dict['tomographyParams'].update(method=tomography_method, iterations=int(tomography_iterations),
                                              weight=None if tomography_weight is None else float(tomography_weight))
         if save:
@@ -268,7 +275,7 @@ def main(argv=None):
                          "propag/retrieval/{contact,thickness,phi}_<expID><fmt> under each bin's directory")
     ap.add_argument("--material", default=None,
                     help="--retrieve-propagation: the sample material the filter assumes (default: the sample's first)")
-    tomo.add_tomography_options(ap)              # --tomography and its --tomography-modality, -method, -iterations, -weight
+    tomo.add_tomography_options(ap)              # --tomography and its --tomography-modality, -differential, -method, ...
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
                 'overSampling': a.oversampling, 'nbExpPoints': a.points, 'simulation_type': a.type,
@@ -293,7 +300,7 @@ def main(argv=None):
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
         material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality,
         tomography_method=a.tomography_method, tomography_iterations=a.tomography_iterations,
-        tomography_weight=a.tomography_weight)
+        tomography_weight=a.tomography_weight, tomography_differential=a.tomography_differential)
 
 
 if __name__ == "__main__":

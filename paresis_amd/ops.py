@@ -1213,7 +1213,8 @@ def paganin(images, whites, alpha, mu, plan, out=None):
 class FbpPlan(_Plan):
     """psx_fbp_plan (the contract is in include/paresis_hip.h): parallel-beam filtered back-projection of [A, n, m] sinograms
     at the A angles `theta_deg` (degrees, any values) about detector column `center` (None: m // 2, radon's), with filter
-    'ramp', 'hann' or 'none', onto [n, m, m] volumes, zero outside the inscribed circle when `circle`.  The plan owns the
+    'ramp', 'hann' or 'none' -- or 'hilbert' / 'hilbert-hann' for a DIFFERENTIAL sinogram, d/d(column) per detector pixel
+    (_lib.FBP_DIFFERENTIAL_FILTERS) --, onto [n, m, m] volumes, zero outside the inscribed circle when `circle`.  The plan owns the
     angle and filter tables, the rocFFT plans and the filtered sinogram of max_rows detector rows (0: the library's
     choice), so n may differ from call to call; `bytes` reports them."""
     _destroy = "psx_fbp_plan_destroy"
@@ -1223,12 +1224,13 @@ class FbpPlan(_Plan):
             theta = [float(v) for v in theta_deg]
         except (TypeError, ValueError):
             raise PsxError("theta_deg must be a sequence of angles in degrees, got %r" % (theta_deg,))
-        if filter not in _lib.FBP_FILTERS:
-            raise PsxError("filter must be one of %s, got %r" % (sorted(_lib.FBP_FILTERS), filter))
+        filters = dict(_lib.FBP_FILTERS, **_lib.FBP_DIFFERENTIAL_FILTERS)
+        if filter not in filters:
+            raise PsxError("filter must be one of %s, got %r" % (sorted(filters), filter))
         self.theta, self.m, self.filter, self.circle = tuple(theta), int(m), filter, bool(circle)
         self.center = float(self.m // 2 if center is None else center)
         self._create(device, "psx_fbp_plan_create", len(theta), self.m, (c_double * len(theta))(*theta), c_double(self.center),
-                     _lib.FBP_FILTERS[filter], int(self.circle), int(max_rows))
+                     filters[filter], int(self.circle), int(max_rows))
         self.bytes = lib().psx_fbp_plan_bytes(self._h)
 
     def fbp(self, sino, out=None):

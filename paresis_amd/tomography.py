@@ -4,6 +4,8 @@
                                         include/paresis_hip.h): [A, n, m] maps, one per angle -> [n, m, m], a slice per
                                         detector row.  The sinogram holds LINE INTEGRALS IN PIXELS of the slice's voxel: a
                                         map in physical units (phi in radians, -ln T) gives the quantity per voxel length.
+                                        filter='hilbert' | 'hilbert-hann': the sinogram is DIFFERENTIAL, d/d(column) of
+                                        those integrals per detector pixel, and is back-projected through a Hilbert filter.
     forward_project(vol, angles_deg, ...)    the matched pair behind the iterative methods (ops.fbp_project / fbp_adjoint):
     back_project(sinogram, angles_deg, ...)  B^T vol, the exact transpose of fbp's interpolation, and B sinogram, unscaled
     sirt(sinogram, angles_deg, iterations, ..., nonneg)   SIRT and CGLS on min |B^T x - b|: what few angles call for,
@@ -13,7 +15,7 @@
     delta_volume(vol, energy_keV, voxel_m)   phi = -k * integral(delta) dl  ->  delta = -vol/(k*voxel), k = getk(E)
     mu_volume(vol, voxel_m)                  -ln T = integral(mu) dl         ->  mu = vol/voxel (1/m)
     project(sample, energy_keV, angles_deg, dims, pixel_um)   the sample's ideal sinograms phi and -ln T on the study grid
-    scan(experiment, angles_deg, modality)                    the real chain once per angle -> sinograms per energy bin
+    scan(experiment, angles_deg, modality, differential)      the real chain once per angle -> sinograms per energy bin
     rotation_center(experiment)                               the detector column of the rotation axis of such a scan
     save_volume(vol, path, fmt)
 
@@ -23,7 +25,14 @@ the same model (scikit-image radon of a slice): the contrast phantom (Samples/ge
 discs on a slice) and a volume of material labels the user brings (Samples/getVolumeFromFile.py: uint8 [n, m, m], from
 the sample's myVolumeFile or set as myVolume).  project and scan refuse every other sample.
 
-    python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase]
+Differential phase tomography: speckle tracking measures the phase GRADIENT.  scan(modality='phase') integrates each angle's
+(dx, dy) into phi (Frankot-Chellappa) and fbp's ramp differentiates it again; scan(..., differential=True) keeps the
+gradient across the rotation axis instead -- dy times retrieval.gradient_scale, radians per detector pixel -- and
+reconstruct back-projects it through the Hilbert filter: 2|f| = (i 2 pi f) * (-i sgn f / pi), the ramp is the derivative
+followed by a Hilbert transform.  No two-dimensional integration, with its mirror extension and its low-frequency errors
+along whole rows, is run.
+
+    python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase [--tomography-differential]]
                                [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]] ...
 """
 import collections
@@ -79,8 +88,11 @@ def fbp(sinogram, angles_deg, center=None, filter='ramp', circle=True):
     retrieval.paganin return them) taken at angles_deg (A angles in degrees, any values) -> the [n, m, m] float32 volume on
     the same device: vol[r] is the slice of detector row r in the orientation of contrast_phantom_slices.  center: the
     detector column of the rotation axis (None: m // 2, scikit-image radon's; rotation_center for a scan).  filter:
-    'ramp', 'hann' or 'none'.  circle: zero outside the inscribed circle.  One plan per (device, A, m, angles, center,
-    filter, circle) is kept for the process's lifetime."""
+    'ramp', 'hann' or 'none'; 'hilbert' or 'hilbert-hann' (the Hilbert filter, alone or under the Hann window): the sinogram
+    is then the DERIVATIVE of those line integrals along axis 2, per detector pixel, and the volume is what 'ramp' / 'hann'
+    give on the integrals themselves, to discretisation.  A constant offset of such a sinogram is not removed exactly.
+    circle: zero outside the inscribed circle.  One plan per (device, A, m, angles, center, filter, circle) is kept for the
+    process's lifetime."""
     from . import ops
     sinogram, angles = _sinogram(sinogram, angles_deg)
     return ops.fbp(sinogram, _plan(sinogram.device, angles, int(sinogram.shape[2]), center, filter, circle))
@@ -322,14 +334,19 @@ def voxel_size(experiment):
     return float(experiment.myDetector.det_param['myPixelSize']) * 1e-6 / float(experiment.exp_dict['magnification'])
 
 
-def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
+def scan(experiment, angles_deg, modality='attenuation', differential=False, **retrieve_options):
     """Run the chain of `experiment` (an Experiment, or the exp_dict of one) once per angle of angles_deg, all of its
     nbExpPoints membrane positions each time, and collect one map per angle and energy bin ->
     {'sinograms': {bin: [A, n, m] float32 tensor}, 'angles': the angles, 'center': rotation_center(experiment),
-     'voxel_m': voxel_size(experiment), 'modality': modality, 'energy_keV': the run's mean detected energy}.
+     'voxel_m': voxel_size(experiment), 'modality': modality, 'differential': differential,
+     'energy_keV': the run's mean detected energy}.
     modality='attenuation': -ln(Propag/White) of position 0 (the propagation image over its flat field; any number of
     positions), for mu_volume.  modality='phase': 'phi' of retrieval.retrieve on the angle's positions (retrieve_options:
     method, max_shift, dark_field, window, search -- bound by retrieval.check_method's rules), for delta_volume.
+    differential=True (modality 'phase' only, ValueError otherwise): the tracker runs without the integration
+    (retrieval.retrieve(results, None, ...)) and the angle's map is dy * retrieval.gradient_scale(...), dy the displacement
+    along map axis 1 = sinogram axis 2: d(phi)/d(column) in radians per detector pixel, what reconstruct then back-projects
+    through the Hilbert filter.
     The sample of interest must be the contrast phantom or a label volume (ValueError otherwise): per angle its myAngle is
     set and its geometry rebuilt on the study grid.  A membrane that has a geometry function gets its geometry per position as main.run
     does; an injected one keeps the geometry it has."""
@@ -337,6 +354,7 @@ def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
     from . import retrieval
     if modality not in MODALITIES:
         raise ValueError("modality must be one of %s, got %r" % (", ".join(MODALITIES), modality))
+    check_differential(differential, modality, DEFAULT_METHOD)
     if isinstance(experiment, dict):
         from .Experiment import Experiment
         experiment = Experiment(experiment)
@@ -366,12 +384,16 @@ def scan(experiment, angles_deg, modality='attenuation', **retrieve_options):
             maps = {b: -torch.log(P[b] / W[b]) for b in range(P.shape[0])}
         else:
             params = retrieval.params_from_experiment(experiment)
-            maps = {b: r['phi'].clone() for b, r in retrieval.retrieve(results, params, **retrieve_options).items()}
+            if differential:
+                scale = retrieval.gradient_scale(**params)
+                maps = {b: r['dy'] * scale for b, r in retrieval.retrieve(results, None, **retrieve_options).items()}
+            else:
+                maps = {b: r['phi'].clone() for b, r in retrieval.retrieve(results, params, **retrieve_options).items()}
         for b, v in maps.items():
             sinos.setdefault(b, []).append(v)
     return {'sinograms': {b: torch.stack(v) for b, v in sinos.items()}, 'angles': angles,
             'center': rotation_center(experiment), 'voxel_m': voxel_size(experiment), 'modality': modality,
-            'energy_keV': float(ed['meanEnergy'])}
+            'differential': bool(differential), 'energy_keV': float(ed['meanEnergy'])}
 
 
 # The reconstruction methods, keyed by what the user says.  Each row: the solver, and whether the method takes (and then
@@ -386,6 +408,8 @@ RECONSTRUCTIONS = {
 METHODS = tuple(m for m, row in RECONSTRUCTIONS.items() if not row.weight)
 REGULARISED_METHODS = tuple(m for m, row in RECONSTRUCTIONS.items() if row.weight)
 DEFAULT_METHOD = 'fbp'
+# what reconstruct's filter means for a differential scan: the same window on the Hilbert filter
+DIFFERENTIAL_FILTER_OF = {'ramp': 'hilbert', 'hann': 'hilbert-hann'}
 
 
 def check_reconstruction(method, iterations, nonneg=False, weight=None):
@@ -410,11 +434,23 @@ def check_reconstruction(method, iterations, nonneg=False, weight=None):
         raise ValueError("nonneg is an option of method 'sirt'")
 
 
-def check_run_options(angles, modality, method, iterations, weight):
+def check_differential(differential, modality, method):
+    """The differential route's rules (ValueError): a phase sinogram, reconstructed by filtered back-projection."""
+    if differential and modality != 'phase':
+        raise ValueError("differential is an option of modality 'phase', not of %r" % (modality,))
+    if differential and method != 'fbp':
+        raise ValueError("a differential sinogram is reconstructed by method 'fbp' (the Hilbert filter), not by %r: the "
+                         "iterative methods solve B^T x = b for integral data" % (method,))
+
+
+def check_run_options(angles, modality, method, iterations, weight, differential=False):
     """The rules of main.run's tomography options (ValueError; needs no GPU): `angles` projections, 0 for no tomography;
     iterations 0 for none."""
     if modality not in MODALITIES:
         raise ValueError("tomography_modality must be one of %s, got %r" % (", ".join(MODALITIES), modality))
+    if differential and not angles:
+        raise ValueError("tomography_differential is an option of tomography")
+    check_differential(differential, modality, method)
     if modality != MODALITIES[0] and not angles:
         raise ValueError("tomography_modality is an option of tomography")
     if (method != DEFAULT_METHOD or iterations) and not angles:
@@ -427,7 +463,7 @@ def check_run_options(angles, modality, method, iterations, weight):
 
 
 def add_tomography_options(ap):
-    """--tomography and --tomography-modality, -method, -iterations, -weight on an argparse parser: main.py's."""
+    """--tomography and --tomography-modality, -differential, -method, -iterations, -weight on an argparse parser: main.py's."""
     iterative = "|".join(m for m, row in RECONSTRUCTIONS.items() if row.iterations)
     ap.add_argument("--tomography", type=int, default=0, metavar="A",
                     help="contrast-phantom and label-volume (getVolumeFromFile) samples: scan A angles (1..%d) on [0, 180) after "
@@ -436,6 +472,9 @@ def add_tomography_options(ap):
     ap.add_argument("--tomography-modality", default=MODALITIES[0], choices=MODALITIES,
                     help="--tomography: mu from -ln(Propag/White) (default), or delta from the retrieved phi (the rules and "
                          "options of --retrieve)")
+    ap.add_argument("--tomography-differential", action="store_true",
+                    help="--tomography-modality phase with --tomography-method fbp: back-project the tracked gradient across "
+                         "the rotation axis through a Hilbert filter; no phase integration is run")
     ap.add_argument("--tomography-method", default=DEFAULT_METHOD, choices=tuple(RECONSTRUCTIONS),
                     help="--tomography: filtered back-projection (default), or --tomography-iterations steps of SIRT, CGLS or "
                          "total-variation reconstruction (tv, with --tomography-weight)")
@@ -447,14 +486,17 @@ def add_tomography_options(ap):
 
 
 def check_tomography_options(ap, a):
-    """The rules of add_tomography_options' five, as ap.error: all are options of --tomography, and which of them the method
+    """The rules of add_tomography_options' six, as ap.error: all are options of --tomography, and which of them the method
     takes."""
     if a.tomography < 0:
         ap.error("--tomography takes a number of angles >= 1")
     for option, given in (("modality", a.tomography_modality != MODALITIES[0]), ("method", a.tomography_method != DEFAULT_METHOD),
-                          ("iterations", a.tomography_iterations != 0), ("weight", a.tomography_weight is not None)):
+                          ("iterations", a.tomography_iterations != 0), ("weight", a.tomography_weight is not None),
+                          ("differential", a.tomography_differential)):
         if given and not a.tomography:
             ap.error("--tomography-%s is an option of --tomography" % option)
+    if a.tomography_differential and (a.tomography_modality != 'phase' or a.tomography_method != DEFAULT_METHOD):
+        ap.error("--tomography-differential goes with --tomography-modality phase and --tomography-method fbp, and only with them")
     row = RECONSTRUCTIONS[a.tomography_method]
     if row.weight != (a.tomography_weight is not None):
         ap.error("--tomography-weight W >= 0 goes with --tomography-method tv, and only with it")
@@ -472,8 +514,18 @@ def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=No
     (with `filter`), or 'sirt' / 'cgls' with `iterations` steps from zero (required for them, refused for 'fbp'; `filter`
     is not used), or 'tv' with `iterations` steps and `weight` (both required, weight refused for the others); nonneg: the
     clamp of sirt and tv.  weight is RELATIVE: tv runs with weight * max|sinogram| per bin, so that scaling a sinogram
-    scales its volume and one weight serves -ln T and radians alike."""
+    scales its volume and one weight serves -ln T and radians alike.
+    A differential scan (scanned['differential'], scan(..., differential=True); a dict without the key is an integral one)
+    holds d(phi)/d(column) and goes through the Hilbert filter: filter 'ramp' then means 'hilbert' and 'hann' means
+    'hilbert-hann', 'none' is refused, and so is every method but 'fbp' (ValueError): sirt, cgls and tv solve B^T x = b for
+    integral data, and an iterative solver on the differentiated operator is out of scope here.  The conversion by
+    delta_volume is the same."""
     check_reconstruction(method, iterations, nonneg, weight)
+    if scanned.get('differential', False):
+        check_differential(True, scanned['modality'], method)
+        if filter not in DIFFERENTIAL_FILTER_OF:
+            raise ValueError("a differential sinogram takes filter %s, got %r" % (" or ".join(DIFFERENTIAL_FILTER_OF), filter))
+        filter = DIFFERENTIAL_FILTER_OF[filter]
     row = RECONSTRUCTIONS[method]
     options = {'iterations': iterations} if row.iterations else {'filter': filter}
     if row.nonneg:

@@ -21,7 +21,8 @@ reads 4 n x m float32 images and writes the extended grid, the filter reads and 
 
 --fbp times psx_fbp_f32 alone at (A, n, m) = (720, 64, 1024): the filter (pack, two rocFFT passes per row pair, the multiply)
 against the bytes it moves, and k_fbp_backproject against its two prices per voxel, angle and detector row: two 4-byte LDS
-reads (as half of two ds_read_b128 that serve four rows) at 256 B per clock and CU, and two float32 FMAs.
+reads (as half of two ds_read_b128 that serve four rows) at 256 B per clock and CU, and two float32 FMAs.  The multiply of
+the Hilbert filter (k_fbp_filter_hilbert, a plan with filter 'hilbert' on the same input) is listed beside the ramp's.
 
 --project times the matched pair at (720, 64, 1024) and (90, 24, 64): k_fbp_project (psx_fbp_project_f32) and
 psx_fbp_adjoint_f32 (k_fbp_pack + k_fbp_backproject at scale 1).  The projector's prices per voxel, angle and detector row: the
@@ -205,9 +206,23 @@ def fbp_case(A, n, m, reps):
     print("A=%d n=%d m=%d  plan %.0f MiB  filter per call %.1f us = kernels %.1f us + rocFFT %.1f us (%s, %d launches each)"
           % (A, n, m, plan.bytes / 2 ** 20, per["k_fbp_pack"] + per["k_fbp_filter"] + fft, per["k_fbp_pack"] + per["k_fbp_filter"],
              fft, ", ".join("%s %.1f" % (k, v) for k, v in per.items() if k.startswith("rocfft")), pairs))
+    # the Hilbert filter's step (a differential sinogram) on the same input: the same loads and stores as the ramp's
+    hilbert = ops.FbpPlan(plan.theta, m, filter="hilbert")
+    for _ in range(2):
+        ops.fbp(sino, hilbert, out=vol)
+    torch.cuda.synchronize()
+    lib().psx_profile_enable(1)
+    for _ in range(reps):
+        ops.fbp(sino, hilbert, out=vol)
+    torch.cuda.synchronize()
+    per["k_fbp_filter_hilbert"] = summary()["k_fbp_filter_hilbert"][1] / reps * 1e3
+    lib().psx_profile_enable(0)
+    hilbert.close()
+    price["k_fbp_filter_hilbert"] = price["k_fbp_filter"]
     for k, b in price.items():
         print("    %s %.1f us  price %.1f MB (%.1f us at 8 TB/s) = %.2f of 8 TB/s" % (k, per[k], b / 1e6, b / PEAK * 1e6,
                                                                                         b / (per[k] * 1e-6) / PEAK))
+    print("    k_fbp_filter_hilbert / k_fbp_filter = %.3f" % (per["k_fbp_filter_hilbert"] / per["k_fbp_filter"]))
     t = per["k_fbp_backproject"] * 1e-6
     work = float(m) * m * A * n
     lds, fma = 8.0 * work, 2.0 * work

@@ -23,7 +23,9 @@
 //     stage C: radix 16 on 16 contiguous points, x FFT_M(h), inverse radix 16  ("middle stage", slab by slab)
 // Between the barriers after forward stage A and before inverse stage A a wave only touches the 2048 points it owns (8 blocks of
 // 256 = 128 slabs of 16), as in fresnel_lds.hip.  Position p = 256 k1 + 16 k2 + k3 of a transformed line holds frequency
-// k1 + R1 k2 + 16 R1 k3; the kernel-spectrum table is stored in that order (p2::perm_spectrum).
+// k1 + R1 k2 + 16 R1 k3.  The kernel-spectrum table holds the M values a line meets there, in the order the lanes of the middle
+// stage load them -- [group of 64 slabs][point pair q of the slab][lane][16 bytes], spectrum::point_index of fresnel_p2_dev.hpp
+// (p2::perm_spectrum) -- so that each of a wave's eight loads reads one aligned 1 KiB block.
 #include "fresnel_p2.hpp"
 
 #include <atomic>
@@ -402,7 +404,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
     const int n3 = ln & 15, blk = ((ln >> 4) & 1) * 2 + (ln >> 5);
     // middle stage: within each half-wave the first 16 lanes take the even slabs and the last 16 the odd ones (one pad slot per
     // TWO slabs: 16 different bank pairs per ds_write_b64 group)
-    const int slabw = (ln & 32) + ((ln & 31) < 16 ? 2 * (ln & 31) : 2 * ((ln & 31) - 16) + 1);
+    const int slabw = spectrum::slab_of_lane(ln);
     const v2f *rowB = tB + n3 * LDB;
     // What a wave owns between the barriers after forward stage A and before inverse stage A: the same 1024 points (4 blocks of 256
     // = 64 slabs) of TWO LDS lines -- lines 2p and 2p + 1 of the round (DUAL: an image line's buffer and the buffer of its second
@@ -419,6 +421,11 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
     // does this thread take part in the forward stages?  DUAL transforms the first LH lines only: with R1 = 32 that is one
     // line = the butterflies of the first four waves; with smaller radices every thread has its share
     const bool fwdA_on = !(DUAL && R1 == 32) || tid < TE / 2;
+    // the wave's group of 64 slabs within a line (S0 % SPL = 64 sg + slabw) and the lane's first 16 bytes of that group's part of a
+    // kernel-spectrum table: load q of the slab's eight lies 64 q float4 further (spectrum::unit_of_lane)
+    const int sg = __builtin_amdgcn_readfirstlane(w % RPL);
+    const int hlane = spectrum::unit_of_lane<8>(sg, 0, ln);
+    static_assert(spectrum::unit_of_lane<8>(0, 1, 0) == 64, "stride of a lane's loads");
     constexpr int NBAF = DUAL ? (R1 == 32 ? 1 : NBA / 2) : NBA;      // forward stage-A butterflies per thread
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 32 + 0] = wall_clock64();
     lds_barrier();                                       // (0) first group is in LDS
@@ -458,11 +465,12 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
         }
         // The kernel spectrum (the engine's only global loads) travels well ahead of its use: the slab's 128 bytes are requested
         // here, before barrier (1) and before the loaders' fetch (DUAL: the second distance's in forward stage B, behind its reads).
+        // Each load of the wave is one 1 KiB block of the table, the lanes in order.
         float4 hh[8], hh1[DUAL ? 8 : 1];
         {
-            const float4 *h4 = reinterpret_cast<const float4 *>(a.H[DUAL ? 2 * d : d] + 16 * (S0 % SPL));
+            const float4 *h4 = reinterpret_cast<const float4 *>(a.H[DUAL ? 2 * d : d]) + hlane;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) hh[q] = h4[q];
+            for (int q = 0; q < 8; ++q) hh[q] = h4[64 * q];
         }
         PSX_STAMP(3);
         lds_barrier();                               // (1)
@@ -479,10 +487,10 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) v0[q] = lds_read(p0 + offB(q));
             if constexpr (DUAL) {
-                const float4 *h4b = reinterpret_cast<const float4 *>(a.H[2 * d + 1] + 16 * (S0 % SPL));
+                const float4 *h4b = reinterpret_cast<const float4 *>(a.H[2 * d + 1]) + hlane;
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) hh1[q] = h4b[q];
+                for (int q = 0; q < 8; ++q) hh1[q] = h4b[64 * q];
                 __builtin_amdgcn_sched_barrier(0);
             } else {
 #pragma unroll
@@ -654,7 +662,7 @@ __global__ void k_p2_perm(const double2 *__restrict__ Hh, const double2 *__restr
     if (p < M) {
         const int k1 = p >> 8, k2 = (p >> 4) & 15, k3 = p & 15;
         const double2 v = Hh[k1 + R1 * k2 + 16 * R1 * k3];
-        out[p] = make_float2((float)(v.x / M), (float)(v.y / M));
+        out[spectrum::point_index(p)] = make_float2((float)(v.x / M), (float)(v.y / M));
     } else if (p < M + LXM) {
         const int t = p - M;
         const double2 v = t < P ? hP[t] : make_double2(0.0, 0.0);

@@ -20,8 +20,9 @@ size_t twA_elems(int R1);
 size_t twB_elems();
 int build_tables(float2 *twA, float2 *twB, int R1, hipStream_t st);
 
-// kernel-spectrum table of one distance: out[p] = Hh[k(p)] / M for the M positions of the in-place transform (k(p) = k1 + R1 k2 +
-// 16 R1 k3 for p = 256 k1 + 16 k2 + k3), followed by the first LXMAX taps h[t] = hP[t] / P (float32)
+// kernel-spectrum table of one distance: Hh[k(p)] / M for the M positions of the in-place transform (k(p) = k1 + R1 k2 +
+// 16 R1 k3 for p = 256 k1 + 16 k2 + k3), position p at element spectrum::point_index(p) (fresnel_p2_dev.hpp: the order in which
+// the lanes of the middle stage load them), followed by the first LXMAX taps h[t] = hP[t] / P (float32)
 size_t spectrum_elems(int R1);
 int perm_spectrum(const double2 *Hh, const double2 *hP, float2 *out, int R1, int P, hipStream_t st);
 

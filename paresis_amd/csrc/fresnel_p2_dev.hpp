@@ -11,6 +11,62 @@ using namespace psx::lines;
 
 constexpr int BSTR = 256 + 8;  // padded stride of a block of 256 points (one pad slot per 32)
 
+// ---- Memory order of the kernel-spectrum tables.  In the middle stage lane ln of a wave holds slab slab_of_lane(ln) of the wave's
+// 64 slabs: within each half-wave the first 16 lanes take the even slabs and the last 16 the odd ones (one pad slot per TWO slabs:
+// 16 different bank pairs per ds_write_b64 group).  The table is stored so that ONE load instruction of a wave reads ONE aligned
+// 1 KiB block, lane ln at byte 16 ln (8 cache lines, where a slab-major table cost 64):
+//     [group of 64 slabs][unit q of the slab][lane][16 bytes],
+// a unit being the 16 bytes a lane takes with one load: UPS = 8 units of two points per slab in fresnel_p2.hip, 16 units of one
+// (bin, bin + M) pair in fresnel_p2x.hip.  The table builders (k_p2_perm, k_p2x_perm) and the readers use the functions below and
+// nothing else.
+namespace spectrum {
+__host__ __device__ constexpr int slab_of_lane(int ln) { return (ln & 32) + ((ln & 31) < 16 ? 2 * (ln & 31) : 2 * ((ln & 31) - 16) + 1); }
+__host__ __device__ constexpr int lane_of_slab(int s) { return (s & 32) + ((s & 1) ? 16 : 0) + ((s & 31) >> 1); }
+// 16-byte unit index of unit q of lane ln's slab in group g (the reader's form: g and q are uniform, ln is the lane itself)
+template <int UPS>
+__host__ __device__ constexpr int unit_of_lane(int g, int q, int ln) { return (g * UPS + q) * 64 + ln; }
+// ... and of unit q of slab s of the transformed line (the builder's form)
+template <int UPS>
+__host__ __device__ constexpr int unit_of_slab(int s, int q) { return unit_of_lane<UPS>(s >> 6, q, lane_of_slab(s & 63)); }
+// fresnel_p2.hip: float2 index of position p = 16 slab + k3 of the transformed line (points 2q, 2q + 1 of a slab share a unit)
+__host__ __device__ constexpr int point_index(int p) { return 2 * unit_of_slab<8>(p >> 4, (p & 15) >> 1) + (p & 1); }
+// fresnel_p2x.hip: float4 index of the pair at position p of a round's LDS lines
+__host__ __device__ constexpr int pair_index(int p) { return unit_of_slab<16>(p >> 4, p & 15); }
+
+constexpr bool lanes_invert() {
+    for (int ln = 0; ln < 64; ++ln)
+        if (lane_of_slab(slab_of_lane(ln)) != ln || slab_of_lane(lane_of_slab(ln)) != ln) return false;
+    return true;
+}
+// is f a bijection of [0, m)?  (m <= 8192)
+template <typename F>
+constexpr bool is_bijection(F f, int m) {
+    bool seen[8192] = {};
+    for (int p = 0; p < m; ++p) {
+        const int i = f(p);
+        if (i < 0 || i >= m || seen[i]) return false;
+        seen[i] = true;
+    }
+    return true;
+}
+// what the reader finds: unit q of lane ln of group g holds positions 16 slab + 2q, + 1 of slab 64 g + slab_of_lane(ln)
+constexpr bool reader_meets_builder(int m) {
+    for (int g = 0; g < m / 1024; ++g)
+        for (int q = 0; q < 8; ++q)
+            for (int ln = 0; ln < 64; ++ln) {
+                const int p = 16 * (64 * g + slab_of_lane(ln)) + 2 * q;
+                if (point_index(p) != 2 * unit_of_lane<8>(g, q, ln) || point_index(p + 1) != 2 * unit_of_lane<8>(g, q, ln) + 1) return false;
+                if (q == 0 && (pair_index(p) != unit_of_lane<16>(g, 0, ln) || pair_index(p + 15) != unit_of_lane<16>(g, 15, ln))) return false;
+            }
+    return true;
+}
+static_assert(lanes_invert(), "slab_of_lane and lane_of_slab are inverse permutations of the 64 lanes");
+static_assert(is_bijection(point_index, 256 * 4) && is_bijection(point_index, 256 * 8) && is_bijection(point_index, 256 * 16) &&
+                  is_bijection(point_index, 256 * 32) && is_bijection(pair_index, 256 * 32),
+              "the table order is a bijection of the M positions for R1 = 4, 8, 16, 32");
+static_assert(reader_meets_builder(256 * 4) && reader_meets_builder(256 * 32), "a lane's loads find its own slab");
+}  // namespace spectrum
+
 // Stage A's twiddles w_M^{n q}, q < R, from the LB = log2(R) powers w^(n 2^b) of the thread's row: w^(n q) is the product of the
 // powers of q's set bits, at most four multiplications deep -- 26 products for R = 32 where two factor tables cost 31 and 62 LDS
 // reads (fresnel_lds.hip, twiddle_A); 5 reads here.  The lower half is applied as it is built, the upper half takes w^(16 n) first.

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2x(LineArgs a) {
     };
     auto slab_of = [&]() __attribute__((always_inline)) {
         const int t = ftid(), ln = t & 63;
-        return 64 * (t >> 6) + (ln & 32) + ((ln & 31) < 16 ? 2 * (ln & 31) : 2 * ((ln & 31) - 16) + 1);
+        return 64 * (t >> 6) + spectrum::slab_of_lane(ln);
     };
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 32 + 0] = wall_clock64();
     lds_barrier();                                       // (0)
@@ -297,12 +297,15 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2x(LineArgs a) {
 #pragma unroll
             for (int q = 0; q < R1; ++q) pA[q * BSTR] = v[q];
         }
-        // the first half of the slab's kernel-spectrum pairs travels ahead of its use
+        // the first half of the slab's kernel-spectrum pairs travels ahead of its use: each load of the wave is one 1 KiB block of
+        // the table, the lanes in order (spectrum::unit_of_lane; wave w owns the slabs of group w)
         const int S0 = slab_of();
-        const float4 *h4 = reinterpret_cast<const float4 *>(a.H[d] + (size_t)ps * 2 * M) + 16 * S0;
+        const int hlane = spectrum::unit_of_lane<16>(__builtin_amdgcn_readfirstlane(ftid() >> 6), 0, ftid() & 63);
+        static_assert(spectrum::unit_of_lane<16>(0, 1, 0) == 64, "stride of a lane's loads");
+        const float4 *h4 = reinterpret_cast<const float4 *>(a.H[d] + (size_t)ps * 2 * M) + hlane;
         float4 hh[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) hh[q] = h4[q];
+        for (int q = 0; q < 8; ++q) hh[q] = h4[64 * q];
         const float2 wsf = a.w2[S0];                     // w_Q^k0 of this lane's slab
         const v2f wsl = (v2f){wsf.x, wsf.y};
         PSX_STAMP(3);
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2x(LineArgs a) {
                 if constexpr (c == 0) {
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) hh[q] = h4[8 + q];
+                    for (int q = 0; q < 8; ++q) hh[q] = h4[64 * (8 + q)];
                     __builtin_amdgcn_sched_barrier(0);
                 }
             });
@@ -495,7 +498,8 @@ __global__ void k_p2x_pad(const double2 *__restrict__ hP, double2 *__restrict__ 
     buf[t] = v;
 }
 
-// out: [2 rounds][M] float4 = (G[k(p)], G[k(p) + M]) / (2 Q) for the M positions of an LDS line, then the first LXMAX taps (float2)
+// out: [2 rounds][M] float4 = (G[k(p)], G[k(p) + M]) / (2 Q) for the M positions p of an LDS line, each round in the order the
+// lanes of the middle stage load them (spectrum::pair_index), then the first LXMAX taps (float2)
 __global__ void k_p2x_perm(const double2 *__restrict__ Hh, const double2 *__restrict__ hP, float2 *__restrict__ out, int P) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < 2 * M) {
@@ -503,7 +507,7 @@ __global__ void k_p2x_perm(const double2 *__restrict__ Hh, const double2 *__rest
         const int k = (p >> 8) + R1 * ((p >> 4) & 15) + 16 * R1 * (p & 15);
         const double2 g0 = Hh[(size_t)sg * Q + k], g1 = Hh[(size_t)sg * Q + k + M];
         const double sc = 1.0 / (2.0 * Q);
-        reinterpret_cast<float4 *>(out)[t] = make_float4((float)(g0.x * sc), (float)(g0.y * sc), (float)(g1.x * sc), (float)(g1.y * sc));
+        reinterpret_cast<float4 *>(out)[sg * M + spectrum::pair_index(p)] = make_float4((float)(g0.x * sc), (float)(g0.y * sc), (float)(g1.x * sc), (float)(g1.y * sc));
     } else if (t < 2 * M + LXM) {
         const int d = t - 2 * M;
         const double2 v = d < P ? hP[d] : make_double2(0.0, 0.0);

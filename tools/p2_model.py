@@ -52,7 +52,9 @@ def dif3(v, R1, inverse=False):
 
 
 def perm_spectrum(h, R1):
-    """H table of the middle stage: position p holds FFT_M(h zero-padded)[k(p)] / M."""
+    """H table of the middle stage: position p holds FFT_M(h zero-padded)[k(p)] / M.  (Indexed by the position of the
+    transformed line; in memory the kernel keeps these values in the order its lanes load them, spectrum::point_index of
+    csrc/fresnel_p2_dev.hpp.)"""
     M = 256 * R1
     Hf = np.fft.fft(np.concatenate([h, np.zeros(M - len(h))])) / M
     p = np.arange(M)

@@ -257,6 +257,16 @@ inline bool first_on_device(std::atomic<unsigned long long> &mask) {
     return !(mask.fetch_or(bit) & bit);
 }
 
+// The dynamic-LDS limit of a kernel that launches with more than the default allows, set once per device: one mask per
+// kernel instantiation.  if (int rc = allow_dynamic_lds<k_name<...>>(bytes)) return rc;
+template <auto Kernel>
+int allow_dynamic_lds(int bytes) {
+    static std::atomic<unsigned long long> mask{0};
+    if (first_on_device(mask))
+        PSX_HIP(hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return 0;
+}
+
 // compute units of the current device (queried per call: ~0.1 us, no cache to go stale when the device changes)
 inline int current_cu_count() {
     int dev = 0, n = 0;

@@ -438,9 +438,7 @@ int launch_banded(const float *I2DF, const float *DF, const float2 *prep, const 
         return status ? psx_status_scan_f32(out, n, status, (void *)st) : 0;
     }
     const size_t lds = sizeof(float4) * (size_t)band * (size_t)W;
-    static std::atomic<unsigned long long> attr_mask{0};
-    if (first_on_device(attr_mask))
-        PSX_HIP(hipFuncSetAttribute((const void *)k_df_gather_banded, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    if (int rc = allow_dynamic_lds<k_df_gather_banded>(64 * 1024)) return rc;
     const int tiles_x = (int)cdiv(Nx, DT), tiles_y = (int)cdiv(Ny, DT);
     PSX_TIMED("k_df_gather", st, k_df_gather_banded<<<tiles_x * tiles_y, 256, lds, st>>>(I2DF, DF, prep, I2, out, Nx, Ny, R, band,
                                                                                          tiles_y, status, accumulate));

@@ -1757,10 +1757,7 @@ static int launch_lines(const LineArgs &la, hipStream_t st, const char *name) {
     }
     using GE = LineGeom<R3, false>;
     constexpr int LPG = DUAL ? GE::LINES / 2 : GE::LINES;        // image lines per round
-    static std::atomic<unsigned long long> attr_mask{0};
-    if (first_on_device(attr_mask))
-        PSX_HIP(hipFuncSetAttribute((const void *)k_fresnel_lines<R3, CONTIG, DUAL, QUEUE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)GE::lds_bytes));
+    if (int rc = allow_dynamic_lds<k_fresnel_lines<R3, CONTIG, DUAL, QUEUE>>((int)GE::lds_bytes)) return rc;
     const int nwork = ((la.nlines + LPG - 1) / LPG) * (la.dist_inner ? 1 : la.n_dist);
     // the queue buffer holds a counter per workgroup of at most 256 (QUEUE_WORDS) and a thief looks at the queues of its
     // XCD with one lane each, 32 at most: a device with more than 256 CUs runs the queued passes on 256 workgroups
@@ -1786,10 +1783,7 @@ static int launch_lines_r(bool contig, bool dual, const LineArgs &la, hipStream_
 template <bool CONTIG, bool DIF>
 static int launch_part(const LineArgs &la, hipStream_t st, const char *name) {
     using GE = LineGeom<16, true>;
-    static std::atomic<unsigned long long> attr_mask{0};
-    if (first_on_device(attr_mask))
-        PSX_HIP(hipFuncSetAttribute((const void *)k_fresnel_part<CONTIG, DIF>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)GE::lds_bytes));
+    if (int rc = allow_dynamic_lds<k_fresnel_part<CONTIG, DIF>>((int)GE::lds_bytes)) return rc;
     const int nwork = la.nlines * la.NB * (la.dist_inner ? 1 : la.n_dist);      // one image line per round
     const int nslot = line_grid_slots(nwork, 0);
     if constexpr (DIF) {

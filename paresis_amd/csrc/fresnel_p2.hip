@@ -683,10 +683,7 @@ int launch_t(const LineArgs &la, hipStream_t st, const char *name) {
         if (la.queue) return launch_t<R1, CONTIG, DUAL, true>(la, st, name);
     }
     using GE = G2<R1, DUAL>;
-    static std::atomic<unsigned long long> attr_mask{0};
-    if (first_on_device(attr_mask))
-        PSX_HIP(hipFuncSetAttribute((const void *)k_fresnel_p2<R1, CONTIG, DUAL, QUEUE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)GE::lds_bytes(GE::max_taps)));
+    if (int rc = allow_dynamic_lds<k_fresnel_p2<R1, CONTIG, DUAL, QUEUE>>((int)GE::lds_bytes(GE::max_taps))) return rc;
     if (la.n_dist < 1 || la.n_dist > MAX_LINE || (DUAL && !la.dist_inner))
         return fail(PSX_E_STATE, "LDS engine (power-of-two lines): %d distances, dist_inner %d", la.n_dist, la.dist_inner);
     const int ntap = DUAL ? 2 * ((la.n_dist + 1) / 2) : la.n_dist;

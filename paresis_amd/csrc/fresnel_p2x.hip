@@ -529,9 +529,7 @@ __global__ void k_p2x_twiddles(float2 *w2, float2 *w4) {
 
 template <bool CONTIG>
 int launch_x(const LineArgs &la, hipStream_t st, const char *name) {
-    static std::atomic<unsigned long long> attr_mask{0};
-    if (first_on_device(attr_mask))
-        PSX_HIP(hipFuncSetAttribute((const void *)k_fresnel_p2x<CONTIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MAX_TAPS)));
+    if (int rc = allow_dynamic_lds<k_fresnel_p2x<CONTIG>>((int)lds_bytes(MAX_TAPS))) return rc;
     if (la.n_dist < 1 || la.n_dist > MAX_TAPS || (!CONTIG && (la.dist_inner || !la.in_blocked)) || (CONTIG && la.in_si != 1))
         return fail(PSX_E_STATE, "LDS engine (power-of-two lines, two rounds): %d distances, dist_inner %d", la.n_dist, la.dist_inner);
     const int nwork = la.nlines * (la.dist_inner ? 1 : la.n_dist);

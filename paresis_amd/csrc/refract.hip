@@ -928,88 +928,103 @@ struct DetScratch {
     }
 };
 
-// far-ray counters and lists of a call: [ndist][ntiles] counts, then [ndist][ntiles][TH*TW] records
-template <class G>
-size_t lists_bytes(int Nx, int Ny, int ndist) {
-    const size_t nt = (size_t)cdiv(Nx, G::TH) * (size_t)cdiv(Ny, G::TW) * (size_t)ndist;
-    return 16 * ((sizeof(unsigned) * nt + 15) / 16) + sizeof(FarRay) * nt * G::TH * G::TW;
-}
-// + (order-independent replay) behind the lists: the call's maximum word (16 bytes), a fold-table count per list,
-// [ndist][Nx*Ny] scratch words
 inline size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
-template <class G>
-size_t det_bytes(int Nx, int Ny, int ndist) {
-    const size_t nt = (size_t)cdiv(Nx, G::TH) * (size_t)cdiv(Ny, G::TW);
-    return 16 + pad16(sizeof(unsigned) * nt * ndist) + sizeof(long long) * (size_t)Nx * (size_t)Ny * (size_t)ndist;
-}
-template <class G>
-void det_pointers(RefractArgs &a, char *gmax, char *rest, int ndist) {      // rest: det_bytes() - 16 bytes
-    const size_t nt = (size_t)a.tiles_x * a.tiles_y;
-    a.det_gmax = (unsigned *)gmax;
-    a.det_fold_count = (unsigned *)rest;
-    a.det_acc = (long long *)(rest + pad16(sizeof(unsigned) * nt * ndist));
-}
-template <class G>
-size_t workspace_for(int Nx, int Ny, int ndist) {
-    return lists_bytes<G>(Nx, Ny, ndist) + (g_deterministic ? det_bytes<G>(Nx, Ny, ndist) : 0);
-}
 
-// one chunk of a batch: the lists of REFRACT_TAB refractions, then (order-independent replay) REFRACT_TAB one-distance regions
+// The workspace of one launch sequence (near kernel + replay): the ONE statement of its layout, for the size entry points
+// and the launchers alike.  A single or multi call is one slot of a.ndist distances, a chunk of a batch REFRACT_TAB slots of
+// one distance each:
+//   [far counts    slots * ndist * ntiles unsigned, padded to 16 bytes]
+//   [far lists     slots * ndist * ntiles * TH*TW records (a tile can never overflow its list)]
+//   order-independent replay (psx_set_deterministic) only:
+//   [maximum words 16 bytes per slot, side by side: one memset node clears them all]
+//   per slot: [fold-table counts ndist * ntiles unsigned, padded to 16 bytes][scratch words ndist * Nx*Ny long long]
+// Every region begins where the one before it ends, and bytes() is the end of the last.
 template <class G>
-size_t batch_chunk_bytes(int Nx, int Ny) {
-    return lists_bytes<G>(Nx, Ny, REFRACT_TAB) + (g_deterministic ? (size_t)REFRACT_TAB * det_bytes<G>(Nx, Ny, 1) : 0);
-}
-static size_t batch_chunk_max(int Nx, int Ny) {
-    return PSX_GEO_MAX(batch_chunk_bytes<G_>(Nx, Ny));
+struct RefractWorkspace {
+    static constexpr size_t CAP = (size_t)G::TH * G::TW;      // records per list
+    int tiles_x, tiles_y, slots;
+    bool det;
+    size_t slot_lists;                                        // lists of one slot: ndist * ntiles
+    size_t far_list, gmax, det_slot0, det_slot_bytes, det_acc_in_slot, end;      // byte offsets (the far counts are at 0)
+
+    RefractWorkspace(int Nx, int Ny, int slots_, int ndist, bool det_)
+        : tiles_x((int)cdiv(Nx, G::TH)), tiles_y((int)cdiv(Ny, G::TW)), slots(slots_), det(det_) {
+        slot_lists = (size_t)tiles_x * tiles_y * ndist;
+        size_t at = 0;
+        auto region = [&at](size_t bytes) { const size_t begin = at; at += bytes; return begin; };
+        region(pad16(sizeof(unsigned) * slots * slot_lists));
+        far_list = region(sizeof(FarRay) * slots * slot_lists * CAP);
+        gmax = det_slot0 = det_slot_bytes = det_acc_in_slot = 0;
+        if (det) {
+            gmax = region(16 * (size_t)slots);
+            det_acc_in_slot = pad16(sizeof(unsigned) * slot_lists);
+            det_slot_bytes = det_acc_in_slot + sizeof(long long) * (size_t)Nx * Ny * ndist;
+            det_slot0 = region(slots * det_slot_bytes);
+        }
+        end = at;
+    }
+    size_t bytes() const { return end; }
+
+    // an argument block's view of slot `slot` of the workspace at `ws`, with the tiling the layout is counted in
+    void bind(RefractArgs &a, void *ws, int slot) const {
+        char *const w = (char *)ws, *const s = w + det_slot0 + slot * det_slot_bytes;
+        a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tile_cap = (int)CAP;
+        a.far_count = (unsigned *)w + slot * slot_lists;
+        a.far_list = (FarRay *)(w + far_list) + slot * slot_lists * CAP;
+        a.det_gmax = det ? (unsigned *)(w + gmax + 16 * (size_t)slot) : nullptr;
+        a.det_fold_count = det ? (unsigned *)s : nullptr;
+        a.det_acc = det ? (long long *)(s + det_acc_in_slot) : nullptr;
+    }
+    // The only words of the workspace with an initial state are the maximum words, measured anew by every launch sequence
+    // unless the caller's scale (scale_bits != 0) takes their place.
+    int clear_max(void *ws, unsigned scale_bits, hipStream_t st) const {
+        if (det && !scale_bits) PSX_HIP(hipMemsetAsync((char *)ws + gmax, 0, 16 * (size_t)slots, st));
+        return 0;
+    }
+};
+
+template <class G, int MODE>
+void launch_far(dim3 grid, hipStream_t st, const RefractArgs &a) { k_refract_far<G, MODE><<<grid, FAR_THREADS, 0, st>>>(a); }
+template <class G, int MODE>
+void launch_far(dim3 grid, hipStream_t st, const RefractTab &t) { k_refract_far_batch<G, MODE><<<grid, FAR_THREADS, 0, st>>>(t); }
+
+// What follows the launch of a near kernel, for a call's argument block or a chunk's table of them: the check of that launch,
+// then the replay of the `lists` far-ray lists of each of the n refractions.
+template <class G, class Args>
+int launch_replay(const Args &args, const long long *det_acc, int lists, int n, hipStream_t st) {
+    if (int rc = launch_check("k_refract_near")) return rc;
+    const dim3 grid((unsigned)cdiv(lists, FAR_LISTS), (unsigned)n);
+    if (det_acc) {      // order-independent replay: two passes over the lists, scratch from the workspace
+        PSX_TIMED("k_refract_far_add", st, launch_far<G, FAR_ADD>(grid, st, args));
+        PSX_TIMED("k_refract_far_fold", st, launch_far<G, FAR_FOLD>(grid, st, args));
+    } else {
+        PSX_TIMED("k_refract_far", st, launch_far<G, FAR_FLOAT>(grid, st, args));
+    }
+    return launch_check("k_refract_far");
 }
 
 template <class G>
 int launch_refract(RefractArgs &a, const float *I_in, const double *phi_in, int nmat, void *workspace, hipStream_t st) {
-    a.tiles_x = (int)cdiv(a.Nx, G::TH);
-    a.tiles_y = (int)cdiv(a.Ny, G::TW);
-    a.tile_cap = G::TH * G::TW;
-    a.far_count = (unsigned *)workspace;
-    a.far_list = (FarRay *)((char *)workspace + 16 * ((sizeof(unsigned) * (size_t)a.tiles_x * a.tiles_y * a.ndist + 15) / 16));
-    a.det_gmax = nullptr; a.det_fold_count = nullptr; a.det_acc = nullptr; a.det_scale_bits = 0u;
-    if (g_deterministic) {
-        char *const det = (char *)workspace + lists_bytes<G>(a.Nx, a.Ny, a.ndist);
-        det_pointers<G>(a, det, det + 16, a.ndist);
-        a.det_scale_bits = det_scale_bits();
-        if (!a.det_scale_bits)
-            PSX_HIP(hipMemsetAsync(a.det_gmax, 0, 16, st));      // the only word of the mode with an initial state: set per call
-    }
+    const RefractWorkspace<G> ws(a.Nx, a.Ny, 1, a.ndist, g_deterministic != 0);
+    ws.bind(a, workspace, 0);
+    a.det_scale_bits = ws.det ? det_scale_bits() : 0u;
+    if (int rc = ws.clear_max(workspace, a.det_scale_bits, st)) return rc;
+    const int nt = a.tiles_x * a.tiles_y;
     int rc_launch = 0;
     auto launch = [&](auto nm, auto hi, auto hp) -> int {
         constexpr int NM = decltype(nm)::value;
         constexpr bool HI = decltype(hi)::value, HP = decltype(hp)::value;
         if constexpr (!HP && NM > 0) {
             if (a.mask) {
-                static std::atomic<unsigned long long> attr_mask_s{0};
-                if (first_on_device(attr_mask_s))
-                    PSX_HIP(hipFuncSetAttribute((const void *)k_refract_near_split<G, NM, HI>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
-                PSX_TIMED("k_refract_near", st,
-                          k_refract_near_split<G, NM, HI><<<a.tiles_x * a.tiles_y, G::NT, G::LDS, st>>>(a));
+                if (int rc = allow_dynamic_lds<k_refract_near_split<G, NM, HI>>((int)G::LDS)) return rc;
+                PSX_TIMED("k_refract_near", st, k_refract_near_split<G, NM, HI><<<nt, G::NT, G::LDS, st>>>(a));
             }
         }
         if (!a.mask) {
-            static std::atomic<unsigned long long> attr_mask{0};
-            if (first_on_device(attr_mask))
-                PSX_HIP(hipFuncSetAttribute((const void *)k_refract_near<G, NM, HI, HP>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
-            PSX_TIMED("k_refract_near", st,
-                      k_refract_near<G, NM, HI, HP><<<a.tiles_x * a.tiles_y, G::NT, G::LDS, st>>>(a));
+            if (int rc = allow_dynamic_lds<k_refract_near<G, NM, HI, HP>>((int)G::LDS)) return rc;
+            PSX_TIMED("k_refract_near", st, k_refract_near<G, NM, HI, HP><<<nt, G::NT, G::LDS, st>>>(a));
         }
-        if (int rc = launch_check("k_refract_near")) return rc;
-        const int nlists = a.tiles_x * a.tiles_y * a.ndist;
-        const int fgrid = (nlists + FAR_LISTS - 1) / FAR_LISTS;
-        if (a.det_acc) {      // order-independent replay: two passes over the lists, scratch from the workspace
-            PSX_TIMED("k_refract_far_add", st, k_refract_far<G, FAR_ADD><<<fgrid, FAR_THREADS, 0, st>>>(a));
-            PSX_TIMED("k_refract_far_fold", st, k_refract_far<G, FAR_FOLD><<<fgrid, FAR_THREADS, 0, st>>>(a));
-            return 0;
-        }
-        PSX_TIMED("k_refract_far", st, k_refract_far<G><<<fgrid, FAR_THREADS, 0, st>>>(a));
-        return 0;
+        return launch_replay<G>(a, a.det_acc, nt * a.ndist, 1, st);
     };
     PSX_DISPATCH_NMAT(nmat, {
         using N_ = std::integral_constant<int, NM>;
@@ -1018,48 +1033,28 @@ int launch_refract(RefractArgs &a, const float *I_in, const double *phi_in, int 
         else if (phi_in) rc_launch = launch(N_{}, std::false_type{}, std::true_type{});
         else rc_launch = launch(N_{}, std::false_type{}, std::false_type{});
     });
-    if (rc_launch) return rc_launch;
-    return launch_check("k_refract_far");
+    return rc_launch;
 }
 
+// one chunk of a batch: n <= REFRACT_TAB refractions, every one a slot of the chunk's workspace (the table's padding
+// blocks beyond n look at slot 0, like the rest of their fields)
 template <class G>
 int launch_refract_batch(RefractTab &t, int n, bool has_I, int nmat, void *workspace, hipStream_t st) {
-    const int tiles_x = (int)cdiv(t.e[0].Nx, G::TH), tiles_y = (int)cdiv(t.e[0].Ny, G::TW);
-    const size_t nt = (size_t)tiles_x * tiles_y;
+    const RefractWorkspace<G> ws(t.e[0].Nx, t.e[0].Ny, REFRACT_TAB, 1, g_deterministic != 0);
+    const unsigned scale_bits = ws.det ? det_scale_bits() : 0u;
     for (int e = 0; e < REFRACT_TAB; ++e) {
-        RefractArgs &a = t.e[e];
-        a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tile_cap = G::TH * G::TW;
-        const int k = e < n ? e : 0;
-        a.far_count = (unsigned *)workspace + (size_t)k * nt;
-        a.far_list = (FarRay *)((char *)workspace + 16 * ((sizeof(unsigned) * nt * REFRACT_TAB + 15) / 16)) + (size_t)k * nt * a.tile_cap;
-        // order-independent replay: every refraction of the chunk its own exponents, marks and scratch words behind the chunk's lists
-        a.det_gmax = nullptr; a.det_fold_count = nullptr; a.det_acc = nullptr; a.det_scale_bits = g_deterministic ? det_scale_bits() : 0u;
-        if (g_deterministic) {    // the chunk's maximum words side by side (one memset node), then each refraction's counts and words
-            char *const det = (char *)workspace + lists_bytes<G>(a.Nx, a.Ny, REFRACT_TAB);
-            det_pointers<G>(a, det + 16 * k, det + 16 * REFRACT_TAB + (size_t)k * (det_bytes<G>(a.Nx, a.Ny, 1) - 16), 1);
-        }
+        ws.bind(t.e[e], workspace, e < n ? e : 0);
+        t.e[e].det_scale_bits = scale_bits;
     }
-    if (g_deterministic && !t.e[0].det_scale_bits)      // every refraction of the chunk its own maximum word (its own unit: an image of its own)
-        PSX_HIP(hipMemsetAsync(t.e[0].det_gmax, 0, 16 * REFRACT_TAB, st));
+    if (int rc = ws.clear_max(workspace, scale_bits, st)) return rc;
+    const int nt = ws.tiles_x * ws.tiles_y;
     int rc_launch = 0;
     auto launch = [&](auto nm, auto hi) -> int {
         constexpr int NM = decltype(nm)::value;
         constexpr bool HI = decltype(hi)::value;
-        static std::atomic<unsigned long long> attr_mask{0};
-        if (first_on_device(attr_mask))
-            PSX_HIP(hipFuncSetAttribute((const void *)k_refract_near_batch<G, NM, HI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)G::LDS));
+        if (int rc = allow_dynamic_lds<k_refract_near_batch<G, NM, HI>>((int)G::LDS)) return rc;
         PSX_TIMED("k_refract_near", st, k_refract_near_batch<G, NM, HI><<<dim3((unsigned)nt, (unsigned)n), G::NT, G::LDS, st>>>(t));
-        if (int rc = launch_check("k_refract_near")) return rc;
-        const int fgrid = ((int)nt + FAR_LISTS - 1) / FAR_LISTS;
-        const dim3 fg((unsigned)fgrid, (unsigned)n);
-        if (t.e[0].det_acc) {
-            PSX_TIMED("k_refract_far_add", st, k_refract_far_batch<G, FAR_ADD><<<fg, FAR_THREADS, 0, st>>>(t));
-            PSX_TIMED("k_refract_far_fold", st, k_refract_far_batch<G, FAR_FOLD><<<fg, FAR_THREADS, 0, st>>>(t));
-        } else {
-            PSX_TIMED("k_refract_far", st, k_refract_far_batch<G><<<fg, FAR_THREADS, 0, st>>>(t));
-        }
-        return launch_check("k_refract_far");
+        return launch_replay<G>(t, t.e[0].det_acc, nt, n, st);
     };
     PSX_DISPATCH_NMAT(nmat, {
         using N_ = std::integral_constant<int, NM>;
@@ -1069,13 +1064,40 @@ int launch_refract_batch(RefractTab &t, int n, bool has_I, int nmat, void *works
     return rc_launch;
 }
 
+// the checks every refraction entry point (`fn`, for the message) makes of its grid, its margin and the n output images of
+// its `what` (distances, refractions)
+int check_refract_call(const char *fn, const char *what, int Nx, int Ny, int margin, float *const *I_out, int n) {
+    PSX_REQUIRE(Nx >= 3 && Ny >= 3, "%s: grid %dx%d too small for the edge_order=2 gradient", fn, Nx, Ny);
+    PSX_REQUIRE((int64_t)Nx * Ny < (1ll << 31), "%s: grid %dx%d exceeds int32 pixel indices", fn, Nx, Ny);
+    PSX_REQUIRE(margin >= 8 && margin <= 4096, "%s: margin %d must be >= 8 (the widest gather halo)", fn, margin);
+    for (int e = 0; e < n; ++e) {
+        PSX_REQUIRE(I_out[e] != nullptr, "%s: null output image %d", fn, e);
+        for (int f = 0; f < e; ++f) PSX_REQUIRE(I_out[f] != I_out[e], "%s: %s %d and %d share an output image", fn, what, f, e);
+    }
+    return 0;
+}
+
+// the fields of an argument block that are the same for every refraction of a call, and nulls for the optional ones
+void fill_shared(RefractArgs &a, int Nx, int Ny, int margin, double clamp_x, double clamp_y, unsigned *status, float out_scale,
+                 int accumulate) {
+    a.Nx = Nx; a.Ny = Ny; a.margin = margin;
+    a.clamp_xf = (float)clamp_x; a.clamp_yf = (float)clamp_y; a.status = status; a.out_scale = out_scale; a.accumulate = accumulate;
+    a.mask = nullptr; a.phi_in = nullptr; a.Dx_out = nullptr; a.Dy_out = nullptr; a.I_mut = nullptr; a.stamps = nullptr;
+}
+
+// A caller sizes its workspace before it knows the halo of the call: the largest over the geometries.  Chunk c of a batch
+// begins at c * batch_chunk_max().
+size_t batch_chunk_max(int Nx, int Ny) {
+    return PSX_GEO_MAX(RefractWorkspace<G_>(Nx, Ny, REFRACT_TAB, 1, g_deterministic != 0).bytes());
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t psx_refract_multi_workspace_bytes(int Nx, int Ny, int ndist) {
     if (Nx <= 0 || Ny <= 0 || ndist <= 0) return 16;
-    return PSX_GEO_MAX(workspace_for<G_>(Nx, Ny, ndist));
+    return PSX_GEO_MAX(RefractWorkspace<G_>(Nx, Ny, 1, ndist, g_deterministic != 0).bytes());
 }
 
 size_t psx_refract_workspace_bytes(int Nx, int Ny) { return psx_refract_multi_workspace_bytes(Nx, Ny, 1); }
@@ -1094,9 +1116,7 @@ static int refract_multi_impl(const float *I_in, const float *mask, float I0, co
                               void *workspace, void *stream) {
     PSX_REQUIRE(I_out != nullptr && dscale != nullptr && workspace != nullptr, "psx_refract_multi_f32: null outputs, distances or workspace");
     PSX_REQUIRE(ndist >= 1 && ndist <= PSX_MAX_DIST, "psx_refract_multi_f32: %d distances, 1..%d supported per call", ndist, PSX_MAX_DIST);
-    PSX_REQUIRE(Nx >= 3 && Ny >= 3, "psx_refract_multi_f32: grid %dx%d too small for the edge_order=2 gradient", Nx, Ny);
-    PSX_REQUIRE((int64_t)Nx * Ny < (1ll << 31), "psx_refract_multi_f32: grid %dx%d exceeds int32 pixel indices", Nx, Ny);
-    PSX_REQUIRE(margin >= 8 && margin <= 4096, "psx_refract_multi_f32: margin %d must be >= 8 (the widest gather halo)", margin);
+    if (int rc = check_refract_call("psx_refract_multi_f32", "distances", Nx, Ny, margin, I_out, ndist)) return rc;
     PSX_REQUIRE((Dx_out == nullptr) == (Dy_out == nullptr), "psx_refract_multi_f32: Dx_out and Dy_out go together");
     PSX_REQUIRE(ndist == 1 || (Dx_out == nullptr && I_mut == nullptr),
                 "psx_refract_multi_f32: displacement maps / input mutation belong to ONE distance (got %d)", ndist);
@@ -1106,16 +1126,13 @@ static int refract_multi_impl(const float *I_in, const float *mask, float I0, co
     hipStream_t st = (hipStream_t)stream;
     for (int d = 0; d < PSX_MAX_DIST; ++d) {
         const int e = d < ndist ? d : 0;
-        PSX_REQUIRE(I_out[e] != nullptr, "psx_refract_multi_f32: null output image %d", e);
-        for (int f = 0; f < e; ++f)
-            PSX_REQUIRE(I_out[f] != I_out[e], "psx_refract_multi_f32: distances %d and %d share an output image", f, e);
         a.I_out[d] = I_out[e];
         a.dscale[d] = dscale[e];
     }
     a.ndist = ndist;
-    a.I_in = I_in; a.mask = mask; a.I0 = I0; a.phi_in = phi_in; a.out_scale = out_scale; a.accumulate = accumulate;
-    a.Dx_out = Dx_out; a.Dy_out = Dy_out; a.I_mut = I_mut; a.Nx = Nx; a.Ny = Ny; a.margin = margin;
-    a.clamp_xf = (float)clamp_x; a.clamp_yf = (float)clamp_y; a.status = status; a.stamps = g_stamps;
+    fill_shared(a, Nx, Ny, margin, clamp_x, clamp_y, status, out_scale, accumulate);
+    a.I_in = I_in; a.mask = mask; a.I0 = I0; a.phi_in = phi_in;
+    a.Dx_out = Dx_out; a.Dy_out = Dy_out; a.I_mut = I_mut; a.stamps = g_stamps;
     if (Dx_out) {
         const size_t padded = sizeof(float) * (size_t)(Nx + 2 * margin) * (size_t)(Ny + 2 * margin);
         PSX_HIP(hipMemsetAsync(Dx_out, 0, padded, st));     // zero margins (RF2:65-66)
@@ -1201,15 +1218,10 @@ int psx_refract_batch_f32(int n, const float *const *I_in, const float *I0, cons
     PSX_REQUIRE(nmat > 0, "psx_refract_batch_f32: the phase comes from the thickness maps (nmat > 0)");
     const bool has_I = I_in != nullptr && I_in[0] != nullptr;
     PSX_REQUIRE(has_I || I0 != nullptr, "psx_refract_batch_f32: neither input images nor uniform intensities");
-    for (int e = 0; e < n; ++e) {
-        PSX_REQUIRE(I_out[e] != nullptr, "psx_refract_batch_f32: null output image %d", e);
+    for (int e = 0; e < n; ++e)
         PSX_REQUIRE(!has_I || I_in[e] != nullptr, "psx_refract_batch_f32: input images for all refractions or for none (%d)", e);
-        for (int f = 0; f < e; ++f) PSX_REQUIRE(I_out[f] != I_out[e], "psx_refract_batch_f32: refractions %d and %d share an output image", f, e);
-    }
+    if (int rc = check_refract_call("psx_refract_batch_f32", "refractions", Nx, Ny, margin, I_out, n)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    PSX_REQUIRE(Nx >= 3 && Ny >= 3, "psx_refract_batch_f32: grid %dx%d too small for the edge_order=2 gradient", Nx, Ny);
-    PSX_REQUIRE((int64_t)Nx * Ny < (1ll << 31), "psx_refract_batch_f32: grid %dx%d exceeds int32 pixel indices", Nx, Ny);
-    PSX_REQUIRE(margin >= 8 && margin <= 4096, "psx_refract_batch_f32: margin %d must be >= 8 (the widest gather halo)", margin);
     const size_t chunk_ws = batch_chunk_max(Nx, Ny);
     for (int e0 = 0; e0 < n; e0 += REFRACT_TAB) {           // REFRACT_TAB argument blocks fit one launch
         const int m = std::min(REFRACT_TAB, n - e0);
@@ -1219,15 +1231,13 @@ int psx_refract_batch_f32(int n, const float *const *I_in, const float *I0, cons
             RefractArgs &a = t.e[k];
             if (int rc = pack_mats(a.m, T, cphase ? cphase + (size_t)e * nmat : nullptr, catt ? catt + (size_t)e * nmat : nullptr, nmat))
                 return rc;
+            fill_shared(a, Nx, Ny, margin, clamp_x, clamp_y, status, out_scale, accumulate);
             a.ndist = 1;
-            a.I_in = has_I ? I_in[e] : nullptr; a.mask = nullptr; a.I0 = I0 ? I0[e] : 1.f;
+            a.I_in = has_I ? I_in[e] : nullptr; a.I0 = I0 ? I0[e] : 1.f;
             for (int d = 0; d < PSX_MAX_DIST; ++d) {
                 a.I_out[d] = I_out[e];
                 a.dscale[d] = dscale[e];
             }
-            a.phi_in = nullptr; a.out_scale = out_scale; a.accumulate = accumulate;
-            a.Dx_out = nullptr; a.Dy_out = nullptr; a.I_mut = nullptr; a.Nx = Nx; a.Ny = Ny; a.margin = margin;
-            a.clamp_xf = (float)clamp_x; a.clamp_yf = (float)clamp_y; a.status = status; a.stamps = nullptr;
         }
         void *ws = (char *)workspace + (size_t)(e0 / REFRACT_TAB) * chunk_ws;     // every chunk its own far-ray lists
         const int rc = PSX_GEO_DISPATCH(G_, launch_refract_batch<G_>(t, m, has_I, nmat, ws, st));

@@ -419,21 +419,34 @@ def accumulate_many(acc, imgs, sums, weights, scales=None, mats=None, add=True):
 
 
 # ----------------------------------------------------------------------------------------------- refraction
-def refract(shape, mats, dscale, clamp, margin=15, I_in=None, I0=1.0, phi_in=None, out=None, out_scale=1.0, add=False,
-            want_D=False, I_mut=None):
-    """K9-K13 (refractionFileNumba2.py:25-86 + 198-263).  Returns (I_out, Dx|None, Dy|None); Dx,Dy are padded."""
-    mats = _mats(mats)
+def _refract_io(shape, outs, k, add, mats=None, I_in=None, phi_in=None, on=None, name="I_out",
+                missing="existing output images"):
+    """The preamble the refraction wrappers share; returns (Nx, Ny, device, outs).  The optional inputs I_in / phi_in are
+    checked; the device is that of `on`, else of the first input given, else of the maps; the k output images are allocated
+    there (not with add=True, which needs the `missing` ones) or checked under `name` (numbered where it holds a %d)."""
     Nx, Ny = int(shape[0]), int(shape[1])
-    dev = (I_in if I_in is not None else (phi_in if phi_in is not None else mats.map(0))).device
+    if on is None:
+        on = I_in if I_in is not None else (phi_in if phi_in is not None else mats.map(0))
+    dev = on.device
     if I_in is not None:
         _need(I_in, torch.float32, "I_in", (Nx, Ny))
     if phi_in is not None:
         _need(phi_in, torch.float64, "phi_in", (Nx, Ny))
-    if out is None:
+    if outs is None:
         if add:
-            raise PsxError("add=True needs an existing output image")
-        out = torch.empty((Nx, Ny), dtype=torch.float32, device=dev)
-    _need(out, torch.float32, "I_out", (Nx, Ny))
+            raise PsxError("add=True needs " + missing)
+        outs = [torch.empty((Nx, Ny), dtype=torch.float32, device=dev) for _ in range(k)]
+    for e, t in enumerate(outs):
+        _need(t, torch.float32, name % e if "%" in name else name, (Nx, Ny))
+    return Nx, Ny, dev, outs
+
+
+def refract(shape, mats, dscale, clamp, margin=15, I_in=None, I0=1.0, phi_in=None, out=None, out_scale=1.0, add=False,
+            want_D=False, I_mut=None):
+    """K9-K13 (refractionFileNumba2.py:25-86 + 198-263).  Returns (I_out, Dx|None, Dy|None); Dx,Dy are padded."""
+    mats = _mats(mats)
+    Nx, Ny, dev, (out,) = _refract_io(shape, None if out is None else [out], 1, add, mats, I_in, phi_in,
+                                      missing="an existing output image")
     Dx = Dy = None
     if want_D:
         Dx = torch.empty((Nx + 2 * margin, Ny + 2 * margin), dtype=torch.float32, device=dev)
@@ -454,19 +467,8 @@ def refract_split(shape, mats, dscale, clamp, mask, margin=15, I_in=None, I0=1.0
     """fastRefractionDF's split and its two refractions (RF2:147-154) in one call (psx_refract_split_f32): returns
     (refraction of the sources where mask == 0, refraction of the sources where mask != 0); mask: float32 [Nx][Ny]."""
     mats = _mats(mats)
-    Nx, Ny = int(shape[0]), int(shape[1])
-    _need(mask, torch.float32, "mask", (Nx, Ny))
-    dev = mask.device
-    if I_in is not None:
-        _need(I_in, torch.float32, "I_in", (Nx, Ny))
-    if phi_in is not None:
-        _need(phi_in, torch.float64, "phi_in", (Nx, Ny))
-    if outs is None:
-        if add:
-            raise PsxError("add=True needs existing output images")
-        outs = [torch.empty((Nx, Ny), dtype=torch.float32, device=dev) for _ in range(2)]
-    for o in outs:
-        _need(o, torch.float32, "I_out", (Nx, Ny))
+    _need(mask, torch.float32, "mask", (int(shape[0]), int(shape[1])))
+    Nx, Ny, dev, outs = _refract_io(shape, outs, 2, add, mats, I_in, phi_in, on=mask)
     ws = _workspace(dev, lib().psx_refract_multi_workspace_bytes(Nx, Ny, 2))
     T, cp, ca, n = mats.cargs((Nx, Ny))
     check(lib().psx_refract_split_f32(_ptr(I_in), _ptr(mask), c_float(I0), T, cp, ca, n, _ptr(phi_in), _ptr(outs[0]),
@@ -483,16 +485,10 @@ def refract_batch(shape, mats, dscales, clamp, margin=15, I_in=None, I0=None, ou
     ne = len(dscales)
     Nx, Ny = int(shape[0]), int(shape[1])
     T, nm, cph, cat = _batch_mats(mats, ne, (Nx, Ny), "refract_batch")
-    dev = (mats.base if isinstance(mats, MaterialBatch) else _mats(mats[0])).map(0).device
-    if I_in is not None:
-        for e, t in enumerate(I_in):
-            _need(t, torch.float32, "I_in[%d]" % e, (Nx, Ny))
-    if outs is None:
-        if add:
-            raise PsxError("add=True needs existing output images")
-        outs = [torch.empty((Nx, Ny), dtype=torch.float32, device=dev) for _ in range(ne)]
-    for e, t in enumerate(outs):
-        _need(t, torch.float32, "outs[%d]" % e, (Nx, Ny))
+    maps = (mats.base if isinstance(mats, MaterialBatch) else _mats(mats[0])).map(0)
+    for e, t in enumerate(I_in if I_in is not None else ()):
+        _need(t, torch.float32, "I_in[%d]" % e, (Nx, Ny))
+    _, _, dev, outs = _refract_io(shape, outs, ne, add, on=maps, name="outs[%d]")
     I0 = [1.0] * ne if I0 is None else [float(v) for v in I0]
     for e0 in range(0, ne, _lib.PSX_MAX_SRC):
         el = range(e0, min(ne, e0 + _lib.PSX_MAX_SRC))
@@ -515,21 +511,10 @@ def refract_multi(shape, mats, dscales, clamp, margin=15, I_in=None, I0=1.0, phi
     one launch per kernel (psx_refract_multi_f32); the thickness maps are read once per tile for all distances.
     Returns the list of images, each identical to refract(..., dscale=dscales[d])[0]."""
     mats = _mats(mats)
-    Nx, Ny = int(shape[0]), int(shape[1])
     nd = len(dscales)
-    dev = (I_in if I_in is not None else (phi_in if phi_in is not None else mats.map(0))).device
-    if I_in is not None:
-        _need(I_in, torch.float32, "I_in", (Nx, Ny))
-    if phi_in is not None:
-        _need(phi_in, torch.float64, "phi_in", (Nx, Ny))
-    if outs is None:
-        if add:
-            raise PsxError("add=True needs existing output images")
-        outs = [torch.empty((Nx, Ny), dtype=torch.float32, device=dev) for _ in range(nd)]
-    if len(outs) != nd:
+    if outs is not None and len(outs) != nd:
         raise PsxError("refract_multi: %d output images for %d distances" % (len(outs), nd))
-    for o in outs:
-        _need(o, torch.float32, "I_out", (Nx, Ny))
+    Nx, Ny, dev, outs = _refract_io(shape, outs, nd, add, mats, I_in, phi_in)
     ws = _workspace(dev, lib().psx_refract_multi_workspace_bytes(Nx, Ny, nd))
     T, cp, ca, n = mats.cargs((Nx, Ny))
     dsc = (c_double * nd)(*[float(x) for x in dscales])

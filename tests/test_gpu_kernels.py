@@ -606,6 +606,54 @@ def test_order_independent_far_replay_needs_no_workspace_state(ops):
     assert (gx * ds[3]).max() > 6
 
 
+@pytest.mark.parametrize("halo", [4, 16])
+def test_deterministic_batch_over_two_chunks_is_the_single_call(ops, halo):
+    """The order-independent replay of a batch that needs TWO chunks of argument blocks (9 refractions, 8 per chunk): every
+    refraction has its own far lists, maximum word, fold counts and scratch words in the chunk's share of the workspace.  The
+    buffer is garbage before every call and has held a call of another layout (8 distances of one refraction); all 9 images
+    are bitwise repeatable and bitwise the single call's.  Every refraction has rays beyond the halo."""
+    import paresis_amd.ops as O
+    rng = np.random.default_rng(11)
+    Nx, Ny, ne = 120, 70, 9
+    ramp = np.broadcast_to(np.cumsum(rng.uniform(0, 2e-5, (Nx, 1)), axis=0), (Nx, Ny))      # up to ~3.6 rad per pixel along x
+    Tn = np.stack([ramp, rng.uniform(0, 4e-5, (Nx, Ny))]).astype(np.float32)
+    T = dev(Tn, torch.float32)
+    k = 2.6e11
+    mats = ops.MaterialStack(T, cphase=[-k * 6.2e-7, -k * 9.9e-8], catt=[-2 * k * 4e-9, -2 * k * 4.5e-11])
+    factors = [0.8 + 0.0625 * e for e in range(ne)]
+    stacks = [mats.with_coeffs(cphase=[c * f for c in mats.cphase], catt=[c * (2.0 - f) for c in mats.catt]) for f in factors]
+    dscales = [6.5 + 0.5 * e for e in range(ne)]      # under 1 % to over half of the rays beyond 17 pixels, most beyond 5
+    I0 = [100.0 - 7.0 * e for e in range(ne)]
+    phi = Tn[0].astype(np.float64) * mats.cphase[0] + Tn[1].astype(np.float64) * mats.cphase[1]
+    reach = max(np.abs(np.gradient(phi, axis=0)).max(), np.abs(np.gradient(phi, axis=1)).max())
+    for e in range(ne):
+        assert reach * factors[e] * dscales[e] > halo + 1, (e, reach)      # far rays in every refraction, at either halo
+
+    def trash():
+        for buf in O._workspaces.values():
+            buf.random_(0, 255)
+
+    ops.set_refract_halo(halo)
+    try:
+        ops.set_deterministic(True)
+        O._workspace(T.device, O.lib().psx_refract_batch_workspace_bytes(Nx, Ny, ne))      # one buffer for both layouts
+        trash()
+        ops.refract_multi((Nx, Ny), mats, [1.0 + 0.5 * d for d in range(8)], (Nx, Ny), I0=100.0)
+        runs = []
+        for _ in range(2):
+            trash()
+            runs.append([t.clone() for t in ops.refract_batch((Nx, Ny), stacks, dscales, (Nx, Ny), I0=I0)])
+        for e in range(ne):
+            assert torch.equal(runs[0][e], runs[1][e]), e
+            trash()
+            one = ops.refract((Nx, Ny), stacks[e], dscales[e], (Nx, Ny), I0=I0[e])[0]
+            assert torch.equal(one, runs[0][e]), e
+        ops.check_status(T.device)
+    finally:
+        ops.set_deterministic(False)
+        ops.set_refract_halo(4)
+
+
 @pytest.mark.parametrize("case", ["masked", "black_beside_bright", "pile_up"])
 @pytest.mark.parametrize("halo", [4, 8, 16])
 def test_order_independent_replay_has_no_float_fallback(ops, case, halo):

@@ -44,6 +44,49 @@ def test_bad_arguments_fail_loudly_without_gpu():
     assert rc == -1
 
 
+def test_refraction_workspace_sizes_follow_the_stated_layout():
+    """The two size entry points against the layout stated here on its own: per tile geometry the far counts and lists of
+    every list of the call, behind them (order-independent replay only) a 16-byte maximum word, the fold counts and one
+    8-byte scratch word per pixel and distance; a call reserves the largest over the five geometries, a batch one chunk of
+    8 one-distance refractions per 8 refractions begun."""
+    from paresis_amd import _lib
+    lib = _lib.lib()
+    tiles = (56, 52, 48, 40, 32)                     # TH = TW of the five halos
+
+    def cdiv(a, b):
+        return -(-a // b)
+
+    def pad16(b):
+        return cdiv(b, 16) * 16
+
+    def lists(Nx, Ny, t, nd):
+        nt = cdiv(Nx, t) * cdiv(Ny, t)
+        return pad16(4 * nt * nd) + 16 * nt * nd * t * t
+
+    def det(Nx, Ny, t, nd):
+        nt = cdiv(Nx, t) * cdiv(Ny, t)
+        return 16 + pad16(4 * nt * nd) + 8 * Nx * Ny * nd
+
+    was = lib.psx_get_deterministic()
+    try:
+        for on in (0, 1):
+            assert lib.psx_set_deterministic(on) == 0
+            for Nx, Ny in ((3, 3), (56, 56), (57, 56), (100, 50), (333, 290), (4096, 4096)):
+                for nd in (1, 2, 8):
+                    want = max(lists(Nx, Ny, t, nd) + on * det(Nx, Ny, t, nd) for t in tiles)
+                    assert lib.psx_refract_multi_workspace_bytes(Nx, Ny, nd) == want, (on, Nx, Ny, nd)
+                assert lib.psx_refract_workspace_bytes(Nx, Ny) == lib.psx_refract_multi_workspace_bytes(Nx, Ny, 1)
+                chunk = max(lists(Nx, Ny, t, 8) + on * 8 * det(Nx, Ny, t, 1) for t in tiles)
+                for n in (1, 8, 9, 16):
+                    assert lib.psx_refract_batch_workspace_bytes(Nx, Ny, n) == cdiv(max(n, 1), 8) * chunk, (on, Nx, Ny, n)
+            for args in ((0, 5, 1), (5, -1, 1), (5, 5, 0)):
+                assert lib.psx_refract_multi_workspace_bytes(*args) == 16, args
+            for args in ((0, 5, 3), (5, -1, 3)):
+                assert lib.psx_refract_batch_workspace_bytes(*args) == 16, args
+    finally:
+        lib.psx_set_deterministic(was)
+
+
 def test_no_cpu_fallback():
     import torch
     from paresis_amd import ops

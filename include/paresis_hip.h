@@ -582,6 +582,35 @@ int psx_fbp_tv_step_f32(psx_fbp_plan *plan, int n, double lambda, int nonneg, co
                         const float *xbar_in, float *xbar_out, const float *px_in, const float *py_in, float *px_out,
                         float *py_out, void *stream);
 
+/* ---- spectral material decomposition of energy-binned scans (paresis_amd/spectral.py) -------------------------------------
+ * Projection-domain decomposition: per pixel, from the B per-bin log-transmissions L_b = -ln(transmission of bin b), the
+ * thicknesses x_m (metres) of M <= B materials under the polychromatic model
+ *   T_b(x) = sum_e w_be exp(-sum_m a_mbe x_m),
+ * w_be the flat field's per-energy share of bin b (each bin's summing to 1), a_mbe the linear attenuation coefficient of
+ * material m at that energy (1/m): beam hardening is part of the model.  Per pixel, in float64 throughout:
+ *   any L_b not finite: thickness 0, residual +inf, steps -1;
+ *   start x = G L, G the M x B matrix of the linearised problem, (Abar^T V Abar)^-1 Abar^T V with Abar_bm = sum_e w_be a_mbe
+ *   (the caller's: row-major [M][B]);
+ *   iteration k = 1 .. iterations (weighted Gauss-Newton): per bin s_e = w_be exp(-sum_m a_mbe x_m), T_b = sum_e s_e,
+ *   g_bm = sum_e a_mbe s_e / T_b, r_b = L_b + ln T_b; N = sum_b v_b g_b g_b^T and rhs = sum_b v_b g_b r_b are added to bin by
+ *   bin; N d = rhs by LDL^T without pivoting (as psx_lcs_df_f32).  A pivot <= 0 or not finite, or a d that is not finite:
+ *   steps = -2 and x is kept.  Otherwise x += d, steps = k, and the pixel stops when max_m |d_m| abar_m <= tol,
+ *   abar_m = max_b Abar_bm: on its own step alone, so a pixel's result does not depend on its neighbours;
+ *   residual = sqrt(sum_b v_b r_b^2) at the final x.  The thickness is never clamped.
+ * A pixel with L = 0 in all bins gives exactly 0 where every bin's weights sum to exactly 1 in float64.
+ * logT: HOST array of B device pointers to n float32 values; bin_size[b] >= 1 energies in bin b, their sum E <= 256; w: the E
+ * weights, bin after bin; a: [M][E]; v: B bin weights, each finite and > 0; G: [M][B] -- HOST arrays all, copied in the
+ * call.  thickness: HOST array of M device pointers to n float32 values; residual, steps: n float32 each, or NULL.
+ * PSX_E_ARG, before any GPU call: a null pointer, B outside [1, PSX_DECOMP_MAX_BINS], M outside [1, PSX_DECOMP_MAX_MAT],
+ * M > B, a bin size < 1 or a sum above PSX_DECOMP_MAX_ENERGIES, a v that is not finite and > 0, iterations < 1, tol negative or
+ * not finite, n < 1.  One launch; like psx_membrane_f32 the call waits for the stream once (the tables' upload). */
+#define PSX_DECOMP_MAX_MAT 4
+#define PSX_DECOMP_MAX_BINS 8
+#define PSX_DECOMP_MAX_ENERGIES 256      /* all bins together */
+int psx_decompose_f32(const float *const *logT, int B, const int *bin_size, const double *w, const double *a, int M,
+                      const double *v, const double *G, int iterations, double tol, int64_t n,
+                      float *const *thickness, float *residual, float *steps, void *stream);
+
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------------------------------------
  * psx_profile_enable(1) clears the log and makes every kernel launch of the library record a HIP event pair on the
  * stream it is launched on; psx_profile_summary() waits for the recorded events and writes one line per kernel,

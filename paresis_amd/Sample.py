@@ -229,11 +229,15 @@ class AnalyticalSample(Sample):
         """MaterialStack for intensity + phase: cphase = -k delta, catt = -2 k beta (Sample.py:347-348).  Scattering
         materials enter with their thickness scaled by the sphere volume fraction (Sample.py:332,343), which is the same
         as scaling their two coefficients -- and so they fold (ops.MaterialStack), while dark_field() reads the raw maps."""
+        cphase, catt = self.coeffs_rt(energy, phase, att)
+        return ops.MaterialStack(self.geometry_dev(), cphase=cphase, catt=catt, fold_cache=self.fold_cache())
+
+    def coeffs_rt(self, energy, phase=True, att=True):
+        """stack_rt's (cphase, catt), one value per material: host numbers, no geometry and no GPU needed."""
         k = k_sample(energy)
         d, b = self._coeff(self.delta, energy), self._coeff(self.beta, energy)
         frac = np.array([1.0 if self._df_model(i) is None else self._df_model(i)[1] for i in range(len(self.myMaterials))])
-        return ops.MaterialStack(self.geometry_dev(), cphase=(-k * d * frac if phase else 0 * d),
-                                 catt=(-2 * k * b * frac if att else 0 * b), fold_cache=self.fold_cache())
+        return (-k * d * frac if phase else 0 * d), (-2 * k * b * frac if att else 0 * b)
 
     DF_CACHE_BYTES = 16 << 30  # width maps kept per sample: one float64 map per energy of a spectrum, least recently used out first
 

@@ -5,6 +5,7 @@
                                [--out DIR] [--format .tif|.edf|.npy] [--xml DIR] [--no-noise] [--seed S] [--backend nccl|gloo]
                                [--retrieve [--max-shift S] [--dark-field] [--method lcs|umpa|umpa-df --window W --search M]]
                                [--retrieve-propagation [--material NAME]]
+                               [--decompose [--decompose-materials A,B]]
                                [--tomography A [--tomography-modality attenuation|phase [--tomography-differential]]
                                 [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]]]
 
@@ -18,7 +19,11 @@ residual_<expID><fmt>; it takes neither --dark-field nor --max-shift.  --method 
 dark-field term and adds visibility_<expID><fmt>.  --retrieve-propagation (independent of --retrieve; any number of
 positions) runs Paganin's single-material retrieval of each bin's propagation image over its flat field on rank 0 and writes
 propag/retrieval/{contact,thickness,phi}_<expID><fmt> under the bin's directory; --material names the sample material whose
-delta and beta the filter takes (default: the sample of interest's first).  --tomography A (samples that are the contrast
+delta and beta the filter takes (default: the sample of interest's first).  --decompose (independent of --retrieve; any number
+of positions; a run of several energy bins) decomposes the bins' propagation images over their flat fields into one thickness
+map per sample material on rank 0 (paresis_amd/spectral.py: the run's own spectrum and the materials' attenuation, beam
+hardening included) and writes propag/materials/thickness_<material>_<expID><fmt> and residual_<expID><fmt> under the first
+bin's directory; --decompose-materials names the materials to decompose into (default: all of the sample's).  --tomography A (samples that are the contrast
 phantom or a getVolumeFromFile label volume) then turns the sample through A angles on [0, 180) degrees, runs the chain at
 each (paresis_amd/tomography.py scan),
 reconstructs by filtered back-projection on rank 0 and writes tomography/mu_<expID> (--tomography-modality attenuation,
@@ -41,7 +46,8 @@ import numpy as np
 
 def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
         method='lcs', window=2, search=3, propagation=False, material=None, tomography=0, tomography_modality='attenuation',
-        tomography_method='fbp', tomography_iterations=0, tomography_weight=None, tomography_differential=False):
+        tomography_method='fbp', tomography_iterations=0, tomography_weight=None, tomography_differential=False,
+        decompose=False, decompose_materials=None):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
@@ -56,6 +62,14 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     parameters and the delta, beta of `material` -- retrieval.propagation_material: by default the sample of interest's
     first); with save, contact, thickness and phi go to <bin dir>/propag/retrieval/.  exp_dict['propagationParams'] then
     holds the parameters, the material and the delta, beta, alpha and mu it used.
+
+    decompose (extension, independent of retrieve, any number of positions): rank 0 also decomposes the bins of position
+    0's propagation image over its flat field into the thicknesses of decompose_materials (the sample of interest's
+    materials, all by default; spectral.model_of and spectral.decompose_run); a model that cannot be decomposed -- fewer
+    bins than materials, materials of one energy dependence -- is a ValueError before the images are computed.  With save,
+    <first bin dir>/propag/materials/ gets thickness_<material>_ and residual_<expID><fmt>.  exp_dict['decomposeParams']
+    then holds the materials, the bins' energies and weights and the model's condition number, and
+    exp_dict['decomposition'] the {'thickness', 'residual', 'steps'} device tensors.
 
     tomography = A > 0 (extension; the sample of interest must be the contrast phantom or a getVolumeFromFile label
     volume): after the run, rank 0 turns it through A angles on [0, 180), runs the chain at each (tomography.scan with
@@ -78,6 +92,8 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
         check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
     if material is not None and not propagation:
         raise ValueError("material is an option of propagation")
+    if decompose_materials is not None and not decompose:
+        raise ValueError("decompose_materials is an option of decompose")
     if retrieve and method != "lcs":
         from .retrieval import check_method
         check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
@@ -108,6 +124,9 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     if propagation:
         from .retrieval import propagation_material
         material = propagation_material(experiment, material)       # a wrong name fails before the images are computed
+    if decompose:
+        from . import spectral
+        spectral_model = spectral.model_of(experiment, decompose_materials)   # a model error fails before the images are computed
     if tomography:
         tomo._phantom(experiment.mySampleofInterest)                # another sample fails before the images are computed
     sim = exp_dict['simulation_type']
@@ -218,6 +237,14 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
         if save:
             for ibin in sorted(propagated):
                 retrieval.save_propagation(propagated[ibin], paths[ibin], exp_dict['expID'], saving_format)
+    if rank == 0 and decompose:
+        decomposed = spectral.decompose_run(gathered, spectral_model)
+        exp_dict['decomposeParams'] = {'materials': list(spectral_model.names), 'energies_keV': [e.tolist() for e in spectral_model.energies],
+                                       'weights': [w.tolist() for w in spectral_model.weights], 'condition': spectral_model.condition(),
+                                       'iterations': spectral.ITERATIONS, 'tol': spectral.TOL}
+        exp_dict['decomposition'] = decomposed
+        if save:
+            spectral.save_decomposition(decomposed, spectral_model.names, paths[0], exp_dict['expID'], saving_format)
     if rank == 0 and tomography:
         angles = [180.0 * a / int(tomography) for a in range(int(tomography))]
         options = {}
@@ -275,6 +302,11 @@ def main(argv=None):
                          "propag/retrieval/{contact,thickness,phi}_<expID><fmt> under each bin's directory")
     ap.add_argument("--material", default=None,
                     help="--retrieve-propagation: the sample material the filter assumes (default: the sample's first)")
+    ap.add_argument("--decompose", action="store_true",
+                    help="material decomposition of the energy bins' propagation images after the run (any --points): "
+                         "propag/materials/thickness_<material>_<expID><fmt> and residual_<expID><fmt> under the first bin's directory")
+    ap.add_argument("--decompose-materials", default=None, metavar="A,B",
+                    help="--decompose: the sample materials to decompose into, comma-separated (default: all of the sample's)")
     tomo.add_tomography_options(ap)              # --tomography and its --tomography-modality, -differential, -method, ...
     a = ap.parse_args(argv)
     exp_dict = {'experimentName': a.experiment, 'filepath': a.out if a.out.endswith('/') else a.out + '/',
@@ -295,12 +327,15 @@ def main(argv=None):
         ap.error("--dark-field needs --points %d or more" % floor[True])
     if a.material is not None and not a.retrieve_propagation:
         ap.error("--material is an option of --retrieve-propagation")
+    if a.decompose_materials is not None and not a.decompose:
+        ap.error("--decompose-materials is an option of --decompose")
     tomo.check_tomography_options(ap, a)
     run(exp_dict, save=True, saving_format=a.format, backend=a.backend, retrieve=a.retrieve, max_shift=a.max_shift,
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
         material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality,
         tomography_method=a.tomography_method, tomography_iterations=a.tomography_iterations,
-        tomography_weight=a.tomography_weight, tomography_differential=a.tomography_differential)
+        tomography_weight=a.tomography_weight, tomography_differential=a.tomography_differential, decompose=a.decompose,
+        decompose_materials=None if a.decompose_materials is None else [m.strip() for m in a.decompose_materials.split(",")])
 
 
 if __name__ == "__main__":

@@ -1194,6 +1194,65 @@ def paganin(images, whites, alpha, mu, plan, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------- spectral material decomposition
+def decompose(logT, bin_size, w, a, v, G, iterations=12, tol=1e-13, out=None):
+    """Projection-domain material decomposition of B energy bins (psx_decompose_f32; the contract is in
+    include/paresis_hip.h): logT, a [B, ...] float32 tensor in HBM or a sequence of B equal-shaped ones, L_b = -ln of bin
+    b's transmission; bin_size, the B numbers of energies per bin (their sum E <= PSX_DECOMP_MAX_ENERGIES); w, the E
+    weights bin after bin; a, the [M][E] attenuation coefficients in 1/m (M <= B, M <= PSX_DECOMP_MAX_MAT); v, the B bin
+    weights (> 0); G, the M x B matrix of the linearised start -- host numbers all (paresis_amd.spectral builds them)
+    -> (thickness [M, ...] in metres, residual [...], steps [...]), float32.  out: three such tensors to write into."""
+    L = [logT[b] for b in range(logT.shape[0])] if isinstance(logT, torch.Tensor) else list(logT)
+    B = len(L)
+    if not 1 <= B <= _lib.PSX_DECOMP_MAX_BINS:
+        raise PsxError("logT: B=%d bins outside [1, %d]" % (B, _lib.PSX_DECOMP_MAX_BINS))
+    bin_size = [int(s) for s in bin_size]
+    E = sum(bin_size)
+    if len(bin_size) != B or min(bin_size) < 1 or E > _lib.PSX_DECOMP_MAX_ENERGIES:
+        raise PsxError("bin_size must hold %d counts >= 1 summing to %d at most, got %r" % (B, _lib.PSX_DECOMP_MAX_ENERGIES, bin_size))
+    w = [float(x) for x in w]
+    a = [[float(x) for x in row] for row in a]
+    v = [float(x) for x in v]
+    G = [[float(x) for x in row] for row in G]
+    M = len(a)
+    if not 1 <= M <= min(B, _lib.PSX_DECOMP_MAX_MAT):
+        raise PsxError("a: M=%d materials outside [1, %d] (B=%d bins)" % (M, min(B, _lib.PSX_DECOMP_MAX_MAT), B))
+    if len(w) != E or any(len(row) != E for row in a):
+        raise PsxError("w and every row of a must hold %d values (the sum of bin_size)" % E)
+    if len(v) != B or not all(math.isfinite(x) and x > 0.0 for x in v):
+        raise PsxError("v must hold %d finite weights > 0, got %r" % (B, v))
+    if len(G) != M or any(len(row) != B for row in G):
+        raise PsxError("G must be %d x %d" % (M, B))
+    if isinstance(iterations, bool) or int(iterations) != iterations or int(iterations) < 1:
+        raise PsxError("iterations must be an integer >= 1, got %r" % (iterations,))
+    if not (math.isfinite(float(tol)) and float(tol) >= 0.0):
+        raise PsxError("tol must be finite and >= 0, got %r" % (tol,))
+    shape = tuple(L[0].shape) if isinstance(L[0], torch.Tensor) else None
+    for b, t in enumerate(L):
+        _need(t, torch.float32, "logT[%d]" % b, shape)
+        _on(t, "logT[%d]" % b, L[0].device, "logT[0]")
+    n = L[0].numel()
+    if n < 1:
+        raise PsxError("logT holds no pixel: shape %s" % (shape,))
+    dev = L[0].device
+    if out is None:
+        out = (torch.empty((M,) + shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev),
+               torch.empty(shape, dtype=torch.float32, device=dev))
+    else:
+        out = tuple(out)
+        _out_count(out, ("thickness", "residual", "steps"))
+        for nm, t, sh in zip(("thickness", "residual", "steps"), out, ((M,) + shape, shape, shape)):
+            _need(t, torch.float32, "out " + nm, sh)
+            _on(t, "out " + nm, dev, "logT")
+    flat = [x for row in a for x in row]
+    with torch.cuda.device(dev):
+        check(lib().psx_decompose_f32(_ptrs(L), B, (c_int * B)(*bin_size), (c_double * E)(*w), (c_double * (M * E))(*flat), M,
+                                      (c_double * B)(*v), (c_double * (M * B))(*[x for row in G for x in row]), int(iterations),
+                                      c_double(float(tol)), n, _ptrs([out[0][m] for m in range(M)]), _ptr(out[1]), _ptr(out[2]),
+                                      _stream()), "psx_decompose_f32")
+    return out
+
+
 # --------------------------------------------------------------------------------------- filtered back-projection
 class FbpPlan(_Plan):
     """psx_fbp_plan (the contract is in include/paresis_hip.h): parallel-beam filtered back-projection of [A, n, m] sinograms

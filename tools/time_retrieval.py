@@ -1,6 +1,6 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project] [--tv] [--volume]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project] [--tv] [--volume] [--decompose]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
@@ -41,6 +41,13 @@ study pixel: on contrast_phantom_volume (13 materials, [512, 2048, 2048] labels)
 boxes, and on a random 8-material volume of the same size (every voxel inside the circle its own label: four different
 labels at most steps).  The baseline is psx_contrast_phantom_f32 at that grid (k_phantom_lines + k_phantom_maps), which is
 how the same maps are made from the 13 analytic discs.  The byte price is one read of the labels and one write of the maps.
+
+--decompose times k_decompose (psx_decompose_f32, the spectral material decomposition) at 2048 x 2048 pixels, M = 2 materials,
+B = 3 bins of 8, 8 and 15 energies (a 20-80 keV spectrum sampled at 2 keV): its price is the float64 exp, one per pixel, energy
+and Gauss-Newton step plus one pass for the residual, counted from the steps the kernel reports and set against the v_fma_f64
+rate -- the time is given as float64 FMA slots per exp.  Beside it: the same iteration written with torch operations in
+float64 (torch_decompose below, kept in this tool only; every pixel takes the kernel's largest step count), timed with a host
+clock around a synchronised loop.
 """
 import argparse
 import ctypes
@@ -404,6 +411,66 @@ def volume_case(dimX, dimY, pix_um, reps):
     run("random 8-material volume", v, 8, True)
 
 
+def _decompose_model():
+    """20-80 keV at 2 keV in bins of 8, 8 and 15 energies; a soft and a bone-like material (1/m)."""
+    E = np.arange(20.0, 81.0, 2.0)
+    t = (E - 18.0) / 62.0
+    flux = t * (1.2 - t) ** 2 + 0.02
+    sizes = [8, 8, 15]
+    cut = np.cumsum([0] + sizes)
+    w = np.concatenate([flux[cut[b]:cut[b + 1]] / flux[cut[b]:cut[b + 1]].sum() for b in range(3)])
+    a = np.stack([54.0 * (20.0 / E) ** 4 + 18.0 * (60.0 / E), 700.0 * (20.0 / E) ** 3.2 + 38.0 * (60.0 / E) ** 0.8])
+    return sizes, w, a
+
+
+def torch_decompose(L, sizes, w, a, v, G, steps):
+    """`steps` Gauss-Newton steps of psx_decompose_f32's iteration for M = 2 on every pixel, in float64 torch operations."""
+    L = L.double()
+    x = torch.einsum("mb,bn->mn", G, L)
+    for _ in range(steps):
+        N00 = N01 = N11 = r0 = r1 = 0.0
+        e0 = 0
+        for b, ne in enumerate(sizes):
+            ab = a[:, e0:e0 + ne]
+            s = w[e0:e0 + ne, None] * torch.exp(-(ab.T @ x))
+            T = s.sum(dim=0)
+            g = (ab @ s) / T
+            r = L[b] + torch.log(T)
+            N00, N01, N11 = N00 + v[b] * g[0] * g[0], N01 + v[b] * g[0] * g[1], N11 + v[b] * g[1] * g[1]
+            r0, r1 = r0 + v[b] * g[0] * r, r1 + v[b] * g[1] * r
+            e0 += ne
+        det = N00 * N11 - N01 * N01
+        x = x + torch.stack([(N11 * r0 - N01 * r1) / det, (N00 * r1 - N01 * r0) / det])
+    return x
+
+
+def decompose_case(n, m, reps):
+    sizes, w, a = _decompose_model()
+    B, E = len(sizes), sum(sizes)
+    v = np.ones(B)
+    cut = np.cumsum([0] + sizes)
+    A = np.stack([a[:, cut[b]:cut[b + 1]] @ w[cut[b]:cut[b + 1]] for b in range(B)])
+    G = np.linalg.solve(A.T @ A, A.T)
+    g = torch.Generator(device="cuda").manual_seed(n + m)
+    x = torch.rand((2, n * m), device="cuda", generator=g, dtype=torch.float64) * torch.tensor([[0.05], [0.01]], device="cuda")
+    wd, ad = torch.from_numpy(w).cuda(), torch.from_numpy(a).cuda()
+    L = torch.stack([-torch.log((wd[cut[b]:cut[b + 1], None] * torch.exp(-(ad[:, cut[b]:cut[b + 1]].T @ x))).sum(dim=0))
+                     for b in range(B)]).float().reshape(B, n, m).contiguous()
+    out = ops.decompose(L, sizes, w, a, v, G)
+    steps = out[2]
+    kmax, ksum = int(steps.max()), float(steps.double().sum())
+    (t,) = _kernel_us(("k_decompose",), lambda: ops.decompose(L, sizes, w, a, v, G, out=out), reps)
+    exps = (ksum + n * m) * E
+    print("n=%d m=%d M=2 B=3 E=%d  k_decompose %9.1f us; steps %d..%d (mean %.2f); %.3g float64 exps = %.2f ns per pixel, %.1f float64 "
+          "FMA slots per exp (at %.3g FMA/s)" % (n, m, E, t, int(steps.min()), kmax, ksum / (n * m), exps, t * 1e3 / (n * m),
+                                                  t * 1e-6 * FMA64_PEAK / exps, FMA64_PEAK))
+    Gd, Lf = torch.from_numpy(G).cuda(), L.reshape(B, -1)
+    ref = torch_decompose(Lf, sizes, wd, ad, v, Gd, kmax)
+    print("    torch_decompose agrees to %.1e m of %.1e m" % (float((ref - out[0].reshape(2, -1).double()).abs().max()), float(ref.abs().max())))
+    t_torch = _host_us(lambda: torch_decompose(Lf, sizes, wd, ad, v, Gd, kmax), max(reps // 4, 2))
+    print("    the same %d steps in torch operations %9.1f us = %.1f x k_decompose" % (kmax, t_torch, t_torch / t))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=20)
@@ -414,7 +481,11 @@ def main():
     ap.add_argument("--project", action="store_true", help="time psx_fbp_project_f32 and psx_fbp_adjoint_f32 only")
     ap.add_argument("--tv", action="store_true", help="time psx_fbp_tv_step_f32 and an iteration of tomography.tv only")
     ap.add_argument("--volume", action="store_true", help="time psx_volume_project_u8 against psx_contrast_phantom_f32 only")
+    ap.add_argument("--decompose", action="store_true", help="time psx_decompose_f32 against the same iteration in torch operations only")
     a = ap.parse_args()
+    if a.decompose:
+        decompose_case(2048, 2048, a.reps)
+        return
     if a.volume:
         volume_case(512, 2048, 20.0, max(a.reps // 4, 2))
         return

@@ -258,6 +258,17 @@ int psx_detect_multi_f32(psx_detector_plan *plan, const float *const *imgs, floa
  * fails with PSX_E_ARG when it exceeds wcap. */
 int psx_detector_operator_host(int N, int ov, int n, int margin, double sigma_src, double sigma_psf, int *start,
                                float *weights, int wcap, int *W_out);
+/* What a plan decided, for tests and tools (host only, no GPU call, nothing about a detection changes): fills info[0 .. min(cap,
+ * PSX_DETECTOR_PLAN_INFO)) and returns how many it wrote (0 for a null plan or info, or cap <= 0), in this order:
+ *   0-3  band widths of the front operators of axis 0 and 1 and of the back (PSF + crop) operators of axis 0 and 1 (0 without
+ *        a PSF);
+ *   4-6  the fused front pair: fits (0/1), its tiles' halos are cheap (0/1), output rows per tile;
+ *   7-8  the fused back pair: fits (0/1), output rows per tile;
+ *   9    both back operators are plain convolutions (0/1: the PSF stage can run as a stencil);
+ *   10   row pitch of the fused front's intermediate image, floats;   11  its row length, floats.
+ * Whether a fused form RUNS also depends on the call: Ny % 4, the images' alignment and the "detect_4pass" switch. */
+#define PSX_DETECTOR_PLAN_INFO 12
+int psx_detector_plan_info(const psx_detector_plan *plan, int *info, int cap);
 /* out[x][y] = sum of the s x s block of img, s = Nx/sx (Detector.resize, Detector.py:185-198) */
 int psx_resize_f32(const float *img, int Nx, int Ny, float *out, int sx, int sy, void *stream);
 /* out[p] = Poisson(lam[p]) drawn from a counter-based generator keyed by (seed, p)  (Detector.py:113-115;

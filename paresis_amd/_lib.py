@@ -25,11 +25,12 @@ PSX_VOLUME_MAX_MAT = 16
 PSX_MAX_DIST = 8
 PSX_MAX_POISSON = 8
 PSX_MAX_DETECT = 4
+PSX_DETECTOR_PLAN_INFO = 12
 PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class PsxError(RuntimeError):
@@ -81,6 +82,7 @@ PROTOTYPES = {
                                               _vpp, _vpp, _fp, _vp]),
     "psx_detector_plan_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, _vpp]),
     "psx_detector_plan_destroy": (c_int, [_vp]),
+    "psx_detector_plan_info": (c_int, [_vp, POINTER(c_int), c_int]),
     "psx_detect_f32": (c_int, [_vp, _vp, _vp, _vp]),
     "psx_detect_multi_f32": (c_int, [_vp, _vpp, _vpp, c_int, _vp]),
     "psx_detector_operator_host": (c_int, [c_int, c_int, c_int, c_int, c_double, c_double, POINTER(c_int), _fp, c_int,

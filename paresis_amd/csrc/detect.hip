@@ -1012,6 +1012,18 @@ int psx_detector_plan_destroy(psx_detector_plan *p) {
     return 0;
 }
 
+int psx_detector_plan_info(const psx_detector_plan *p, int *info, int cap) {
+    if (!p || !info || cap <= 0) return 0;
+    const int v[PSX_DETECTOR_PLAN_INFO] = {p->fx.W, p->fy.W, p->bx.W, p->by.W,
+                                           p->front.ok, p->front.cheap, p->front.RT,
+                                           p->back.ok, p->back.RT,
+                                           p->bx.stencil && p->by.stencil,
+                                           p->pitch2, p->fy.n_out};
+    const int n = std::min(cap, (int)PSX_DETECTOR_PLAN_INFO);
+    std::copy(v, v + n, info);
+    return n;
+}
+
 namespace {
 
 // strips of rows per workgroup: enough workgroups to fill 256 CUs several times over, strips long enough to amortise

@@ -819,6 +819,19 @@ class DetectorPlan(_Plan):
         self._create(device, "psx_detector_plan_create", self.Nx, self.Ny, int(ov), self.nx, self.ny, int(margin),
                      c_double(sigma_src), c_double(sigma_psf))
 
+    INFO_FIELDS = ("fx_W", "fy_W", "bx_W", "by_W", "front_ok", "front_cheap", "front_RT", "back_ok", "back_RT", "back_stencil",
+                   "pitch2", "fy_n_out")
+
+    def info(self):
+        """What the plan decided (psx_detector_plan_info, host only): the band widths of the four operators, whether the fused
+        pairs fit (and the front's halos are cheap), their rows per tile, whether the PSF stage is a plain stencil, and the
+        pitch and row length of the fused front's intermediate image."""
+        buf = (c_int * _lib.PSX_DETECTOR_PLAN_INFO)()
+        n = lib().psx_detector_plan_info(self._h, buf, len(buf))
+        if n != len(self.INFO_FIELDS):
+            raise _lib.PsxError("psx_detector_plan_info wrote %d of %d fields" % (n, len(self.INFO_FIELDS)))
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in buf)))
+
     def detect(self, img, out=None):
         _need(img, torch.float32, "img", (self.Nx, self.Ny))
         if out is None:

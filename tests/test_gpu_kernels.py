@@ -406,8 +406,9 @@ def test_detector_multi_block_grids(ops, case):
     """The banded detector kernels on grids of several 256-output blocks: the fused (contiguous axis, axis 0) pairs where
     the rows are 16-byte aligned and the bands fit (front only, front + PSF, the bench geometry) and the four-pass form
     elsewhere (unaligned rows, wide source blur), with and without each blur; the PSF stage as a stencil (k_psf_tile: 5, 9, 11, 13
-    and 15 taps, its three instantiations) and as a banded pair (19 taps): against the dense composite operator of the
-    host builder (the one the CPU suite holds to the oracle), applied in float64."""
+    and 15 taps, its three instantiations) and as two passes, k_band_cols + k_band_rows (19 taps: too wide for the fused
+    pair, whose contiguous band holds at most 16; tests/test_gpu_detector.py runs the back pair): against the dense
+    composite operator of the host builder (the one the CPU suite holds to the oracle), applied in float64."""
     Nx, Ny, ov, sig_src, sig_psf = case
     nx, ny = Nx // ov, Ny // ov
     rng = np.random.default_rng(Nx + Ny)

@@ -17,6 +17,7 @@ from oracle import paresis_oracle as orc
 from paresis_amd import _lib
 from tests import _materials_oracle as mo
 from tests._golden import relmax
+from tests._profile import profile_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -236,20 +237,6 @@ def check_propagate(ops, st, m, seed, engine, with_wave):
         assert relmax(host(it), 0.5 + isc * np.abs(ref) ** 2) < TOL, (st.name, engine, z)
     plan.close()
     return worst
-
-
-def profile_counts(run):
-    """{kernel name: launches} of what run() launches, through psx_profile_*."""
-    lib = _lib.lib()
-    lib.psx_profile_enable(1)
-    try:
-        run()
-        torch.cuda.synchronize()
-        buf = ctypes.create_string_buffer(1 << 14)
-        _lib.check(lib.psx_profile_summary(buf, len(buf)), "psx_profile_summary")
-    finally:
-        lib.psx_profile_enable(0)
-    return {l.split()[0]: int(l.split()[1]) for l in buf.value.decode().splitlines() if l.strip()}
 
 
 def check_propagate_sources(ops, st, m, seed):

@@ -31,6 +31,9 @@ struct BandOp {
     std::vector<int> h_start;   // host copy of start[] (row tiles of the fused pair are laid out from it)
     bool stencil = false;       // every output reads start[0] + o .. with the SAME weights (a plain convolution: k_psf_tile)
     std::vector<float> h_w0;    // those weights
+    bool stage16 = false;       // k_band_cols can stage 16 bytes a load: rows of whole float4s, spans of at most 64 * STAGE_MIT
+                                // float4, at most 64 taps (the full-resolution pass always does for even grids); band_cols adds
+                                // the alignment of the image it is given
 };
 
 // A contiguous-axis operator followed by an axis-0 operator in ONE pass (k_band_pair): per tile of RT output rows the
@@ -47,13 +50,13 @@ struct psx_detector_plan {
     int Nx = 0, Ny = 0, ov = 0, nx = 0, ny = 0, margin = 0;
     BandOp fx, fy, bx, by;   // front / back operator of each axis; back.n_out == 0 when there is no PSF
     DevBuf<float> t1;        // [Nx][fy.n_out]
-    DevBuf<float> t2;        // [fx.n_out][fy.n_out]   (only with a PSF)
+    DevBuf<float> t2;        // [slots][fx.n_out][pitch2] (only with a PSF), pitch2 = fy.n_out rounded up to 4 (16-byte rows for
+                             // the back pair's loads); PSX_MAX_DETECT slots, one per image of a psx_detect_multi_f32 launch,
+                             // where the back pair fits, else 1.  A two-pass stage uses slot 0 at pitch fy.n_out.
     DevBuf<float> t3;        // [fx.n_out][ny]         (only with a PSF)
-    BandPair front, back;    // fused (contiguous axis, axis 0) pairs; front writes t2p, back reads it
-    DevBuf<float> t2p;       // [PSX_MAX_DETECT][fx.n_out][pitch2], pitch2 = fy.n_out rounded up to 4 (16-byte rows for the back
-                             // pair's loads); one per image of a psx_detect_multi_f32 launch
+    BandPair front, back;    // fused (contiguous axis, axis 0) pairs; front writes t2, back reads it
     int pitch2 = 0;
-    size_t bytes = 0;
+    bool psf_stencil = false;   // the PSF stage as a stencil (k_psf_tile): both back operators plain convolutions of at most 17 taps
 };
 
 namespace {
@@ -165,29 +168,90 @@ void compose_axis(int N, int ov, int n, int margin, double sigma_src, double sig
 // A workgroup owns 256 consecutive outputs c and a strip of rows.  The weights of output c sit in registers (WMAX of
 // them, the band is narrower than that); the input span the 256 outputs need -- start[c0] .. start[c0+255] + W, about
 // 256 ov + W floats -- is staged row by row (RG rows per round) in LDS with coalesced loads, so HBM sees every input once.
-template <int WMAX, int RG>
+//
+// The 16-byte staging of a round of eight rows (k_band_cols with MIT != 0, k_band_pair), for rows that are 16-byte aligned
+// (pitch % 4 == 0, aligned base) and spans of at most 64 * MIT float4 per row: wave v of the workgroup stages rows v, v+4 of
+// the round; all of a thread's loads (2 rows x MIT float4) are issued before the first LDS write, so ~10 KB per wave are in
+// flight.
+constexpr int STAGE_MIT = 5;     // float4 per lane and staged row: spans up to 1280 floats
+
+template <int MIT>
+struct Stage16 {
+    float4 v[2][MIT];
+    // rows i0 + wave (+ 4) of img, none beyond row ilast, columns s0 + 4 t4 for t4 < n4 (s0 % 4 == 0)
+    __device__ __forceinline__ void fetch(const float *img, int pitch, int s0, int n4, int i0, int ilast) {
+        const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = min(i0 + wv + 4 * h, ilast);
+            const float4 *row = reinterpret_cast<const float4 *>(img + (int64_t)i * pitch + s0);
+#pragma unroll
+            for (int m = 0; m < MIT; ++m) {
+                const int t4 = ln + 64 * m;
+                // rows are whole float4s (pitch % 4 == 0): a float4 lies wholly inside or wholly outside its row; beyond the
+                // row: zeros (a band wider than the axis)
+                v[h][m] = (t4 < n4 && s0 + 4 * t4 < pitch) ? row[t4] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    }
+    // into stage[8][span_ld]; columns at and beyond Cin are pitch padding, not data.  PADDED = false: the caller's rows have
+    // none (Cin == pitch), and the mask is left out (it cost k_band_cols 2 to 5 VGPRs: 81 for 79 at 16 taps, a wave per SIMD)
+    template <bool PADDED>
+    __device__ __forceinline__ void commit(float *stage, int span_ld, int s0, int n4, int Cin) const {
+        const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int m = 0; m < MIT; ++m) {
+                const int t4 = ln + 64 * m;
+                if (t4 < n4) {
+                    float4 x = v[h][m];
+                    const int e = s0 + 4 * t4;
+                    if (PADDED && e + 3 >= Cin) {
+                        x.x = e < Cin ? x.x : 0.f;
+                        x.y = e + 1 < Cin ? x.y : 0.f;
+                        x.z = e + 2 < Cin ? x.z : 0.f;
+                        x.w = 0.f;
+                    }
+                    *reinterpret_cast<float4 *>(stage + (wv + 4 * h) * span_ld + 4 * t4) = x;
+                }
+            }
+    }
+};
+
+// MIT = 0: any rows, staged with 4-byte loads, four to a round; MIT != 0: the 16-byte staging (span_ld % 4 == 0).
+template <int WMAX, int MIT>
 __global__ __launch_bounds__(256) void k_band_cols(const float *__restrict__ in, float *__restrict__ out,
                                                    const int *__restrict__ start, const int2 *__restrict__ blk,
                                                    const float *__restrict__ wT, int R, int Cin, int Cout, int W,
                                                    int span_ld, int rows_per_block) {
-    extern __shared__ float sdet[];                       // [RG][span_ld]
+    constexpr int RG = MIT ? 8 : 4;
+    extern __shared__ __attribute__((aligned(16))) float sdet[];     // [RG][span_ld]
     const int c0 = blockIdx.x * 256, c = c0 + threadIdx.x;
     const bool live = c < Cout;
     const int cl = live ? c : Cout - 1;
-    const int s0 = blk[blockIdx.x].x, s1 = blk[blockIdx.x].y;             // input range of this block's outputs
-    const int span = s1 - s0, valid = min(s1, Cin) - s0;                  // a band wider than the axis reads zeros beyond it
+    const int s0 = MIT ? blk[blockIdx.x].x & ~3 : blk[blockIdx.x].x, s1 = blk[blockIdx.x].y;   // input range of this block's outputs
     const int off = start[cl] - s0;
     float w[WMAX];
 #pragma unroll
     for (int k = 0; k < WMAX; ++k) w[k] = k < W ? wT[(int64_t)k * Cout + cl] : 0.f;
     const int r_begin = blockIdx.y * rows_per_block, r_end = min(R, r_begin + rows_per_block);
     for (int i0 = r_begin; i0 < r_end; i0 += RG) {
-        __syncthreads();
+        if constexpr (MIT != 0) {
+            const int n4 = (s1 - s0 + 3) >> 2;                             // float4 per row (<= 64 * MIT, checked by the host)
+            Stage16<MIT> rows;
+            rows.fetch(in, Cin, s0, n4, i0, R - 1);
+            __syncthreads();                                               // the previous round's reads are done
+            rows.template commit<false>(sdet, span_ld, s0, n4, Cin);
+        } else {
+            const int span = s1 - s0, valid = min(s1, Cin) - s0;           // a band wider than the axis reads zeros beyond it
+            __syncthreads();
 #pragma unroll
-        for (int rr = 0; rr < RG; ++rr) {
-            const int i = min(i0 + rr, R - 1);
-            const float *row = in + (int64_t)i * Cin + s0;
-            for (int t = threadIdx.x; t < span; t += 256) sdet[rr * span_ld + t] = t < valid ? row[t] : 0.f;
+            for (int rr = 0; rr < RG; ++rr) {
+                const int i = min(i0 + rr, R - 1);
+                const float *row = in + (int64_t)i * Cin + s0;
+                for (int t = threadIdx.x; t < span; t += 256) sdet[rr * span_ld + t] = t < valid ? row[t] : 0.f;
+            }
         }
         __syncthreads();
         if (live) {
@@ -199,65 +263,6 @@ __global__ __launch_bounds__(256) void k_band_cols(const float *__restrict__ in,
 #pragma unroll
                     for (int k = 0; k < WMAX; ++k)
                         if (k < W) acc = fmaf(w[k], x[k], acc);     // off + k < span for every k < W by construction
-                    out[(int64_t)(i0 + rr) * Cout + c] = acc;
-                }
-            }
-        }
-    }
-}
-
-// The same with 16-byte staging loads, for rows that are 16-byte aligned (Cin % 4 == 0, aligned base) and spans of at most
-// 64 * MIT float4 per row: wave v of the workgroup stages rows v, v+4 of the round; all of a thread's loads (2 rows x MIT
-// float4) are issued before the first LDS write, so ~10 KB per wave are in flight.
-template <int WMAX, int MIT>
-__global__ __launch_bounds__(256) void k_band_cols_v4(const float *__restrict__ in, float *__restrict__ out,
-                                                      const int *__restrict__ start, const int2 *__restrict__ blk,
-                                                      const float *__restrict__ wT, int R, int Cin, int Cout, int W,
-                                                      int span_ld, int rows_per_block) {
-    constexpr int RG = 8;
-    extern __shared__ __attribute__((aligned(16))) float sdet[];     // [RG][span_ld], span_ld % 4 == 0
-    const int c0 = blockIdx.x * 256, c = c0 + threadIdx.x;
-    const bool live = c < Cout;
-    const int cl = live ? c : Cout - 1;
-    const int s0 = blk[blockIdx.x].x & ~3, s1 = blk[blockIdx.x].y;
-    const int n4 = (s1 - s0 + 3) >> 2;                                 // float4 per row (<= 64 * MIT, checked by the host)
-    const int off = start[cl] - s0;
-    float w[WMAX];
-#pragma unroll
-    for (int k = 0; k < WMAX; ++k) w[k] = k < W ? wT[(int64_t)k * Cout + cl] : 0.f;
-    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    const int r_begin = blockIdx.y * rows_per_block, r_end = min(R, r_begin + rows_per_block);
-    for (int i0 = r_begin; i0 < r_end; i0 += RG) {
-        float4 v[2][MIT];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int i = min(i0 + wv + 4 * h, R - 1);
-            const float4 *row = reinterpret_cast<const float4 *>(in + (int64_t)i * Cin + s0);
-#pragma unroll
-            for (int m = 0; m < MIT; ++m) {
-                const int t4 = ln + 64 * m;
-                // a float4 of an aligned row lies wholly inside or wholly outside it; beyond the row: zeros (a band wider than the axis)
-                v[h][m] = (t4 < n4 && s0 + 4 * t4 < Cin) ? row[t4] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-        __syncthreads();                                               // the previous round's reads are done
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int m = 0; m < MIT; ++m) {
-                const int t4 = ln + 64 * m;
-                if (t4 < n4) *reinterpret_cast<float4 *>(sdet + (wv + 4 * h) * span_ld + 4 * t4) = v[h][m];
-            }
-        __syncthreads();
-        if (live) {
-#pragma unroll
-            for (int rr = 0; rr < RG; ++rr) {
-                if (i0 + rr < r_end) {
-                    const float *x = sdet + rr * span_ld + off;
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < WMAX; ++k)
-                        if (k < W) acc = fmaf(w[k], x[k], acc);
                     out[(int64_t)(i0 + rr) * Cout + c] = acc;
                 }
             }
@@ -318,8 +323,6 @@ __global__ __launch_bounds__(256) void k_band_rows(const float *__restrict__ in,
 // combines them -- the intermediate image of the two-pass form (34 MB written and read again per 4096^2 image for the front
 // pair, 17 MB for the PSF pair) never exists.  Tiles are walked by a grid-stride loop (column blocks of a row tile are
 // neighbours in the walk: they share input rows in L2).
-constexpr int PAIR_MIT = 5;      // float4 per lane and staged row: spans up to 1280 floats
-
 struct PairArgs {
     const float *in[PSX_MAX_DETECT];   // blockIdx.z = image of the launch (psx_detect_multi_f32: the images of one energy bin)
     float *out[PSX_MAX_DETECT];
@@ -337,12 +340,11 @@ struct PairArgs {
 
 template <int WC, int MIT>
 __global__ __launch_bounds__(256) void k_band_pair(PairArgs a) {
-    constexpr int H = 2, RG = 4 * H;                                 // two rows per wave and round
+    constexpr int RG = 8;                                            // two rows per wave and round
     extern __shared__ __attribute__((aligned(16))) float sdet[];     // stage [RG][span_ld] | mid [mid_rows][256] | wsh [RT][r_W] | ssh [RT]
     float *mid = sdet + RG * a.span_ld;
     float *wsh = mid + a.mid_rows * 256;
     int *ssh = reinterpret_cast<int *>(wsh + a.RT * a.r_W);
-    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     const float *const img_in = a.in[blockIdx.z];
     float *const img_out = a.out[blockIdx.z];
     // a workgroup keeps its column block: the column's weights and the staged span are set up once
@@ -369,20 +371,7 @@ __global__ __launch_bounds__(256) void k_band_pair(PairArgs a) {
     // it (with zero weights): make it zeros once (stale LDS could hold NaN bit patterns)
     for (int rr = 0; rr < RG; ++rr)
         for (int t = 4 * n4 + (int)threadIdx.x; t < a.span_ld; t += 256) sdet[rr * a.span_ld + t] = 0.f;
-    float4 v[H][MIT];
-    auto fetch = [&](int i0, int ihi) __attribute__((always_inline)) {
-#pragma unroll
-        for (int h = 0; h < H; ++h) {
-            const int i = min(i0 + wv + 4 * h, ihi - 1);
-            const float4 *row = reinterpret_cast<const float4 *>(img_in + (int64_t)i * a.in_pitch + s0);
-#pragma unroll
-            for (int m = 0; m < MIT; ++m) {
-                const int t4 = ln + 64 * m;
-                // rows are padded to whole float4s (in_pitch % 4 == 0); beyond the axis: zeros (a band wider than the axis)
-                v[h][m] = (t4 < n4 && s0 + 4 * t4 < a.in_pitch) ? row[t4] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-    };
+    Stage16<MIT> rows;
     for (int rt = blockIdx.y; rt < a.n_rtiles; rt += gridDim.y) {
         const int ilo = a.r_tile[rt].x, ihi = a.r_tile[rt].y;
         const int r0 = rt * a.RT, r1 = min(a.Rout, r0 + a.RT);
@@ -391,32 +380,16 @@ __global__ __launch_bounds__(256) void k_band_pair(PairArgs a) {
         int spre = 0;
         if ((int)threadIdx.x < (r1 - r0) * a.r_W) wpre = a.r_w[(int64_t)r0 * a.r_W + threadIdx.x];
         if ((int)threadIdx.x < r1 - r0) spre = a.r_start[r0 + threadIdx.x];
-        fetch(ilo, ihi);
+        rows.fetch(img_in, a.in_pitch, s0, n4, ilo, ihi - 1);
         for (int i0 = ilo; i0 < ihi; i0 += RG) {
             __syncthreads();                                           // the previous round's (and tile's) reads are done
             if (i0 == ilo) {
                 if ((int)threadIdx.x < a.RT * a.r_W) wsh[threadIdx.x] = wpre;
                 if ((int)threadIdx.x < a.RT) ssh[threadIdx.x] = spre;
             }
-#pragma unroll
-            for (int h = 0; h < H; ++h)
-#pragma unroll
-                for (int m = 0; m < MIT; ++m) {
-                    const int t4 = ln + 64 * m;
-                    if (t4 < n4) {
-                        float4 x = v[h][m];
-                        const int e = s0 + 4 * t4;                     // columns at and beyond Cin are pitch padding, not data
-                        if (e + 3 >= a.Cin) {
-                            x.x = e < a.Cin ? x.x : 0.f;
-                            x.y = e + 1 < a.Cin ? x.y : 0.f;
-                            x.z = e + 2 < a.Cin ? x.z : 0.f;
-                            x.w = 0.f;
-                        }
-                        *reinterpret_cast<float4 *>(sdet + (wv + 4 * h) * a.span_ld + 4 * t4) = x;
-                    }
-                }
+            rows.template commit<true>(sdet, a.span_ld, s0, n4, a.Cin);
             __syncthreads();
-            if (i0 + RG < ihi) fetch(i0 + RG, ihi);                    // the next round's rows fly during this round's arithmetic
+            if (i0 + RG < ihi) rows.fetch(img_in, a.in_pitch, s0, n4, i0 + RG, ihi - 1);   // the next round's rows fly during this round's arithmetic
 #pragma unroll
             for (int rr = 0; rr < RG; ++rr) {
                 if (i0 + rr < ihi) {
@@ -464,6 +437,16 @@ struct PsfArgs {
     int in_pitch, out_pitch, Rin, Cin, Rout, Cout, ox, oy;
     float gx[20], gy[20];
 };
+
+// the images of a launch (blockIdx.z) and their row pitches, for PairArgs and PsfArgs
+template <class Args>
+void set_images(Args &a, const float *const *in, int in_pitch, float *const *out, int out_pitch, int nimg) {
+    for (int k = 0; k < PSX_MAX_DETECT; ++k) {
+        a.in[k] = in[std::min(k, nimg - 1)];
+        a.out[k] = out[std::min(k, nimg - 1)];
+    }
+    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
+}
 
 // output rows per workgroup (session r5s71: 16 -> 25 KB of LDS, six workgroups per CU: 0.0270 against 0.0287 ms with 32)
 constexpr int PSF_TR = 16;
@@ -902,10 +885,7 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
     std::unique_ptr<psx_detector_plan> p(new psx_detector_plan());
     p->Nx = Nx; p->Ny = Ny; p->ov = ov; p->nx = nx; p->ny = ny; p->margin = margin;
     int rc = 0;
-    auto up = [&](auto &dst, const auto &src) -> int {      // a host vector into its device buffer
-        p->bytes += sizeof(src[0]) * src.size();
-        return dst.upload(src.data(), src.size());
-    };
+    auto up = [](auto &dst, const auto &src) -> int { return dst.upload(src.data(), src.size()); };   // a host vector into its device buffer
     auto build = [&](BandOp &op, int N, int n, int stage) -> int {
         std::vector<int> st;
         std::vector<float> w;
@@ -933,6 +913,7 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
             blk.push_back(make_int2(lo, hi + op.W));
             op.span = std::max(op.span, hi + op.W - lo);
         }
+        op.stage16 = op.n_in % 4 == 0 && op.span + 3 + 3 <= 4 * 64 * STAGE_MIT && op.W <= 64;
         if (int e = up(op.blk, blk)) return e;
         if (int e = up(op.start, st)) return e;
         if (int e = up(op.w, w)) return e;
@@ -943,18 +924,14 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
     if (!rc) rc = build(p->fy, Ny, ny, psf ? STAGE_FRONT : STAGE_ALL);
     if (!rc && psf) rc = build(p->bx, Nx, nx, STAGE_BACK);
     if (!rc && psf) rc = build(p->by, Ny, ny, STAGE_BACK);
-    auto scratch = [&](DevBuf<float> &dst, size_t elems) -> int {
-        p->bytes += sizeof(float) * elems;
-        return dst.alloc(elems);
-    };
-    if (!rc) rc = scratch(p->t1, (size_t)Nx * (size_t)p->fy.n_out);
-    if (!rc && psf) rc = scratch(p->t2, (size_t)p->fx.n_out * (size_t)p->fy.n_out);
-    if (!rc && psf) rc = scratch(p->t3, (size_t)p->fx.n_out * (size_t)ny);
+    p->psf_stencil = psf && p->bx.stencil && p->by.stencil && p->bx.W <= 17 && p->by.W <= 17;
+    if (!rc) rc = p->t1.alloc((size_t)Nx * (size_t)p->fy.n_out);
+    if (!rc && psf) rc = p->t3.alloc((size_t)p->fx.n_out * (size_t)ny);
     // the fused (contiguous axis, axis 0) pairs: tiles of RT output rows, the largest RT whose LDS footprint leaves four
     // workgroups per CU; a geometry that does not fit (very wide bands) keeps the four-pass form
     auto pair = [&](BandPair &pr, const BandOp &C, const BandOp &R) -> int {
         pr.ok = false;
-        if (C.W > 16 || C.span + 3 + 3 > 4 * 64 * PAIR_MIT) return 0;
+        if (C.W > 16 || C.span + 3 + 3 > 4 * 64 * STAGE_MIT) return 0;
         pr.span_ld = (C.span + 3 + 24) / 4 * 4;      // + alignment slack of the block's first input + the aligned tap reads' overshoot
         for (int RT : {16, 8, 4}) {
             std::vector<int2> tiles;
@@ -985,7 +962,7 @@ int psx_detector_plan_create(int Nx, int Ny, int ov, int nx, int ny, int margin,
     if (!rc) rc = pair(p->front, p->fy, p->fx);
     if (!rc && psf) rc = pair(p->back, p->by, p->bx);
     p->pitch2 = (p->fy.n_out + 3) / 4 * 4;
-    if (!rc && psf && p->back.ok) rc = scratch(p->t2p, (size_t)PSX_MAX_DETECT * (size_t)p->fx.n_out * (size_t)p->pitch2);
+    if (!rc && psf) rc = p->t2.alloc((size_t)(p->back.ok ? PSX_MAX_DETECT : 1) * (size_t)p->fx.n_out * (size_t)p->pitch2);
     if (rc) return rc;
     *plan = p.release();
     return 0;
@@ -1035,41 +1012,30 @@ int strip_rows(int rows, int col_blocks) {
 }
 
 int band_cols(const BandOp &op, const float *in, float *out, int R, hipStream_t st) {
-    // 16-byte staging when the rows allow it (the full-resolution pass always does for even grids)
-    constexpr int MIT = 5;
-    if (op.n_in % 4 == 0 && (uintptr_t)in % 16 == 0 && op.span + 3 + 3 <= 4 * 64 * MIT && op.W <= 64) {
-        constexpr int RG8 = 8;
-        const int cb = (op.n_out + 255) / 256;
-        const int per = (strip_rows(R, cb) + RG8 - 1) / RG8 * RG8;
-        const dim3 grid(cb, (R + per - 1) / per);
-        const int span_ld = (op.span + 3 + 3 + 4) / 4 * 4;      // + alignment slack of the block's first input, whole float4s
-        const size_t lds = sizeof(float) * RG8 * (size_t)span_ld;
-#define PSX_BAND_COLS_V4(WMAX)                                                                                          \
-    PSX_TIMED("k_band_cols", st, k_band_cols_v4<WMAX, MIT><<<grid, 256, lds, st>>>(in, out, op.start.get(), op.blk.get(), op.wT.get(), R, \
-                                                                                     op.n_in, op.n_out, op.W, span_ld, per))
-        if (op.W <= 8) PSX_BAND_COLS_V4(8);
-        else if (op.W <= 16) PSX_BAND_COLS_V4(16);
-        else if (op.W <= 32) PSX_BAND_COLS_V4(32);
-        else PSX_BAND_COLS_V4(64);
-#undef PSX_BAND_COLS_V4
-        return launch_check("k_band_cols");
-    }
-    constexpr int RG = 4;
+    const bool v4 = op.stage16 && (uintptr_t)in % 16 == 0;      // 16-byte staging when the rows allow it: eight rows a round
+    const int RG = v4 ? 8 : 4;
     const int cb = (op.n_out + 255) / 256;
     const int per = (strip_rows(R, cb) + RG - 1) / RG * RG;
     const dim3 grid(cb, (R + per - 1) / per);
-    const int span_ld = op.span + 1;
+    // 16-byte staging: + alignment slack of the block's first input, whole float4s
+    const int span_ld = v4 ? (op.span + 3 + 3 + 4) / 4 * 4 : op.span + 1;
     const size_t lds = sizeof(float) * RG * (size_t)span_ld;
     PSX_REQUIRE(lds <= 64 * 1024, "detector: oversampling %d needs %zu bytes of LDS per row strip", op.span / 256, lds);
-#define PSX_BAND_COLS(WMAX)                                                                                            \
-    PSX_TIMED("k_band_cols", st, k_band_cols<WMAX, RG><<<grid, 256, lds, st>>>(in, out, op.start.get(), op.blk.get(), op.wT.get(), R, op.n_in, \
-                                                                                 op.n_out, op.W, span_ld, per))
-    if (op.W <= 8) PSX_BAND_COLS(8);
-    else if (op.W <= 16) PSX_BAND_COLS(16);
-    else if (op.W <= 32) PSX_BAND_COLS(32);
-    else if (op.W <= 64) PSX_BAND_COLS(64);
-    else if (op.W <= 128) PSX_BAND_COLS(128);
+#define PSX_BAND_COLS(WMAX, MIT)                                                                                        \
+    PSX_TIMED("k_band_cols", st, k_band_cols<WMAX, MIT><<<grid, 256, lds, st>>>(in, out, op.start.get(), op.blk.get(), op.wT.get(), R, op.n_in, \
+                                                                                  op.n_out, op.W, span_ld, per))
+#define PSX_BAND_COLS_EITHER(WMAX)                 \
+    do {                                           \
+        if (v4) PSX_BAND_COLS(WMAX, STAGE_MIT);    \
+        else PSX_BAND_COLS(WMAX, 0);               \
+    } while (0)
+    if (op.W <= 8) PSX_BAND_COLS_EITHER(8);
+    else if (op.W <= 16) PSX_BAND_COLS_EITHER(16);
+    else if (op.W <= 32) PSX_BAND_COLS_EITHER(32);
+    else if (op.W <= 64) PSX_BAND_COLS_EITHER(64);
+    else if (op.W <= 128) PSX_BAND_COLS(128, 0);                // stage16 holds no band of more than 64 taps
     else return fail(PSX_E_UNSUPPORTED, "detector: band of %d taps (source blur of more than 60 study pixels?)", op.W);
+#undef PSX_BAND_COLS_EITHER
 #undef PSX_BAND_COLS
     return launch_check("k_band_cols");
 }
@@ -1089,18 +1055,10 @@ int band_rows(const BandOp &op, const float *in, float *out, int C, hipStream_t 
     return launch_check("k_band_rows");
 }
 
-}  // namespace
-
-namespace {
-
 int band_pair(const BandPair &pr, const BandOp &C, const BandOp &R, const float *const *in, int in_pitch, float *const *out,
               int out_pitch, int nimg, hipStream_t st) {
     PairArgs a;
-    for (int k = 0; k < PSX_MAX_DETECT; ++k) {
-        a.in[k] = in[std::min(k, nimg - 1)];
-        a.out[k] = out[std::min(k, nimg - 1)];
-    }
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
+    set_images(a, in, in_pitch, out, out_pitch, nimg);
     a.c_start = C.start.get(); a.c_blk = C.blk.get(); a.c_wT = C.wT.get(); a.c_W = C.W; a.Cin = C.n_in; a.Cout = C.n_out;
     a.r_start = R.start.get(); a.r_w = R.w.get(); a.r_W = R.W; a.Rin = R.n_in; a.Rout = R.n_out;
     a.r_tile = pr.r_tile.get(); a.RT = pr.RT; a.n_rtiles = pr.n_rtiles; a.span_ld = pr.span_ld; a.mid_rows = pr.mid_rows;
@@ -1112,24 +1070,17 @@ int band_pair(const BandPair &pr, const BandOp &C, const BandOp &R, const float 
     const dim3 grid(cb, strips, nimg);
     // the column operator's taps sit in registers, a float4 of them per aligned LDS read: as few as the band needs (a plain
     // ov = 2 binning has 2 taps, the usual PSF 9: two reads instead of three, four instead of five)
-    if (C.W <= 4) PSX_TIMED("k_band_pair", st, k_band_pair<4, PAIR_MIT><<<grid, 256, pr.lds, st>>>(a));
-    else if (C.W <= 8) PSX_TIMED("k_band_pair", st, k_band_pair<8, PAIR_MIT><<<grid, 256, pr.lds, st>>>(a));
-    else if (C.W <= 12) PSX_TIMED("k_band_pair", st, k_band_pair<12, PAIR_MIT><<<grid, 256, pr.lds, st>>>(a));
-    else PSX_TIMED("k_band_pair", st, k_band_pair<16, PAIR_MIT><<<grid, 256, pr.lds, st>>>(a));
+    if (C.W <= 4) PSX_TIMED("k_band_pair", st, k_band_pair<4, STAGE_MIT><<<grid, 256, pr.lds, st>>>(a));
+    else if (C.W <= 8) PSX_TIMED("k_band_pair", st, k_band_pair<8, STAGE_MIT><<<grid, 256, pr.lds, st>>>(a));
+    else if (C.W <= 12) PSX_TIMED("k_band_pair", st, k_band_pair<12, STAGE_MIT><<<grid, 256, pr.lds, st>>>(a));
+    else PSX_TIMED("k_band_pair", st, k_band_pair<16, STAGE_MIT><<<grid, 256, pr.lds, st>>>(a));
     return launch_check("k_band_pair");
 }
-
-// the PSF stage as a stencil (k_psf_tile): both back operators plain convolutions of at most 17 taps
-bool psf_stencil_ok(const BandOp &C, const BandOp &R) { return C.stencil && R.stencil && C.W <= 17 && R.W <= 17; }
 
 int psf_tile(const BandOp &C, const BandOp &R, const float *const *in, int in_pitch, float *const *out, int out_pitch, int nimg,
              hipStream_t st) {
     PsfArgs a = {};
-    for (int k = 0; k < PSX_MAX_DETECT; ++k) {
-        a.in[k] = in[std::min(k, nimg - 1)];
-        a.out[k] = out[std::min(k, nimg - 1)];
-    }
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
+    set_images(a, in, in_pitch, out, out_pitch, nimg);
     a.Rin = R.n_in; a.Cin = C.n_in; a.Rout = R.n_out; a.Cout = C.n_out; a.ox = R.h_start[0]; a.oy = C.h_start[0];
     for (int k = 0; k < R.W; ++k) a.gx[k] = R.h_w0[k];
     for (int l = 0; l < C.W; ++l) a.gy[l] = C.h_w0[l];
@@ -1141,7 +1092,29 @@ int psf_tile(const BandOp &C, const BandOp &R, const float *const *in, int in_pi
     return launch_check("k_psf_tile");
 }
 
-bool four_pass_forced() { return debug_switch(DBG_DETECT_4PASS) != 0; }   // diagnostics (psx_debug_switch "detect_4pass")
+// the form each stage of a call runs in
+struct Route {
+    enum { FRONT_PAIR, FRONT_TWO_PASS } front;
+    enum { BACK_NONE, BACK_STENCIL, BACK_PAIR, BACK_TWO_PASS } back;
+    bool back_fused() const { return back == BACK_STENCIL || back == BACK_PAIR; }
+    // the images of a call go through each launch together (grid.z); a two-pass stage takes them one by one
+    bool shared() const { return front == FRONT_PAIR && back != BACK_TWO_PASS; }
+};
+
+// Each stage as ONE fused pass (k_band_pair) where that moves fewer bytes: the front stage when the image rows are 16-byte
+// aligned, the bands fit its tiles and the tiles' halos are small (a wide source blur makes an 8-row tile re-read half
+// its rows: two passes are cheaper then); the PSF stage whenever its bands fit -- it reads the front stage's result at a
+// 16-byte row pitch, which the two-pass front can only write when the row length is a multiple of 4 anyway.
+// aligned: EVERY image of the call is 16-byte aligned; four_pass: diagnostics (psx_debug_switch "detect_4pass").
+Route route(const psx_detector_plan &p, bool aligned, bool four_pass) {
+    Route r = {Route::FRONT_TWO_PASS, Route::BACK_NONE};
+    if (!four_pass && p.front.ok && p.front.cheap && p.Ny % 4 == 0 && aligned) r.front = Route::FRONT_PAIR;
+    if (p.bx.n_out != 0) {
+        const bool fused = !four_pass && p.back.ok && (r.front == Route::FRONT_PAIR || p.pitch2 == p.fy.n_out);
+        r.back = !fused ? Route::BACK_TWO_PASS : p.psf_stencil ? Route::BACK_STENCIL : Route::BACK_PAIR;
+    }
+    return r;
+}
 
 }  // namespace
 
@@ -1149,49 +1122,45 @@ bool four_pass_forced() { return debug_switch(DBG_DETECT_4PASS) != 0; }   // dia
 // (grid.z): a 4096^2 -> 2048^2 detection is two launches of 20-25 us whose set-up, first fetch and tail are a good part of
 // them, and an energy bin always detects two to four images.  Image k is computed exactly as a call of its own would.
 static int detect_impl(psx_detector_plan *p, const float *const *imgs, float *const *outs, int nimg, hipStream_t st) {
-    const bool psf = p->bx.n_out != 0;
-    // Each stage as ONE fused pass (k_band_pair) where that moves fewer bytes: the front stage when the image rows are 16-byte
-    // aligned, the bands fit its tiles and the tiles' halos are small (a wide source blur makes an 8-row tile re-read half
-    // its rows: two passes are cheaper then); the PSF stage whenever its bands fit -- it reads the front stage's result at a
-    // 16-byte row pitch, which the two-pass front can only write when the row length is a multiple of 4 anyway.
-    const bool allowed = !four_pass_forced();
     bool aligned = true;
     for (int k = 0; k < nimg; ++k) aligned = aligned && (uintptr_t)imgs[k] % 16 == 0;
-    const bool front_f = allowed && p->front.ok && p->front.cheap && p->Ny % 4 == 0 && aligned;
-    const bool back_f = allowed && psf && p->back.ok && p->t2p && (front_f || p->pitch2 == p->fy.n_out);
-    if (nimg > 1 && front_f && (back_f || !psf)) {
-        float *mids[PSX_MAX_DETECT];
-        for (int k = 0; k < nimg; ++k) mids[k] = p->t2p.get() + (size_t)k * p->fx.n_out * p->pitch2;
-        if (!psf) return band_pair(p->front, p->fy, p->fx, imgs, p->Ny, outs, p->fy.n_out, nimg, st);
-        if (int rc = band_pair(p->front, p->fy, p->fx, imgs, p->Ny, mids, p->pitch2, nimg, st)) return rc;
-        if (psf_stencil_ok(p->by, p->bx)) return psf_tile(p->by, p->bx, mids, p->pitch2, outs, p->ny, nimg, st);
-        return band_pair(p->back, p->by, p->bx, mids, p->pitch2, outs, p->ny, nimg, st);
-    }
-    for (int k = 0; k < nimg; ++k) {
-        const float *img = imgs[k];
-        float *out = outs[k];
-        float *mid_img = back_f ? p->t2p.get() : p->t2.get();
-        const int mid_pitch = back_f ? p->pitch2 : p->fy.n_out;
-        float *front_out = psf ? mid_img : out;
-        if (front_f) {
-            if (int rc = band_pair(p->front, p->fy, p->fx, &img, p->Ny, &front_out, psf ? mid_pitch : p->fy.n_out, 1, st)) return rc;
-        } else {
-            // contiguous axis first (the only pass over the full-resolution image), then axis 0
-            if (int rc = band_cols(p->fy, img, p->t1.get(), p->Nx, st)) return rc;
-            if (int rc = band_rows(p->fx, p->t1.get(), front_out, p->fy.n_out, st)) return rc;
+    const Route rt = route(*p, aligned, debug_switch(DBG_DETECT_4PASS) != 0);
+    const int group = rt.shared() ? nimg : 1;
+    const int mid_pitch = rt.back_fused() ? p->pitch2 : p->fy.n_out;
+    for (int k0 = 0; k0 < nimg; k0 += group) {
+        const float *const *in = imgs + k0;
+        float *const *out = outs + k0;
+        float *mids[PSX_MAX_DETECT] = {};       // image k of the group in slot k of t2
+        if (rt.back != Route::BACK_NONE)
+            for (int k = 0; k < group; ++k) mids[k] = p->t2.get() + (size_t)k * p->fx.n_out * p->pitch2;
+        float *const *front_out = rt.back == Route::BACK_NONE ? out : mids;
+        const int front_pitch = rt.back == Route::BACK_NONE ? p->fy.n_out : mid_pitch;
+        int rc = 0;
+        switch (rt.front) {
+        case Route::FRONT_PAIR:
+            rc = band_pair(p->front, p->fy, p->fx, in, p->Ny, front_out, front_pitch, group, st);
+            break;
+        case Route::FRONT_TWO_PASS:     // contiguous axis first (the only pass over the full-resolution image), then axis 0
+            rc = band_cols(p->fy, in[0], p->t1.get(), p->Nx, st);
+            if (!rc) rc = band_rows(p->fx, p->t1.get(), front_out[0], p->fy.n_out, st);
+            break;
         }
-        if (!psf) continue;
-        // back operator (PSF + crop) at detector resolution
-        if (back_f) {
-            if (psf_stencil_ok(p->by, p->bx)) {
-                if (int rc = psf_tile(p->by, p->bx, &mid_img, mid_pitch, &out, p->ny, 1, st)) return rc;
-            } else if (int rc = band_pair(p->back, p->by, p->bx, &mid_img, mid_pitch, &out, p->ny, 1, st)) {
-                return rc;
-            }
-            continue;
+        if (rc) return rc;
+        switch (rt.back) {              // back operator (PSF + crop) at detector resolution
+        case Route::BACK_NONE:
+            break;
+        case Route::BACK_STENCIL:
+            rc = psf_tile(p->by, p->bx, mids, mid_pitch, out, p->ny, group, st);
+            break;
+        case Route::BACK_PAIR:
+            rc = band_pair(p->back, p->by, p->bx, mids, mid_pitch, out, p->ny, group, st);
+            break;
+        case Route::BACK_TWO_PASS:
+            rc = band_cols(p->by, mids[0], p->t3.get(), p->fx.n_out, st);
+            if (!rc) rc = band_rows(p->bx, p->t3.get(), out[0], p->ny, st);
+            break;
         }
-        if (int rc = band_cols(p->by, p->t2.get(), p->t3.get(), p->fx.n_out, st)) return rc;
-        if (int rc = band_rows(p->bx, p->t3.get(), out, p->ny, st)) return rc;
+        if (rc) return rc;
     }
     return 0;
 }

@@ -303,7 +303,8 @@ assert set(MANY) <= set(CASES)
 @pytest.mark.parametrize("c", MANY, ids=ident)
 def test_images_of_a_call_are_each_the_single_detection(ops, c):
     """detect_many of 2, 4 and 5 images (5: two calls) is bit for bit detect of each alone -- in one launch per fused stage
-    where both stages are fused, one by one elsewhere, and one by one when an image of the call is not 16-byte aligned."""
+    where both stages are fused, one by one elsewhere, and one by one when an image of the call is not 16-byte aligned (the
+    launches of that call are the three images' own: `dispatch` for a misaligned image, times three)."""
     Nx, Ny, ov, fwhm, psf, margin, _ = c
     plan = ops.DetectorPlan(Nx, Ny, ov, Nx // ov, Ny // ov, fwhm / 2.355, psf, margin=margin)
     info = plan.info()
@@ -323,7 +324,15 @@ def test_images_of_a_call_are_each_the_single_detection(ops, c):
             assert torch.equal(outs[k], single[k]), (ident(c), n, k)
     mis = shifted(imgs[1].cpu().numpy(), 1)
     outs = [torch.full_like(single[0], -1.0) for _ in range(3)]
-    res = plan.detect_many([imgs[0], mis, imgs[2]], outs)
+    # one misaligned image decides for the call: every image takes the two-pass front on its own (no k_band_pair for the
+    # front stage), then its own back stage -- two passes, or one k_psf_tile / k_band_pair launch per image, never shared
+    front_m, back_m, one = dispatch(info, c[:6] + (1,), False)
+    assert front_m[0].startswith("cols") and one["k_band_cols"] == one["k_band_rows"] == (2 if back_m and back_m[0].startswith("cols") else 1)
+    assert one.get("k_band_pair", 0) + one.get("k_psf_tile", 0) == (1 if back_m and not back_m[0].startswith("cols") else 0)
+    res = []
+    got = profile_counts(lambda: res.extend(plan.detect_many([imgs[0], mis, imgs[2]], outs)))
+    got = {k: v for k, v in got.items() if k in ("k_band_cols", "k_band_rows", "k_band_pair", "k_psf_tile")}
+    assert got == {k: 3 * v for k, v in one.items()}, (ident(c), "misaligned", info, "launched", got, "one image", one)
     for k in range(3):
         assert res[k] is outs[k] and torch.equal(outs[k], single[k]), (ident(c), "misaligned", k)
     plan.close()

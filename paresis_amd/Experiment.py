@@ -14,6 +14,7 @@ What is different under the hood (MI355X-first, not a translation):
     the same inputs to this class and to the oracle.
 """
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -28,8 +29,13 @@ from .Source import Source
 
 
 def _rebased(base, rows):
-    """ops.MaterialBatch of cached coefficient rows (cphase rows, catt rows) over this position's maps."""
-    return ops.MaterialBatch(base, rows[0], rows[1])
+    """ops.MaterialBatch of cached coefficient rows (cphase rows, catt rows) over this position's maps; None without maps."""
+    return ops.MaterialBatch(base, rows[0], rows[1]) if base is not None else None
+
+
+def _at(base, rows, k):
+    """This position's maps under row k of cached coefficient rows: the stack of one energy of a bin."""
+    return base.with_coeffs(cphase=rows[0][k], catt=rows[1][k])
 
 
 class Experiment:
@@ -123,6 +129,7 @@ class Experiment:
         self._sums_pool, self._sums_next = None, 0
         self.darkFieldPropag = None
         self._df_tmp = None           # dark-field half of the fused sample hop
+        self._df_tab_cache = {}       # (energy, distance) -> what _df_tables derives from the width map
         self._zero_stack = None       # Propag / White of every position but 0
         self._halo = None             # refraction gather halo of this experiment (exp_dict['refractionHalo']: 4 | 6 | 8 | 'auto')
 
@@ -220,9 +227,9 @@ class Experiment:
             if type(darkField) == int or type(darkField) == float:
                 return fastRefraction(intensityRefracted, phi, propagationDistance, Energy, magnification,
                                       self.exp_dict["studyPixelSize"])
-            known = self.mySampleofInterest.dark_field_max(darkField) if hasattr(self.mySampleofInterest, "dark_field_max") else None
             return fastRefractionDF(intensityRefracted, phi, propagationDistance, Energy, magnification,
-                                    self.exp_dict["studyPixelSize"], darkField, darkFieldMax=known,
+                                    self.exp_dict["studyPixelSize"], darkField,
+                                    darkFieldMax=self.mySampleofInterest.dark_field_max(darkField),
                                     check=not self.exp_dict.get('deferStatus'), mutate=_mutate, want_D=_want_D)
 
     def _reproducible(self):
@@ -258,18 +265,13 @@ class Experiment:
         # handed -- main.run, which saves or packs every stack, the bench's position loop -- sets exp_dict['sharedZeroStacks']:
         # Propag and White of every position but 0 are then ONE zero stack per experiment, not 33 MB filled per position (10 us
         # at 2048^2 detectors, the kernel trace of gpurun_out/r5s36) and half the memory kept per position.
-        if pointNum != 0 and self.exp_dict.get('sharedZeroStacks', False):
-            if self._zero_stack is None or tuple(self._zero_stack.shape) != (nbins, n0, n1) or self._zero_stack.device != dev:
-                self._zero_stack = ops.fill(torch.empty((nbins, n0, n1), dtype=torch.float32, device=dev), 0.0)
-            two = torch.empty((2, nbins, n0, n1), dtype=torch.float32, device=dev)
-            out = [two[0], two[1], self._zero_stack, self._zero_stack]
-        elif pointNum != 0:
-            four = torch.empty((4, nbins, n0, n1), dtype=torch.float32, device=dev)
-            ops.fill(four[2:], 0.0)
-            out = [four[0], four[1], four[2], four[3]]
-        else:
-            four = torch.empty((4, nbins, n0, n1), dtype=torch.float32, device=dev)
-            out = [four[0], four[1], four[2], four[3]]
+        shared = pointNum != 0 and self.exp_dict.get('sharedZeroStacks', False)
+        if shared and (self._zero_stack is None or tuple(self._zero_stack.shape) != (nbins, n0, n1) or self._zero_stack.device != dev):
+            self._zero_stack = ops.fill(torch.empty((nbins, n0, n1), dtype=torch.float32, device=dev), 0.0)
+        own = torch.empty((2 if shared else 4, nbins, n0, n1), dtype=torch.float32, device=dev)
+        if pointNum != 0 and not shared:
+            ops.fill(own[2:], 0.0)
+        out = [own[0], own[1]] + ([self._zero_stack] * 2 if shared else [own[2], own[3]])
         N = tuple(int(v) for v in self.exp_dict['studyDimensions'])
         # the four study-grid accumulators live as long as the experiment; the first energy of a bin STORES into them, so they
         # are never cleared (the reference re-allocates zeros after every bin, EXP:396-399)
@@ -337,13 +339,24 @@ class Experiment:
         ed = self.exp_dict
         return self.mySource.source_dict["mySize"] * ed['distObjectToDetector'] / (ed['distSourceToMembrane'] + ed['distMembraneToObject']) / self.myDetector.det_param['myPixelSize'] * ed['overSampling']   # EXP:380
 
-    def _zero_unvisited_bins(self, stacks, nvisited, pointNum):
-        """Bins no energy ever closed (thresholds denser than the spectrum) stay all-zero in the reference (np.zeros,
+    def _finish(self, sim, pointNum, stacks, nvisited, sums, N):
+        """The end of a position, whichever form its energies took: unvisited bins, status word (RT), mean energy, the tuple
+        the reference returns (EXP:403-405 / 523-526).
+
+        Bins no energy ever closed (thresholds denser than the spectrum) stay all-zero in the reference (np.zeros,
         EXP:302-305); the stacks here are uninitialised memory until a bin's detection writes them."""
-        nbins = stacks[0].shape[0]
-        if nvisited < nbins:
+        ed = self.exp_dict
+        if nvisited < stacks[0].shape[0]:
             for k in ((0, 1, 2, 3) if pointNum == 0 else (0, 1)):
                 ops.fill(stacks[k][nvisited:], 0.0)
+        if sim == "RT" and not ed.get('deferStatus'):
+            ops.check_status(stacks[0].device, "computeSampleAndReferenceImages_RT")       # RF2:81-82, checked once
+        self._finish_mean_energy(sums, N[0] * N[1])
+        if sim == "Fresnel":
+            return tuple(stacks)
+        if not ed.get('deferMeanEnergy'):
+            print("Mean detected energy in reference image", ed['meanEnergy'])
+        return stacks[0], stacks[1], stacks[2], stacks[3], self.Dxreal, self.Dyreal, self.darkFieldPropag
 
     def _detect_bin(self, ibin, pointNum, stacks, accs):
         """EXP:378-401 / 501-521: detection of the accumulated images of one energy bin.  The detector operator writes
@@ -354,14 +367,68 @@ class Experiment:
         self.myDetector.detect_many([accs[k] for k in kinds], ess, self.exp_dict, [stacks[k][ibin] for k in kinds],
                                     [(pointNum, ibin, k) for k in kinds])
 
-    # -------------------------------------------------------------------------------------- Fresnel chain
-    def _add_intensity(self, acc, img, plate_att, add=True):
-        """acc (+)= img * plate attenuation (EXP:351-358); img is left untouched."""
-        ops.accumulate(acc, img, 1.0, plate_att, add=add)
+    # ------------------------------------------------------------------------------ what both chains share
+    def _hops(self, sim, ie, E, flux, pointNum):
+        """THE statement of a chain's hops for one energy (EXP:320-349 Fresnel, EXP:456-474 ray tracing): the incident
+        intensity, the material stack each hop sees, by name, and the magnification and distance each hop uses, as the scalars
+        its kernel takes.  The per-energy loops read it as it is, _bin_tables reduces it to coefficient rows per bin.
 
-    def _white(self, white, I_scalar, air_rt, plate_att, first):
+        stacks: "mem" the membrane exit (air + membrane), "plate" the plate's attenuation (None without a plate) and, at
+        position 0 only (a stack of more than PSX_MAX_MAT maps costs a fold where it is built), "propag" the sample without
+        the membrane (air + sample) and "white" the flat field (air + plate attenuation);
+          Fresnel: "smp" the sample alone; the first hop at the LOCAL magnification (EXP:340), the other two at the total one:
+                   (aA, gA) membrane -> sample plane and -> detector, (aB, gB) sample -> detector, du; amp = sqrt(I0) (EXP:334);
+          RT:      "mem_phase" the membrane's phase only (EXP:474), "both" that phase + the sample (EXP:469-473); the total
+                   magnification M on every hop (_dscale): dsMO membrane -> sample, dsOD sample -> detector over the distance
+                   zOD (the dark-field hop and Experiment.refraction take distance and magnification, not the scale)."""
+        ed = self.exp_dict
+        concat = ops.MaterialStack.concat
+        dSM, dMO, dOD, M = ed['distSourceToMembrane'], ed['distMembraneToObject'], ed['distObjectToDetector'], ed['magnification']
+        air, plate = (None if ed['inVacuum'] else self.myAirVolume), self.myPlate
+        air_att = air.stack_rt(E, phase=False) if air is not None else None
+        h = SimpleNamespace(E=E, I0=self._incident(flux, E, ie))
+        if sim == "Fresnel":
+            h.amp = float(np.sqrt(h.I0))
+            air_w = air.stack_wave(E, phase=False) if air is not None else None     # sqrt(exp(-2 k beta T))
+            smp = self.mySampleofInterest.stack_wave(E)
+            h.stacks = {"mem": concat(air_w, self.myMembrane.stack_wave(E)), "smp": smp}         # EXP:323,338
+            propag = (air_w, smp)
+            (a1, g1, h.du), (a2, g2, _), (a3, g3, _) = (self._fresnel_scalars(dMO, E, (dSM + dMO) / dSM),
+                                                         self._fresnel_scalars(dOD + dMO, E, M), self._fresnel_scalars(dOD, E, M))
+            h.aA, h.gA, h.aB, h.gB = [a1, a2], [g1, g2], [a3], [g3]
+        else:
+            mem, smp = self.myMembrane.stack_rt(E), self.mySampleofInterest.stack_rt(E)
+            mem_phase = mem.with_coeffs(catt=[0.0] * mem.n)
+            h.stacks = {"mem": concat(air_att, mem), "mem_phase": mem_phase, "both": concat(mem_phase, smp)}
+            propag = (air_att, smp)
+            h.dsMO, h.dsOD, h.zOD, h.M = self._dscale(dMO, E), self._dscale(dOD, E), dOD, M
+        h.stacks["plate"] = plate.stack_rt(E, phase=False) if plate is not None else None
+        if pointNum == 0:
+            h.stacks["propag"] = concat(*propag)
+            h.stacks["white"] = concat(air_att, h.stacks["plate"])
+        return h
+
+    def _deposit(self, acc, first, plate_att, op, scratch, sums=None, weight=0.0):
+        """acc (+)= op's image x the plate's attenuation (EXP:351-358 / 478-486), stored for the first energy of a bin and
+        added for the others, in as few passes as the case allows.  op(out, add) writes the image to `out`, or adds it; with
+        out = None it returns an image of its own.  No plate: op stores or adds straight into acc.  Plate: op writes to
+        `scratch` and one pass attenuates it into acc.  With `sums` (the reference image, EXP:360-361) that pass exists
+        anyway, to reduce the image for the mean energy: op only ever stores, into acc itself for the first energy of a bin
+        without a plate, which is then the bin's image so far and is only summed.  Returns what op returned."""
+        fused = plate_att is None and (sums is None or first)
+        r = op(acc if fused else scratch, fused and not first)
+        img = scratch if scratch is not None else r
+        if sums is None:
+            if not fused:
+                ops.accumulate(acc, img, 1.0, plate_att, add=not first)
+        elif fused:
+            ops.accumulate_sum(None, acc, sums, weight)
+        else:
+            ops.accumulate_sum(acc, img, sums, weight, mats=plate_att, add=not first)
+        return r
+
+    def _white(self, white, I_scalar, att, first):
         """EXP:372-375 / 494-497: the flat-field image of one energy (uniform unless air/plate maps are not)."""
-        att = ops.MaterialStack.concat(air_rt, plate_att)
         if first:
             ops.transmit_rt(None, I_scalar, att, want_phi=False, out=white)      # white = I * exp(-2 k beta T) (uniform without maps)
         else:
@@ -431,13 +498,13 @@ class Experiment:
                 cur, ibin = [], ibin + 1
         return bins, cur
 
-    def _bin_tables(self, sim, plate, air):
-        """Everything of the batched chains that depends on the energy only -- incident intensities, coefficient rows of every
-        material stack the chain uses, chirp scalars / displacement scales -- per detector bin, built once per experiment
-        state (the per-energy loop of the reference recomputes them for every membrane position) and re-based on each
-        position's maps (ops.MaterialBatch.rebase)."""
+    def _bin_tables(self, sim):
+        """Everything of the batched chains that depends on the energy only: _hops of every energy of a detector bin, each
+        field as a list over the bin's energies and each stack reduced to its coefficient rows (cphase rows, catt rows).
+        Built once per experiment state (the per-energy loop of the reference recomputes them for every membrane position)
+        and re-based on each position's maps (_rebased, _at).  Only for samples that do not fold (_batch_energies)."""
         ed, spec = self.exp_dict, self.mySource.mySpectrum
-        objs = (self.myMembrane, self.mySampleofInterest, air, plate)
+        objs = (self.myMembrane, self.mySampleofInterest, None if ed['inVacuum'] else self.myAirVolume, self.myPlate)
         key = (sim, id(spec), len(spec), tuple(spec[0]), tuple(spec[-1]), tuple(self.myDetector.det_param["myBinsThersholds"]),
                self.mySource.source_dict["myEnergySampling"], ed['distSourceToMembrane'], ed['distMembraneToObject'],
                ed['distObjectToDetector'], ed['magnification'], ed['meanShotCount'], ed['overSampling'], ed['studyPixelSize'],
@@ -446,153 +513,90 @@ class Experiment:
                tuple((id(o.delta), id(o.beta), len(o.delta), len(o.beta)) if o is not None else None for o in objs))
         if self._tables is not None and self._tables[0] == key:
             return self._tables[1]
-        dSM, dMO, dOD, M = ed['distSourceToMembrane'], ed['distMembraneToObject'], ed['distObjectToDetector'], ed['magnification']
-        rows = lambda stacks: ([st.cphase for st in stacks], [st.catt for st in stacks])
         bins, leftover = self._bins_of_spectrum()
         out = []
         for energies in bins:
-            Es = [E for _, E, _ in energies]
-            t = {"Es": Es, "I0": [self._incident(flux, E, ie) for ie, E, flux in energies]}
-            t["amp"] = [float(np.sqrt(v)) for v in t["I0"]]                                  # EXP:334
-            t["plate"] = rows([plate.stack_rt(E, phase=False) for E in Es]) if plate is not None else None
-            t["air_rt"] = rows([air.stack_rt(E, phase=False) for E in Es]) if air is not None else None
-            if sim == "Fresnel":
-                air_w = [air.stack_wave(E, phase=False) if air is not None else None for E in Es]
-                smp = [self.mySampleofInterest.stack_wave(E) for E in Es]
-                t["mem"] = rows([ops.MaterialStack.concat(aw, self.myMembrane.stack_wave(E)) for aw, E in zip(air_w, Es)])
-                t["smp"] = rows(smp)
-                t["smp0"] = rows([ops.MaterialStack.concat(aw, sm) for aw, sm in zip(air_w, smp)])
-                sc = [(self._fresnel_scalars(dMO, E, (dSM + dMO) / dSM), self._fresnel_scalars(dOD + dMO, E, M),
-                       self._fresnel_scalars(dOD, E, M)) for E in Es]
-                t["du"] = sc[0][0][2]
-                t["aA"], t["gA"] = [[c[0][0], c[1][0]] for c in sc], [[c[0][1], c[1][1]] for c in sc]
-                t["aB"], t["gB"] = [[c[2][0]] for c in sc], [[c[2][1]] for c in sc]
-            else:
-                air_rt = [air.stack_rt(E, phase=False) if air is not None else None for E in Es]
-                mem = [self.myMembrane.stack_rt(E) for E in Es]
-                smp = [self.mySampleofInterest.stack_rt(E) for E in Es]
-                mem_phase = [m.with_coeffs(catt=[0.0] * m.n) for m in mem]
-                t["mem_air"] = rows([ops.MaterialStack.concat(a_, m) for a_, m in zip(air_rt, mem)])
-                t["mem_phase"] = rows(mem_phase)
-                t["both"] = rows([ops.MaterialStack.concat(mp, sm) for mp, sm in zip(mem_phase, smp)])
-                t["air_smp"] = rows([ops.MaterialStack.concat(a_, sm) for a_, sm in zip(air_rt, smp)])
-                t["dsMO"] = [self._dscale(dMO, E) for E in Es]
-                t["dsOD"] = [self._dscale(dOD, E) for E in Es]
+            hops = [self._hops(sim, ie, E, flux, 0) for ie, E, flux in energies]
+            t = SimpleNamespace(**{name: [getattr(h, name) for h in hops] for name in vars(hops[0]) if name != "stacks"})
+            t.rows = {name: ([h.stacks[name].cphase for h in hops], [h.stacks[name].catt for h in hops])
+                      for name, st in hops[0].stacks.items() if st is not None}
             out.append(t)
         self._tables = (key, (out, leftover))
         return out, leftover
 
-    def _fresnel_bins_batched(self, pointNum, stacks, accs, plan, plate, air, N, sums):
+    def _energy_scratch(self, n, N, dev):
+        """n study-grid images for the per-energy intensities of a bin (batched chains), kept across positions."""
+        if self._etmp is None or self._etmp.shape[0] < n or tuple(self._etmp.shape[1:]) != N:
+            self._etmp = torch.empty((n,) + N, dtype=torch.float32, device=dev)
+        return [self._etmp[k] for k in range(n)]
+
+    # -------------------------------------------------------------------------------------- Fresnel chain
+    def _fresnel_bins_batched(self, pointNum, stacks, accs, plan, N, sums):
         """The Fresnel chain of one position (EXP:317-401) with the energies of each bin taken together.  Same operations on
         the same numbers as the per-energy loop; the per-energy intensities go through a scratch stack and are summed in
         spectrum order."""
-        ed = self.exp_dict
         accS, accR, accP, white = accs
-        dSM, dMO, dOD, M = ed['distSourceToMembrane'], ed['distMembraneToObject'], ed['distObjectToDetector'], ed['magnification']
-        tables, leftover = self._bin_tables("Fresnel", plate, air)
-        nmax = max([len(t["Es"]) for t in tables] + [1])
-        if self._etmp is None or self._etmp.shape[0] < nmax or tuple(self._etmp.shape[1:]) != N:
-            self._etmp = torch.empty((nmax,) + N, dtype=torch.float32, device=accS.device)
+        tables, leftover = self._bin_tables("Fresnel")
+        scratch = self._energy_scratch(max([len(t.E) for t in tables] + [1]), N, accS.device)
         # this position's maps under the cached coefficient rows (any energy serves: only the maps are taken)
-        E0 = self.mySource.mySpectrum[0][0]
-        air_w0 = air.stack_wave(E0, phase=False) if air is not None else None
-        smp_b = self.mySampleofInterest.stack_wave(E0)
-        mem_b = ops.MaterialStack.concat(air_w0, self.myMembrane.stack_wave(E0))
-        smp0_b = ops.MaterialStack.concat(air_w0, smp_b)
-        plate_b = plate.stack_rt(E0, phase=False) if plate is not None else None
+        base = self._hops("Fresnel", 0, *self.mySource.mySpectrum[0], pointNum)
+        mats = lambda t, name: _rebased(base.stacks[name], t.rows.get(name))
         for ibin, t in enumerate(tables):
-            Es, ne = t["Es"], len(t["Es"])
-            plate_att = _rebased(plate_b, t["plate"]) if plate is not None else None
-            tmp = [self._etmp[k] for k in range(ne)]
+            ne = len(t.E)
+            tmp, plate_att = scratch[:ne], mats(t, "plate")
             # EXP:341 + EXP:349: membrane exit wave -> sample plane (complex field) and -> detector (|.|^2), every energy
-            wbs = plan.propagate_sources(t["aA"], t["gA"], t["du"], amp=t["amp"], mats=_rebased(mem_b, t["mem"]),
-                                         want_wave=[True, False], inten_out=[[None, x] for x in tmp])
+            wbs = plan.propagate_sources(t.aA, t.gA, base.du, amp=t.amp, mats=mats(t, "mem"), want_wave=[True, False],
+                                         inten_out=[[None, x] for x in tmp])
             self.waveSampleBeforeSample = wbs[-1][0]
             # EXP:355-361: plate attenuation, sum over the bin's energies and the image sums for the mean energy
-            ops.accumulate_many(accR, tmp, sums, Es, mats=plate_att, add=False)
+            ops.accumulate_many(accR, tmp, sums, t.E, mats=plate_att, add=False)
             # EXP:344 + EXP:348: through the sample, on to the detector
-            plan.propagate_sources(t["aB"], t["gB"], t["du"], wave_in=[w[0] for w in wbs], mats=_rebased(smp_b, t["smp"]),
-                                   want_wave=[False], inten_out=[[x] for x in tmp])
+            plan.propagate_sources(t.aB, t.gB, base.du, wave_in=[w[0] for w in wbs], mats=mats(t, "smp"), want_wave=[False],
+                                   inten_out=[[x] for x in tmp])
             ops.accumulate_many(accS, tmp, None, [0.0] * ne, mats=plate_att, add=False)
             if pointNum == 0:                                                              # EXP:363-375
-                plan.propagate_sources(t["aB"], t["gB"], t["du"], amp=t["amp"], mats=_rebased(smp0_b, t["smp0"]),
-                                       want_wave=[False], inten_out=[[x] for x in tmp])
+                plan.propagate_sources(t.aB, t.gB, base.du, amp=t.amp, mats=mats(t, "propag"), want_wave=[False],
+                                       inten_out=[[x] for x in tmp])
                 ops.accumulate_many(accP, tmp, None, [0.0] * ne, mats=plate_att, add=False)
-                for k, E in enumerate(Es):
-                    air_rt = air.stack_rt(E, phase=False) if air is not None else None
-                    self._white(white, t["I0"][k], air_rt, plate.stack_rt(E, phase=False) if plate is not None else None, k == 0)
+                for k in range(ne):
+                    self._white(white, t.I0[k], _at(base.stacks["white"], t.rows["white"], k), k == 0)
             self._detect_bin(ibin, pointNum, stacks, accs)                                 # EXP:378-401
         if leftover:
             # energies above the last threshold: the reference still propagates them (the field it leaves behind is theirs)
-            E = leftover[-1][1]
-            I0 = self._incident(leftover[-1][2], E, leftover[-1][0])
-            air_w = air.stack_wave(E, phase=False) if air is not None else None
-            a1, g1, du = self._fresnel_scalars(dMO, E, (dSM + dMO) / dSM)
-            self.waveSampleBeforeSample = plan.propagate([a1], [g1], du, amp=float(np.sqrt(I0)),
-                                                         mats=ops.MaterialStack.concat(air_w, self.myMembrane.stack_wave(E)))[0]
+            h = self._hops("Fresnel", *leftover[-1], pointNum)
+            self.waveSampleBeforeSample = plan.propagate(h.aA[:1], h.gA[:1], h.du, amp=h.amp, mats=h.stacks["mem"])[0]
         return len(tables)
 
     def computeSampleAndReferenceImages_Fresnel(self, pointNum):
         """Experiment.py:279-405.  Returns (SampleImage, ReferenceImage, PropagImage, detectedWhite), each
         [nbins, n, n] float32 in HBM."""
-        ed = self.exp_dict
         stacks, accs, N, dev, sums = self._begin(pointNum)
         accS, accR, accP, white = accs
         plan = self._plan()
-        plate, air = self.myPlate, (None if ed['inVacuum'] else self.myAirVolume)
         tmp = self._tmp[0]
-        dSM, dMO, dOD, M = ed['distSourceToMembrane'], ed['distMembraneToObject'], ed['distObjectToDetector'], ed['magnification']
         if self._batch_energies(N, plan, "Fresnel"):
-            nvisited = self._fresnel_bins_batched(pointNum, stacks, accs, plan, plate, air, N, sums)
-            self._zero_unvisited_bins(stacks, nvisited, pointNum)
-            self._finish_mean_energy(sums, N[0] * N[1])
-            return tuple(stacks)
-        ibin = 0
-        first = True                     # first energy of the current bin: its images are stored, the later ones added
-        for ie, (currentEnergy, flux) in enumerate(self.mySource.mySpectrum):
-            I0 = self._incident(flux, currentEnergy, ie)
-            amp = float(np.sqrt(I0))                                                      # EXP:334
-            air_w = air.stack_wave(currentEnergy, phase=False) if air is not None else None   # sqrt(exp(-2 k beta T))
-            air_rt = air.stack_rt(currentEnergy, phase=False) if air is not None else None
-            plate_att = plate.stack_rt(currentEnergy, phase=False) if plate is not None else None
-            mem = ops.MaterialStack.concat(air_w, self.myMembrane.stack_wave(currentEnergy))   # EXP:323,338
-            smp = self.mySampleofInterest.stack_wave(currentEnergy)
-            a1, g1, du = self._fresnel_scalars(dMO, currentEnergy, (dSM + dMO) / dSM)     # EXP:340 local magnification
-            a2, g2, _ = self._fresnel_scalars(dOD + dMO, currentEnergy, M)
-            a3, g3, _ = self._fresnel_scalars(dOD, currentEnergy, M)
-            # EXP:341 + EXP:349 in one call: membrane exit wave -> sample plane (complex field) and -> detector (|.|^2)
-            # (the first energy of a bin without a plate IS the bin's image so far: it is written in place and only summed)
-            direct = first and plate_att is None
-            wbs = plan.propagate([a1, a2], [g1, g2], du, amp=amp, mats=mem, want_wave=[True, False],
-                                 inten_out=[None, accR if direct else tmp])[0]
-            self.waveSampleBeforeSample = wbs
-            # EXP:355-361: plate attenuation, sum over energies and the image sum for the mean energy in one pass
-            if direct:
-                ops.accumulate_sum(None, accR, sums, currentEnergy)
-            else:
-                ops.accumulate_sum(accR, tmp, sums, currentEnergy, mats=plate_att, add=not first)
-            # EXP:344 + EXP:348: through the sample, on to the detector
-            if plate_att is None:
-                plan.propagate([a3], [g3], du, wave_in=wbs, mats=smp, want_wave=[False], inten_out=[accS], add=not first)
-            else:
-                plan.propagate([a3], [g3], du, wave_in=wbs, mats=smp, want_wave=[False], inten_out=[tmp])
-                self._add_intensity(accS, tmp, plate_att, add=not first)
-            if pointNum == 0:                                                             # EXP:363-375
-                smp0 = ops.MaterialStack.concat(air_w, smp)
-                if plate_att is None:
-                    plan.propagate([a3], [g3], du, amp=amp, mats=smp0, want_wave=[False], inten_out=[accP], add=not first)
-                else:
-                    plan.propagate([a3], [g3], du, amp=amp, mats=smp0, want_wave=[False], inten_out=[tmp])
-                    self._add_intensity(accP, tmp, plate_att, add=not first)
-                self._white(white, I0, air_rt, plate_att, first)
-            first = False
-            if currentEnergy > self.myDetector.det_param["myBinsThersholds"][ibin] - self.mySource.source_dict["myEnergySampling"] / 2:
-                self._detect_bin(ibin, pointNum, stacks, accs)                            # EXP:378-401
-                ibin += 1
-                first = True
-        self._zero_unvisited_bins(stacks, ibin, pointNum)
-        self._finish_mean_energy(sums, N[0] * N[1])
-        return tuple(stacks)
+            return self._finish("Fresnel", pointNum, stacks, self._fresnel_bins_batched(pointNum, stacks, accs, plan, N, sums), sums, N)
+        bins, leftover = self._bins_of_spectrum()
+        # (energies above the last threshold -- a spectrum sampled finer than half its declared step -- have no bin to be
+        # detected into: like the reference's loop, EXP:378, theirs ends in an IndexError)
+        for ibin, energies in enumerate(bins + ([leftover] if leftover else [])):
+            for k, (ie, E, flux) in enumerate(energies):
+                h = self._hops("Fresnel", ie, E, flux, pointNum)
+                st, first = h.stacks, k == 0         # first energy of a bin: its images are stored, the later ones added
+                # EXP:341 + EXP:349 in one call: membrane exit wave -> sample plane (complex field) and -> detector (|.|^2);
+                # EXP:355-361: plate attenuation, sum over energies and the image sum for the mean energy in one pass
+                wbs = self._deposit(accR, first, st["plate"], lambda out, add: plan.propagate(
+                    h.aA, h.gA, h.du, amp=h.amp, mats=st["mem"], want_wave=[True, False], inten_out=[None, out]), tmp, sums, E)[0]
+                self.waveSampleBeforeSample = wbs
+                # EXP:344 + EXP:348: through the sample, on to the detector
+                self._deposit(accS, first, st["plate"], lambda out, add: plan.propagate(
+                    h.aB, h.gB, h.du, wave_in=wbs, mats=st["smp"], want_wave=[False], inten_out=[out], add=add), tmp)
+                if pointNum == 0:                                                         # EXP:363-375
+                    self._deposit(accP, first, st["plate"], lambda out, add: plan.propagate(
+                        h.aB, h.gB, h.du, amp=h.amp, mats=st["propag"], want_wave=[False], inten_out=[out], add=add), tmp)
+                    self._white(white, h.I0, st["white"], first)
+            self._detect_bin(ibin, pointNum, stacks, accs)                                # EXP:378-401
+        return self._finish("Fresnel", pointNum, stacks, len(bins), sums, N)
 
     # ------------------------------------------------------------------------------------------- RT chain
     def _dscale(self, z, Energy):
@@ -608,7 +612,7 @@ class Experiment:
         (0.10-0.20 ms at 4096^2) runs once per energy of an experiment, not once per position."""
         ed = self.exp_dict
         key = (float(Energy), float(z))
-        cache = self.__dict__.setdefault("_df_tab_cache", {})
+        cache = self._df_tab_cache
         hit = cache.get(key)
         if hit is not None and hit[0] is DF:
             cache[key] = cache.pop(key)
@@ -616,7 +620,7 @@ class Experiment:
         den = ed["studyPixelSize"] * 1e-6 * ed['magnification']      # RF2:114: DF * z / den, in that order
         limit = N[0] / 4                                             # RF2:135
         _, _, DF_px, prep, words = ops.darkfield_split(self._tmp[0], DF, z, den, limit)    # the split images are not used
-        known = self.mySampleofInterest.dark_field_max(DF) if hasattr(self.mySampleofInterest, "dark_field_max") else None
+        known = self.mySampleofInterest.dark_field_max(DF)
         if known is not None and float(known) * z / den <= limit:
             maxDF = maxDFc = float(known) * z / den
         else:
@@ -629,25 +633,26 @@ class Experiment:
         cache[key] = (DF, DF_px, prep, R, margin2)
         return DF_px, prep, R, margin2
 
-    def _refraction_df_fused(self, Ibs, both, z, Energy, DF, N, clamp, out=None, add=False):
+    def _refraction_df_fused(self, Ibs, h, DF, N, clamp, out=None, add=False):
         """The chain's dark-field hop (EXP:469-473 -> RF2:88-196) without its intermediates: the reference forms the transmitted
         (I, phi) pair (SAM:347-348), splits I by the width map (RF2:147-150), refracts both halves and re-splats the dark-field
         half.  Here each halves come out of ONE refraction call straight from the thickness maps with the width map deciding
         a source's half (psx_refract_split_f32: a tile is staged once for both): no (I, phi) pair (12 bytes per pixel written and read twice), no split images, and the tables
-        that depend on the width map alone come from _df_tables.  Same arithmetic per source pixel as the unfused calls."""
-        DF_px, prep, R, margin2 = self._df_tables(DF, z, Energy, N)
+        that depend on the width map alone come from _df_tables.  Same arithmetic per source pixel as the unfused calls.
+        h: the energy's hops (_hops): the membrane phase + sample stack, the distance and the displacement scale."""
+        both = h.stacks["both"]
+        DF_px, prep, R, margin2 = self._df_tables(DF, h.zOD, h.E, N)
         if margin2 < 1:      # a width map that is zero everywhere: the reference's margin-0 special case, through the literal path
             Ias, phis = ops.transmit_rt(Ibs, 1.0, both)
-            img = self.refraction(Ias, phis, z, Energy, self.exp_dict['magnification'], DF, _mutate=False, _want_D=False)[0]
+            img = self.refraction(Ias, phis, h.zOD, h.E, h.M, DF, _mutate=False, _want_D=False)[0]
             if out is not None:
                 ops.accumulate(out, img, 1.0, None, add=add)
                 return out
             return img
         m = max(margin2, 8)
-        dscale = self._dscale(z, Energy)
         if self._df_tmp is None or tuple(self._df_tmp.shape) != N:
             self._df_tmp = torch.empty(N, dtype=torch.float32, device=Ibs.device)
-        I2, I2DF = ops.refract_split(N, both, dscale, clamp, DF_px, margin=m, I_in=Ibs, outs=[self._tmp[0], self._df_tmp])
+        I2, I2DF = ops.refract_split(N, both, h.dsOD, clamp, DF_px, margin=m, I_in=Ibs, outs=[self._tmp[0], self._df_tmp])
         return ops.darkfield_blur_prepared(I2DF, DF_px, prep, I2, R, out=out, add=add)    # the NaN / inf scan (RF2:190-193) rides on its stores
 
     def _set_halo(self, N, clamp, air):
@@ -684,48 +689,39 @@ class Experiment:
                 self._halo = int(want)
         ops.set_refract_halo(self._halo)
 
-    def _rt_bins_batched(self, pointNum, stacks, accs, plate, air, N, sums, clamp):
+    def _rt_bins_batched(self, pointNum, stacks, accs, N, sums, clamp):
         """The ray-tracing chain of one position (EXP:448-521) with the energies of each bin taken together
         (psx_refract_batch_f32: one launch per kernel for up to 8 energies); samples without dark field only."""
-        ed = self.exp_dict
         accS, accR, accP, white = accs
-        dMO, dOD = ed['distMembraneToObject'], ed['distObjectToDetector']
-        tables, _ = self._bin_tables("RayT", plate, air)
-        nmax = max([len(t["Es"]) for t in tables] + [1])
-        if self._etmp is None or self._etmp.shape[0] < 2 * nmax or tuple(self._etmp.shape[1:]) != N:
-            self._etmp = torch.empty((2 * nmax,) + N, dtype=torch.float32, device=accS.device)
+        tables, _ = self._bin_tables("RT")
+        nmax = max([len(t.E) for t in tables] + [1])
+        scratch = self._energy_scratch(2 * nmax, N, accS.device)
         # this position's maps under the cached coefficient rows (any energy serves: only the maps are taken)
-        E0 = self.mySource.mySpectrum[0][0]
-        air_b = air.stack_rt(E0, phase=False) if air is not None else None
-        mem_b, smp_b = self.myMembrane.stack_rt(E0), self.mySampleofInterest.stack_rt(E0)
-        mem_air_b, both_b = ops.MaterialStack.concat(air_b, mem_b), ops.MaterialStack.concat(mem_b, smp_b)
-        air_smp_b = ops.MaterialStack.concat(air_b, smp_b)
-        plate_b = plate.stack_rt(E0, phase=False) if plate is not None else None
+        base = self._hops("RT", 0, *self.mySource.mySpectrum[0], pointNum)
+        mats = lambda t, name: _rebased(base.stacks[name], t.rows.get(name))
         for ibin, t in enumerate(tables):
-            Es, ne, I0 = t["Es"], len(t["Es"]), t["I0"]
-            plate_att = _rebased(plate_b, t["plate"]) if plate is not None else None
-            Ibs = [self._etmp[k] for k in range(ne)]
-            tmp = [self._etmp[nmax + k] for k in range(ne)]
+            ne = len(t.E)
+            Ibs, tmp, plate_att = scratch[:ne], scratch[nmax:nmax + ne], mats(t, "plate")
             # EXP:463 + 466: membrane transmission fused into the first refraction, every energy
-            ops.refract_batch(N, _rebased(mem_air_b, t["mem_air"]), t["dsMO"], clamp, I0=I0, outs=Ibs)
+            ops.refract_batch(N, mats(t, "mem"), t.dsMO, clamp, I0=t.I0, outs=Ibs)
             self.IntensitySampleBeforeSample = Ibs[-1]
             # EXP:474 reference images: refracted again with the membrane phase only; EXP:480-486 their attenuated sum
-            ops.refract_batch(N, _rebased(mem_b, t["mem_phase"]), t["dsOD"], clamp, I_in=Ibs, outs=tmp)
-            ops.accumulate_many(accR, tmp, sums, Es, mats=plate_att, add=False)
+            ops.refract_batch(N, mats(t, "mem_phase"), t.dsOD, clamp, I_in=Ibs, outs=tmp)
+            ops.accumulate_many(accR, tmp, sums, t.E, mats=plate_att, add=False)
             # EXP:469 + 473 sample images: sample attenuation and membrane+sample phase fused into the refraction
-            ops.refract_batch(N, _rebased(both_b, t["both"]), t["dsOD"], clamp, I_in=Ibs, outs=tmp)
+            ops.refract_batch(N, mats(t, "both"), t.dsOD, clamp, I_in=Ibs, outs=tmp)
             ops.accumulate_many(accS, tmp, None, [0.0] * ne, mats=plate_att, add=False)
             if pointNum == 0:                                                             # EXP:488-498
+                rows = t.rows["propag"]
                 if ne > 1:
-                    head = (t["air_smp"][0][:-1], t["air_smp"][1][:-1])
-                    ops.refract_batch(N, _rebased(air_smp_b, head), t["dsOD"][:-1], clamp, I0=I0[:-1], outs=tmp[:-1])
+                    head = _rebased(base.stacks["propag"], (rows[0][:-1], rows[1][:-1]))
+                    ops.refract_batch(N, head, t.dsOD[:-1], clamp, I0=t.I0[:-1], outs=tmp[:-1])
                 # the last energy of the bin leaves the displacement maps behind (EXP:492), like the per-energy loop
-                last = air_smp_b.with_coeffs(cphase=t["air_smp"][0][-1], catt=t["air_smp"][1][-1])
-                _, self.Dxreal, self.Dyreal = ops.refract(N, last, t["dsOD"][-1], clamp, I0=I0[-1], out=tmp[ne - 1], want_D=True)
+                _, self.Dxreal, self.Dyreal = ops.refract(N, _at(base.stacks["propag"], rows, ne - 1), t.dsOD[-1], clamp,
+                                                          I0=t.I0[-1], out=tmp[ne - 1], want_D=True)
                 ops.accumulate_many(accP, tmp, None, [0.0] * ne, mats=plate_att, add=False)
-                for k, E in enumerate(Es):
-                    self._white(white, I0[k], air.stack_rt(E, phase=False) if air is not None else None,
-                                plate.stack_rt(E, phase=False) if plate is not None else None, k == 0)
+                for k in range(ne):
+                    self._white(white, t.I0[k], _at(base.stacks["white"], t.rows["white"], k), k == 0)
             self._detect_bin(ibin, pointNum, stacks, accs)                                # EXP:501-521
         return len(tables)
 
@@ -747,90 +743,53 @@ class Experiment:
         return float(ed['meanShotCount'] / ed['overSampling'] ** 2 * flux)
 
     def _rt_chain(self, pointNum):
-        ed = self.exp_dict
+        ed, sample = self.exp_dict, self.mySampleofInterest
         stacks, accs, N, dev, sums = self._begin(pointNum)
         accS, accR, accP, white = accs
-        plate, air = self.myPlate, (None if ed['inVacuum'] else self.myAirVolume)
         Ibs, tmp = self._tmp[1], self._tmp[0]
-        scattering = self.mySampleofInterest.has_dark_field()
+        scattering = sample.has_dark_field()
         # EXP:444 re-zeros the dark-field map on EVERY call (it only builds up while position 0 is computed, EXP:491): a
         # scattering sample therefore returns zeros for pointNum > 0, whatever positions this object computed before
         # (EXP:444 allocates a NEW array: the map returned for an earlier position stays what it was, so a scattering sample
         # gets a fresh tensor per call -- filling the old one in place would clear what the caller still holds)
         if scattering or not isinstance(self.darkFieldPropag, torch.Tensor) or tuple(self.darkFieldPropag.shape) != N:
             self.darkFieldPropag = ops.fill(torch.empty(N, dtype=torch.float32, device=dev), 0.0)   # scalar dark field: stays zero
-        dMO, dOD = ed['distMembraneToObject'], ed['distObjectToDetector']
         clamp = (N[0], N[1])                                                              # RF2:61-64
-        self._set_halo(N, clamp, air)
+        self._set_halo(N, clamp, None if ed['inVacuum'] else self.myAirVolume)
         if not scattering and self._batch_energies(N, None, "RT"):
-            nvisited = self._rt_bins_batched(pointNum, stacks, accs, plate, air, N, sums, clamp)
-            self._zero_unvisited_bins(stacks, nvisited, pointNum)
-            if not ed.get('deferStatus'):
-                ops.check_status(dev, "computeSampleAndReferenceImages_RT")               # RF2:81-82, checked once
-            self._finish_mean_energy(sums, N[0] * N[1])
-            if not ed.get('deferMeanEnergy'):
-                print("Mean detected energy in reference image", ed['meanEnergy'])
-            return stacks[0], stacks[1], stacks[2], stacks[3], self.Dxreal, self.Dyreal, self.darkFieldPropag
-        ibin = 0
-        first = True
-        for ie, (currentEnergy, flux) in enumerate(self.mySource.mySpectrum):
-            I0 = self._incident(flux, currentEnergy, ie)
-            air_rt = air.stack_rt(currentEnergy, phase=False) if air is not None else None
-            plate_att = plate.stack_rt(currentEnergy, phase=False) if plate is not None else None
-            mem = self.myMembrane.stack_rt(currentEnergy)
-            smp = self.mySampleofInterest.stack_rt(currentEnergy)
-            # EXP:463 + 466: membrane transmission fused into the first refraction
-            ops.refract(N, ops.MaterialStack.concat(air_rt, mem), self._dscale(dMO, currentEnergy), clamp, I0=I0, out=Ibs)
-            self.IntensitySampleBeforeSample = Ibs
-            mem_phase = mem.with_coeffs(catt=[0.0] * mem.n)
-            # EXP:474 reference image: refracted again with the membrane phase only
-            # (the first energy of a bin without a plate IS the bin's image so far: it is written in place and only summed)
-            direct = first and plate_att is None
-            ops.refract(N, mem_phase, self._dscale(dOD, currentEnergy), clamp, I_in=Ibs, out=accR if direct else tmp)
-            # EXP:480-486: plate attenuation, sum over energies and the image sum for the mean energy in one pass
-            if direct:
-                ops.accumulate_sum(None, accR, sums, currentEnergy)
-            else:
-                ops.accumulate_sum(accR, tmp, sums, currentEnergy, mats=plate_att, add=not first)
-            # EXP:469 + 473 sample image: sample attenuation and membrane+sample phase fused into the refraction
-            both = ops.MaterialStack.concat(mem_phase, smp)
-            if scattering:                                       # Lung / cylinder_beeds: fastRefractionDF (EXP:272-275)
-                DF = self.mySampleofInterest.dark_field(currentEnergy)
-                if plate_att is None:         # the sum over energies (EXP:478-483) rides on the re-splat's store
-                    self._refraction_df_fused(Ibs, both, dOD, currentEnergy, DF, N, clamp, out=accS, add=not first)
+            return self._finish("RT", pointNum, stacks, self._rt_bins_batched(pointNum, stacks, accs, N, sums, clamp), sums, N)
+        bins, leftover = self._bins_of_spectrum()
+        # (energies above the last threshold end in an IndexError at their detection, as in the Fresnel loop)
+        for ibin, energies in enumerate(bins + ([leftover] if leftover else [])):
+            for k, (ie, E, flux) in enumerate(energies):
+                h = self._hops("RT", ie, E, flux, pointNum)
+                st, first = h.stacks, k == 0         # first energy of a bin: its images are stored, the later ones added
+                # EXP:463 + 466: membrane transmission fused into the first refraction
+                ops.refract(N, st["mem"], h.dsMO, clamp, I0=h.I0, out=Ibs)
+                self.IntensitySampleBeforeSample = Ibs
+                # EXP:474 reference image: refracted again with the membrane phase only; EXP:480-486: plate attenuation, sum
+                # over energies and the image sum for the mean energy in one pass
+                self._deposit(accR, first, st["plate"], lambda out, add: ops.refract(
+                    N, st["mem_phase"], h.dsOD, clamp, I_in=Ibs, out=out), tmp, sums, E)
+                # EXP:469 + 473 sample image: sample attenuation and membrane+sample phase fused into the refraction
+                if scattering:                                   # Lung / cylinder_beeds: fastRefractionDF (EXP:272-275); the
+                    DF = sample.dark_field(E)                    # sum over energies (EXP:478-483) rides on the re-splat's store
+                    self._deposit(accS, first, st["plate"], lambda out, add: self._refraction_df_fused(
+                        Ibs, h, DF, N, clamp, out=out, add=add), None)
                 else:
-                    img = self._refraction_df_fused(Ibs, both, dOD, currentEnergy, DF, N, clamp)
-                    self._add_intensity(accS, img, plate_att, add=not first)
-            elif plate_att is None:
-                ops.refract(N, both, self._dscale(dOD, currentEnergy), clamp, I_in=Ibs, out=accS, add=not first)
-            else:
-                ops.refract(N, both, self._dscale(dOD, currentEnergy), clamp, I_in=Ibs, out=tmp)
-                self._add_intensity(accS, tmp, plate_att, add=not first)
-            if pointNum == 0:                                                             # EXP:488-498
-                if scattering:
-                    Ip, phip = ops.transmit_rt(None, I0, ops.MaterialStack.concat(air_rt, smp))
-                    self.darkFieldPropag += (DF * flux).to(torch.float32)                 # EXP:491
-                    img, self.Dxreal, self.Dyreal = self.refraction(Ip, phip, dOD, currentEnergy, ed['magnification'], DF,
-                                                                    _mutate=False)
-                    self._add_intensity(accP, img, plate_att, add=not first)
-                else:
-                    _, self.Dxreal, self.Dyreal = ops.refract(N, ops.MaterialStack.concat(air_rt, smp),
-                                                              self._dscale(dOD, currentEnergy), clamp, I0=I0, out=tmp,
-                                                              want_D=True)
-                    self._add_intensity(accP, tmp, plate_att, add=not first)
-                self._white(white, I0, air_rt, plate_att, first)
-            first = False
-            if currentEnergy > self.myDetector.det_param["myBinsThersholds"][ibin] - self.mySource.source_dict["myEnergySampling"] / 2:
-                self._detect_bin(ibin, pointNum, stacks, accs)                            # EXP:501-521
-                ibin += 1
-                first = True
-        self._zero_unvisited_bins(stacks, ibin, pointNum)
-        if not ed.get('deferStatus'):
-            ops.check_status(dev, "computeSampleAndReferenceImages_RT")                   # RF2:81-82, checked once
-        self._finish_mean_energy(sums, N[0] * N[1])
-        if not ed.get('deferMeanEnergy'):
-            print("Mean detected energy in reference image", ed['meanEnergy'])
-        return stacks[0], stacks[1], stacks[2], stacks[3], self.Dxreal, self.Dyreal, self.darkFieldPropag
+                    self._deposit(accS, first, st["plate"], lambda out, add: ops.refract(
+                        N, st["both"], h.dsOD, clamp, I_in=Ibs, out=out, add=add), tmp)
+                if pointNum == 0:                                                         # EXP:488-498
+                    if scattering:
+                        Ip, phip = ops.transmit_rt(None, h.I0, st["propag"])
+                        self.darkFieldPropag += (DF * flux).to(torch.float32)             # EXP:491
+                        img, self.Dxreal, self.Dyreal = self.refraction(Ip, phip, h.zOD, E, h.M, DF, _mutate=False)
+                    else:
+                        img, self.Dxreal, self.Dyreal = ops.refract(N, st["propag"], h.dsOD, clamp, I0=h.I0, out=tmp, want_D=True)
+                    ops.accumulate(accP, img, 1.0, st["plate"], add=not first)
+                    self._white(white, h.I0, st["white"], first)
+            self._detect_bin(ibin, pointNum, stacks, accs)                                # EXP:501-521
+        return self._finish("RT", pointNum, stacks, len(bins), sums, N)
 
     # ------------------------------------------------------------------------------------------- reporting
     def saveAllParameters(self, time0, expDict):

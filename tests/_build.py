@@ -46,6 +46,15 @@ def build_experiment(cfg, sim, noise=False, sample_materials=("Nylon",), sample_
                                    plate=sample(cfg["plate"], "plate", "thin_film", ["C"]))
 
 
+def toggle_plate(cfg, Obj):
+    """The configuration without its plate, or, where it has none, with one: a uniform 1 m map under the air object's
+    coefficients (a few per cent of attenuation at the golden energies)."""
+    cfg = dict(cfg)
+    air = cfg["air"]
+    cfg["plate"] = Obj(np.ones_like(air.geometry), air.delta, air.beta) if cfg["plate"] is None else None
+    return cfg
+
+
 def cfg_from_experiment(exp, Obj):
     """Oracle configuration holding exactly what an XML-built paresis_amd Experiment holds (same XML -> both sides)."""
     import numpy as np

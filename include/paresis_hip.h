@@ -402,6 +402,24 @@ typedef struct {
 } psx_volume_desc;
 int psx_volume_project_u8(const psx_volume_desc *desc, const uint8_t *labels, double *lines_or_null, float *geom, void *stream);
 
+/* ---- the same volume under a point source: divergent (cone-beam) projection -----------------------------------------------
+ * Geometry, in voxels about the rotation axis: depth w = r - c0 along the walk (c0 = m / 2, the walk ascending in r), t
+ * across the axis, z the height above the optical axis.  The source is at (t, w, z) = (0, -dso, 0); the study grid is the
+ * virtual detector through the axis, the plane w = 0, so a ray through its point (t0, z0) is at (t0 g, z0 g) at depth w,
+ * g = (dso + w)/dso.  Same descriptor, buffers and limits as psx_volume_project_u8, plus dso in [m, 1e30] (PSX_E_ARG
+ * otherwise, NaN included): the source lies outside the slice's bounding circle and dso + w > 0 on the whole walk.
+ * In float64, every product, quotient, sum and square root rounded on its own (no contraction), for study pixel (x, y):
+ *   t0 = (double)(y - dimY / 2) * s,  z0 = (double)(x - dimX / 2) * s;  for r = 0 .. m - 1 in ascending order
+ *   g = (dso + (double)(r - c0)) / dso;  cpos = t0 * g + (double)c0;  slice z = n / 2 + (int)floor(z0 * g + 0.5), and a step
+ *   whose z is outside [0, n) adds nothing;  X = cos*cpos + sin*r + off_x,  Y = (-sin*cpos) + cos*r + off_y, and the floors,
+ *   the ceils, dr, dc and the bilinear indicator term of material k are psx_volume_project_u8's, on slice z:  acc_k += term.
+ *   L = sqrt(1 + (t0*t0 + z0*z0)/(dso*dso)), the path length of a unit step in w;
+ *   lines[k][x][y] = acc_k * L,  geom[k][x][y] = (float)(lines[k][x][y] * voxel_m).
+ * No atomics and no reduction across lanes: the order above is the order of the sum.  box spares steps as above.  At
+ * dso >= 2^66 every g is exactly 1 and L is 1: the maps are psx_volume_project_u8's bit for bit. */
+int psx_volume_project_cone_u8(const psx_volume_desc *desc, double dso, const uint8_t *labels, double *lines_or_null,
+                               float *geom, void *stream);
+
 /* ---- phase retrieval of speckle image stacks (no counterpart in the reference: its images' consumer) -----------------
  * LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021) over K positions of one energy bin: per pixel,
  *   R_k ~ x0*S_k + x1*g0_k + x2*g1_k,  (g0, g1) = np.gradient(R_k) (unit spacing, edge_order=1, float32 differences),
@@ -592,6 +610,39 @@ int psx_fbp_adjoint_f32(psx_fbp_plan *plan, const float *sino, int n, float *vol
 int psx_fbp_tv_step_f32(psx_fbp_plan *plan, int n, double lambda, int nonneg, const float *u, const float *c, float *x,
                         const float *xbar_in, float *xbar_out, const float *px_in, const float *py_in, float *px_out,
                         float *py_out, void *stream);
+
+/* ---- FDK: filtered back-projection of a full-turn cone-beam scan (Feldkamp, Davis, Kress, JOSA A 1, 612, 1984) ------------
+ * sino [A][n][m] float32 on the virtual detector through the rotation axis (pixel = voxel), as psx_fbp_f32's; theta: A
+ * angles in degrees, meant to cover a full turn evenly; center: the axis's column; vcenter: the optical axis's row (a
+ * double: fractional, or outside [0, n)); dso: the source's distance from the axis in voxels, in [m, 1e30]; filter:
+ * PSX_FBP_RAMP, _HANN or _NONE (the differential filters are refused).  vol [n][m][m]; slice Z lies at height Z - vcenter.
+ * The geometry is psx_volume_project_cone_u8's: at angle a, voxel (i, j), h = m / 2, has t = (j - h) c_a - (i - h) s_a across
+ * the axis and the depth w = (j - h) s_a + (i - h) c_a, and is seen at (t U, z U), U = dso/(dso + w).
+ *   1. Pre-weight, in float64, each operation rounded on its own, fused into the pack:  dk = (double)k - center,
+ *      dr = (double)r - vcenter,  p' = (float)((double)p * dso / sqrt((dso*dso + dk*dk) + dr*dr)).
+ *   2. The lines of p' are filtered exactly as psx_fbp_f32 filters them (the same H, two lines per transform, the same code).
+ *   3. Back-projection, per angle and voxel in float64, each operation rounded on its own (no contraction):
+ *      t = dj*c - di*s,  w = dj*s + di*c  (dj = j - h, di = i - h);  U = dso/(dso + w);  u = t*U + center;
+ *      v = ((double)Z - vcenter)*U + vcenter.  The sample is bilinear in (v, u) with the float32 weights of B:
+ *      fl = floor(coord), w1 = (float)(coord - fl), w0 = 1.0f - w1, on q with q[-1][.] = q[n][.] = q[.][-1] = q[.][m] = 0,
+ *      and 0 unless -1 < u < m and -1 < v < n: continuous at the detector's edges in both axes.  In float32:
+ *      lo = fmaf(wu1, q[fv][fu+1], wu0*q[fv][fu]),  hi = fmaf(wu1, q[fv+1][fu+1], wu0*q[fv+1][fu]),
+ *      acc = fmaf((float)(U*U), fmaf(wv1, hi, wv0*lo), acc) in ascending a;  vol[Z][i][j] = acc * (float)(pi/(2A)).
+ *      circle != 0: voxels with (i - h)^2 + (j - h)^2 > h^2 are 0.
+ * The scale is the ramp's own: H is 2|f|, and FDK over a full turn is (1/2) int_0^2pi U^2 (p' * |f|) dbeta = (pi/A) sum, hence
+ * pi/(2A) sum with this filter.  As dso grows the volume tends to psx_fbp_f32's.
+ * A voxel of slice Z reads detector rows other than Z, so the plan fixes n as well and owns the filtered sinogram of all
+ * rows, A*n*m float32, besides a parallel plan's tables, transforms and row-block buffer; psx_fdk_plan_bytes reports both.
+ * PSX_E_ARG: A*n*m above PSX_FDK_MAX_SAMPLES (2^31 samples, 8 GiB), n outside [1, 65535], |vcenter| > 2^20, dso outside
+ * [m, 1e30] or NaN, a differential filter, and whatever psx_fbp_plan_create refuses.  Deterministic, no atomics: a voxel's
+ * bits do not depend on n's blocks.  Calls on one plan are ordered on one stream. */
+#define PSX_FDK_MAX_SAMPLES ((int64_t)1 << 31)
+typedef struct psx_fdk_plan psx_fdk_plan;
+int psx_fdk_plan_create(int A, int n, int m, const double *theta_deg, double center, double vcenter, double dso, int filter,
+                        int circle, psx_fdk_plan **plan);
+int psx_fdk_plan_destroy(psx_fdk_plan *plan);
+size_t psx_fdk_plan_bytes(const psx_fdk_plan *plan);
+int psx_fdk_f32(psx_fdk_plan *plan, const float *sino, float *vol, void *stream);
 
 /* ---- spectral material decomposition of energy-binned scans (paresis_amd/spectral.py) -------------------------------------
  * Projection-domain decomposition: per pixel, from the B per-bin log-transmissions L_b = -ln(transmission of bin b), the

@@ -90,6 +90,8 @@ class AnalyticalSample(Sample):
         self.myVolume = None       # getVolumeFromFile: uint8 labels [n, m, m], a numpy array or a CUDA tensor (else myVolumeFile)
         self._dev_volume = None
         self._dev_volume_src = None
+        self.mySourceDistance = None   # metres from a point source to the rotation axis: getVolumeFromFile then projects along
+                                       # diverging rays (tomography.scan(beam='cone') sets it); None: the parallel beam
 
     # ------------------------------------------------------------------------------------------ geometry
     def getMyGeometry(self, studyDimensions, studyPixelSize, oversamp, pointNum=0, number_of_positions=0):
@@ -117,6 +119,10 @@ class AnalyticalSample(Sample):
                 self.myGeometry, self.geom_parameters = geometry.spheres_in_parallelepiped(dimX, dimY, studyPixelSize)
                 return
             if fn == "generateContrastPhantom":                                 # SAM:220-221, on the GPU
+                if getattr(self, "mySourceDistance", None) is not None:
+                    raise ValueError("generateContrastPhantom is analytic and parallel-beam: mySourceDistance is an option "
+                                     "of getVolumeFromFile (Samples.getVolumeFromFile.contrast_phantom_volume gives the "
+                                     "phantom as a label volume)")
                 from .Samples.generateContrastPhantom import generateContrastPhantom
                 self.myGeometry, self.geom_parameters = generateContrastPhantom(dimX, dimY, studyPixelSize,
                                                                                    angle=getattr(self, "myAngle", 30))
@@ -125,7 +131,8 @@ class AnalyticalSample(Sample):
                 from .Samples.getVolumeFromFile import getVolumeFromFile
                 self.myGeometry, self.geom_parameters = getVolumeFromFile(self.volume_dev(), len(self.myMaterials),
                                                                              self.myVoxelSize, dimX, dimY, studyPixelSize,
-                                                                             angle=getattr(self, "myAngle", 30))
+                                                                             angle=getattr(self, "myAngle", 30),
+                                                                             dso=self.source_distance_voxels())
                 return
             if fn == "loadSampleGeometryFromImages":                            # SAM:222-225
                 geom, self.geom_parameters = geometry.load_sample_geometry_from_images(self.myGeometryFolder, dimX, dimY,
@@ -149,6 +156,11 @@ class AnalyticalSample(Sample):
             self.myGeometry = np.full((1, dimX, dimY), self.myThickness * 1e-6, dtype=np.float32)   # SAM:239-243
             return
         raise ValueError("Could not define sample geometry")
+
+    def source_distance_voxels(self):
+        """mySourceDistance (metres) in voxels of myVoxelSize (micrometres): getVolumeFromFile's dso; None for the parallel beam."""
+        d = getattr(self, "mySourceDistance", None)
+        return None if d is None else float(d) * 1e6 / float(self.myVoxelSize)
 
     def volume_dev(self):
         """The label volume of getVolumeFromFile, checked and uploaded once per myVolume object (read from myVolumeFile

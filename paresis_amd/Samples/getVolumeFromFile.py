@@ -5,6 +5,9 @@ tomography.fbp's volume; label 0 is empty, label k + 1 is the sample's material 
 contrast phantom's model -- scikit-image `radon(slice, [angle])`, circle=True: the slice sampled bilinearly along the rotated
 rays -- into one thickness map per material on the study grid (the contract is in include/paresis_hip.h).  Study rows take
 the nearest slice (no interpolation across slices); the study pixel may differ from the voxel by a factor of 1/64 to 64.
+With dso, the distance in voxels from a point source to the rotation axis, the rays diverge from that source instead
+(k_volume_project_cone): the study grid is then the virtual detector through the axis, a ray crosses slices, and the maps
+hold path lengths along the rays.
 
 radon's circle is checked here, once per volume, not in the kernel: a label outside (i - c)^2 + (j - c)^2 <= c^2,
 c = m // 2, is refused.  With it the rotation axis is study column dimY // 2, as for the phantom.
@@ -82,11 +85,11 @@ def upload_volume(labels, nmat):
     return DeviceVolume(t, occupied_box(t), int(nmat))
 
 
-def volume_lines(labels, nmat, voxel_um, dimX, dimY, pixsize_um, angle):
+def volume_lines(labels, nmat, voxel_um, dimX, dimY, pixsize_um, angle, dso=None):
     """(geometry [nmat, dimX, dimY] float32 in HBM, metres; lines [nmat, dimX, dimY] float64, voxels; parameters)."""
     v = upload_volume(labels, nmat)
     geom, lines = ops.volume_project(v.labels, v.nmat, angle, (dimX, dimY), float(pixsize_um) / float(voxel_um),
-                                     float(voxel_um) * 1e-6, want_lines=True, box=v.box)
+                                     float(voxel_um) * 1e-6, want_lines=True, box=v.box, dso=dso)
     return geom, lines, _parameters(v, voxel_um)
 
 
@@ -94,12 +97,13 @@ def _parameters(v, voxel_um):
     return {'volumeShape': (tuple(int(x) for x in v.labels.shape), 'voxels'), 'voxelSize': (float(voxel_um), 'um')}
 
 
-def getVolumeFromFile(labels, nmat, voxel_um, dimX, dimY, pixsize_um, angle):
+def getVolumeFromFile(labels, nmat, voxel_um, dimX, dimY, pixsize_um, angle, dso=None):
     """(geometry [nmat, dimX, dimY] float32 in HBM, metres; parameters): the volume `labels` (an array, a tensor or an
-    upload_volume result) of voxel_um voxels at `angle` degrees on a dimX x dimY grid of pixsize_um pixels."""
+    upload_volume result) of voxel_um voxels at `angle` degrees on a dimX x dimY grid of pixsize_um pixels.  dso: None for
+    the parallel beam, else the source's distance from the rotation axis in voxels (m <= dso <= 1e30)."""
     v = upload_volume(labels, nmat)
     geom = ops.volume_project(v.labels, v.nmat, angle, (dimX, dimY), float(pixsize_um) / float(voxel_um),
-                              float(voxel_um) * 1e-6, box=v.box)
+                              float(voxel_um) * 1e-6, box=v.box, dso=dso)
     return geom, _parameters(v, voxel_um)
 
 

@@ -18,6 +18,7 @@ PSX_MAX_UMPA_SEARCH = 8
 PSX_MAX_PAGANIN = 64
 PSX_DECOMP_MAX_MAT, PSX_DECOMP_MAX_BINS, PSX_DECOMP_MAX_ENERGIES = 4, 8, 256
 PSX_FBP_MAX_ANGLES, PSX_FBP_MAX_M = 4096, 8192
+PSX_FDK_MAX_SAMPLES = 1 << 31                        # the filtered sinogram an FDK plan holds, A*n*m float32
 FBP_FILTERS = {"ramp": 0, "hann": 1, "none": 2}      # PSX_FBP_RAMP / _HANN / _NONE
 FBP_DIFFERENTIAL_FILTERS = {"hilbert": 16, "hilbert-hann": 17}   # PSX_FBP_HILBERT / _HILBERT_HANN: the line is d/d(column)
 PSX_PHANTOM_TUBES = 12
@@ -30,7 +31,7 @@ PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class PsxError(RuntimeError):
@@ -108,6 +109,7 @@ PROTOTYPES = {
     "psx_contrast_phantom_f32": (c_int, [_vp, _vp, _vp, _vp]),
     "psx_contrast_phantom_slices_u8": (c_int, [_vp, _vp, _vp]),
     "psx_volume_project_u8": (c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "psx_volume_project_cone_u8": (c_int, [_vp, c_double, _vp, _vp, _vp, _vp]),
     "psx_lcs_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp]),
     "psx_lcs_df_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp, _vp]),
     "psx_umpa_f32": (c_int, [_vpp, _vpp, c_int, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -124,6 +126,10 @@ PROTOTYPES = {
     "psx_fbp_project_f32": (c_int, [_vp, _vp, c_int, _vp, _vp]),
     "psx_fbp_adjoint_f32": (c_int, [_vp, _vp, c_int, _vp, _vp]),
     "psx_fbp_tv_step_f32": (c_int, [_vp, c_int, c_double, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "psx_fdk_plan_create": (c_int, [c_int, c_int, c_int, _dp, c_double, c_double, c_double, c_int, c_int, _vpp]),
+    "psx_fdk_plan_destroy": (c_int, [_vp]),
+    "psx_fdk_plan_bytes": (c_size_t, [_vp]),
+    "psx_fdk_f32": (c_int, [_vp, _vp, _vp, _vp]),
     "psx_decompose_f32": (c_int, [_vpp, c_int, POINTER(c_int), _dp, _dp, c_int, _dp, _dp, c_int, c_double, c_int64, _vpp, _vp, _vp, _vp]),
     "psx_debug_stamps": (c_int, [_vp]),
     "psx_debug_switch": (c_int, [c_char_p, c_int]),

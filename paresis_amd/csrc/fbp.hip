@@ -13,6 +13,8 @@
 //                  back-projection at scale 1)
 //   k_fbp_tv_step  the voxel step of total-variation reconstruction on the pair (psx_fbp_tv_step_f32): dual projection,
 //                  divergence, primal step, clamp and over-relaxation in one launch
+//   FDK (psx_fdk_*; cone beam, full turn): k_fbp_pack with the cosine pre-weight, the same filter, k_fdk_unpack into the
+//                  plan's filtered sinogram of all rows, k_fdk_backproject: a thread per voxel column and block of 8 slices
 #include "fresnel_plan.hpp"
 
 #include <complex>
@@ -52,8 +54,20 @@ template <typename W> __device__ __forceinline__ bool fbp_lit(int i, int j, int 
     return !circle || (W)(i - h) * (i - h) + (W)(j - h) * (j - h) <= (W)h * h;
 }
 
+// FDK's pre-weight of sample (r, k), the cosine of the ray's angle to the optical axis (include/paresis_hip.h, "FDK"); the
+// parallel beam has none
+struct ConeWeight { double dso, center, vcenter; };
+struct NoWeight {};
+__device__ __forceinline__ float fbp_weighted(float p, int, int, const NoWeight &) { return p; }
+__device__ __forceinline__ float fbp_weighted(float p, int r, int k, const ConeWeight &c) {
+#pragma clang fp contract(off)
+    const double dk = (double)k - c.center, dr = (double)r - c.vcenter;
+    return (float)((double)p * c.dso / sqrt(c.dso * c.dso + dk * dk + dr * dr));
+}
+
+template <typename Weight>
 __global__ __launch_bounds__(256) void k_fbp_pack(const float *__restrict__ sino, float2 *__restrict__ Z, int A, int n, int m,
-                                                  int L, int r0, int npairs) {
+                                                  int L, int r0, int npairs, Weight wt) {
     const int64_t N = (int64_t)npairs * A * L;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (int64_t)gridDim.x * blockDim.x) {
         const int k = (int)(p % L);
@@ -63,8 +77,8 @@ __global__ __launch_bounds__(256) void k_fbp_pack(const float *__restrict__ sino
         if (k < m) {
             const int r = r0 + 2 * rp;
             const int64_t q = ((int64_t)a * n + r) * m + k;
-            z.x = sino[q];
-            if (r + 1 < n) z.y = sino[q + m];
+            z.x = fbp_weighted(sino[q], r, k, wt);
+            if (r + 1 < n) z.y = fbp_weighted(sino[q + m], r + 1, k, wt);
         }
         Z[p] = z;
     }
@@ -158,6 +172,87 @@ __global__ __launch_bounds__(256) void k_fbp_backproject(FbpArgs p) {
 #pragma unroll
     for (int r = 0; r < FBP_ROWS; ++r)
         if (rb + r < p.n) p.vol[((int64_t)(rb + r) * p.m + i) * p.m + j] = lit ? acc[r] * p.scale : 0.f;
+}
+
+// ---- FDK: the filtered lines of every row, resident, and the divergent back-projector ------------------------------------
+constexpr int FDK_TILE = 16;     // a thread per voxel column (i, j) of a 16 x 16 tile
+constexpr int FDK_SLICES = 8;    // slices a thread walks down: t, w, U, u and the column tap are formed once per angle for them
+
+// Q[a][r0 + 2 rp (+ 1)][k] = Z[rp][a][k].x (.y): the filtered row pairs of a block into the plan's sinogram of all rows
+__global__ __launch_bounds__(256) void k_fdk_unpack(const float2 *__restrict__ Z, float *__restrict__ Q, int A, int n, int m, int L,
+                                                    int r0, int npairs) {
+    const int64_t N = (int64_t)npairs * A * m;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (int64_t)gridDim.x * blockDim.x) {
+        const int k = (int)(p % m);
+        const int64_t la = p / m;
+        const int a = (int)(la % A), rp = (int)(la / A);
+        const float2 z = Z[((int64_t)rp * A + a) * L + k];
+        const int r = r0 + 2 * rp;
+        const int64_t q = ((int64_t)a * n + r) * m + k;
+        Q[q] = z.x;
+        if (r + 1 < n) Q[q + m] = z.y;
+    }
+}
+
+struct FdkArgs {
+    const float *Q;           // [A][n][m]: the weighted, filtered sinogram
+    const double *cs;         // [A] cos, then [A] sin
+    float *vol;               // [n][m][m]
+    double center, vcenter, dso;
+    float scale;              // pi / (2A)
+    int A, n, m, circle;
+};
+
+// One thread per voxel column (i, j) and block of FDK_SLICES slices; the angles in ascending order, no atomics.  The four
+// taps are read from global memory: neighbouring threads in j read neighbouring columns of the same detector rows.
+__global__ __launch_bounds__(256) void k_fdk_backproject(FdkArgs p) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    const int h = p.m / 2;
+    const int j = blockIdx.x * FDK_TILE + (tid & (FDK_TILE - 1)), i = blockIdx.y * FDK_TILE + (tid >> 4);
+    const int Z0 = blockIdx.z * FDK_SLICES;
+    if (i >= p.m || j >= p.m) return;
+    const int nz = min(FDK_SLICES, p.n - Z0);
+    float *out = p.vol + ((int64_t)Z0 * p.m + i) * p.m + j;
+    const int64_t zstride = (int64_t)p.m * p.m;
+    if (!fbp_lit<int64_t>(i, j, h, p.circle)) {
+        for (int z = 0; z < nz; ++z) out[z * zstride] = 0.f;
+        return;
+    }
+    float acc[FDK_SLICES];
+#pragma unroll
+    for (int z = 0; z < FDK_SLICES; ++z) acc[z] = 0.f;
+    const double dj = (double)(j - h), di = (double)(i - h);
+    const int m = p.m, n = p.n;
+    for (int a = 0; a < p.A; ++a) {
+        const double c = p.cs[a], s = p.cs[p.A + a];
+        const double t = dj * c - di * s, w = dj * s + di * c;
+        const double U = p.dso / (p.dso + w);                       // dso + w > 0: |w| <= sqrt(2) h < m <= dso
+        const double u = t * U + p.center;
+        if (!(u > -1.0 && u < (double)m)) continue;                 // off the detector for every slice
+        const FbpTap tu = fbp_tap(u);
+        const int ku = (int)tu.fl;                                  // in [-1, m - 1]
+        const bool c0 = ku >= 0, c1 = ku + 1 < m;
+        const float U2 = (float)(U * U);
+        const float *qa = p.Q + (int64_t)a * n * m;                 // the angle's rows; every tap below is indexed inside them
+#pragma unroll
+        for (int z = 0; z < FDK_SLICES; ++z) {
+            if (z >= nz) break;
+            const double v = ((double)(Z0 + z) - p.vcenter) * U + p.vcenter;
+            if (!(v > -1.0 && v < (double)n)) continue;
+            const FbpTap tv = fbp_tap(v);
+            const int kv = (int)tv.fl;                              // in [-1, n - 1]
+            const bool r0 = kv >= 0, r1 = kv + 1 < n;
+            const int64_t o0 = (int64_t)kv * m + ku, o1 = o0 + m;   // (kv, ku) and (kv + 1, ku): read only where on the detector
+            const float q00 = r0 && c0 ? qa[o0] : 0.f, q01 = r0 && c1 ? qa[o0 + 1] : 0.f;
+            const float q10 = r1 && c0 ? qa[o1] : 0.f, q11 = r1 && c1 ? qa[o1 + 1] : 0.f;
+            const float lo = fmaf(tu.w1, q01, tu.w0 * q00), hi = fmaf(tu.w1, q11, tu.w0 * q10);
+            acc[z] = fmaf(U2, fmaf(tv.w1, hi, tv.w0 * lo), acc[z]);
+        }
+    }
+#pragma unroll
+    for (int z = 0; z < FDK_SLICES; ++z)
+        if (z < nz) out[z * zstride] = acc[z] * p.scale;
 }
 
 // ---- forward projection: sino = B^T vol, the gather form ---------------------------------------------------------------
@@ -463,6 +558,31 @@ struct psx_fbp_plan {
     PSX_REQUIRE(n >= 1 && (int64_t)n * plan->A * plan->m <= (int64_t)1 << 40 && (int64_t)n * plan->m * plan->m <= (int64_t)1 << 40, \
                 NAME ": n=%d detector rows outside [1, 2^40 elements]", n)
 
+// Z = the filtered lines (the packed ones, unless `filtered`) of the row pairs [r0, r0 + 2 npairs) of sino, each sample
+// times wt's weight: the first half of psx_fbp_f32 and of psx_fdk_f32.  Inlined into its callers, so that the library's
+// symbols stay what they were.
+template <typename Weight>
+__attribute__((always_inline)) static inline int fbp_filter_rows(psx_fbp_plan *plan, const float *sino, int n, int r0, int npairs,
+                                                                 bool filtered, Weight wt, hipStream_t st) {
+    const int A = plan->A, m = plan->m, L = plan->L;
+    float2 *const Z = plan->Z.get();
+    const int64_t N = (int64_t)npairs * A * L;
+    PSX_TIMED("k_fbp_pack", st, k_fbp_pack<<<ew_grid(N, 256), 256, 0, st>>>(sino, Z, A, n, m, L, r0, npairs, wt));
+    if (int rc = launch_check("k_fbp_pack")) return rc;
+    if (filtered) {
+        for (int rp = 0; rp < npairs; ++rp)
+            if (int rc = plan->fft.execute(FftPlan::FWD, Z + (size_t)rp * A * L, st, "rocfft_fbp_forward")) return rc;
+        if (plan->filter & PSX_FBP_DIFFERENTIAL)
+            PSX_TIMED("k_fbp_filter_hilbert", st, k_fbp_filter<true><<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->table.get(), plan->P, N));
+        else
+            PSX_TIMED("k_fbp_filter", st, k_fbp_filter<false><<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->table.get(), plan->P, N));
+        if (int rc = launch_check("k_fbp_filter")) return rc;
+        for (int rp = 0; rp < npairs; ++rp)
+            if (int rc = plan->fft.execute(FftPlan::INV, Z + (size_t)rp * A * L, st, "rocfft_fbp_inverse")) return rc;
+    }
+    return 0;
+}
+
 // vol = scale * B sino, by row blocks of the plan's max_rows: pack, with `filtered` the plan's filter, back-projection.
 // Inlined into its two entry points, so that the library's symbols stay what they were.
 __attribute__((always_inline)) static inline int fbp_backproject(psx_fbp_plan *plan, const float *sino, int n, float *vol,
@@ -473,20 +593,7 @@ __attribute__((always_inline)) static inline int fbp_backproject(psx_fbp_plan *p
     for (int r0 = 0; r0 < n; r0 += plan->max_rows) {
         const int rows = n - r0 < plan->max_rows ? n - r0 : plan->max_rows;
         const int npairs = (rows + 1) / 2;
-        const int64_t N = (int64_t)npairs * A * L;
-        PSX_TIMED("k_fbp_pack", st, k_fbp_pack<<<ew_grid(N, 256), 256, 0, st>>>(sino, Z, A, n, m, L, r0, npairs));
-        if (int rc = launch_check("k_fbp_pack")) return rc;
-        if (filtered) {
-            for (int rp = 0; rp < npairs; ++rp)
-                if (int rc = plan->fft.execute(FftPlan::FWD, Z + (size_t)rp * A * L, st, "rocfft_fbp_forward")) return rc;
-            if (plan->filter & PSX_FBP_DIFFERENTIAL)
-                PSX_TIMED("k_fbp_filter_hilbert", st, k_fbp_filter<true><<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->table.get(), plan->P, N));
-            else
-                PSX_TIMED("k_fbp_filter", st, k_fbp_filter<false><<<ew_grid(N, 256), 256, 0, st>>>(Z, plan->table.get(), plan->P, N));
-            if (int rc = launch_check("k_fbp_filter")) return rc;
-            for (int rp = 0; rp < npairs; ++rp)
-                if (int rc = plan->fft.execute(FftPlan::INV, Z + (size_t)rp * A * L, st, "rocfft_fbp_inverse")) return rc;
-        }
+        if (int rc = fbp_filter_rows(plan, sino, n, r0, npairs, filtered, NoWeight{}, st)) return rc;
         FbpArgs a;
         a.Z = Z; a.cs = plan->cs.get(); a.vol = vol; a.center = plan->center; a.scale = scale;
         a.A = A; a.n = n; a.m = m; a.L = L; a.r0 = r0; a.npairs = npairs; a.circle = plan->circle;
@@ -496,6 +603,15 @@ __attribute__((always_inline)) static inline int fbp_backproject(psx_fbp_plan *p
     }
     return 0;
 }
+
+// FDK's plan: a parallel plan for the tables, the transform and the row-block buffer, and the filtered sinogram of all rows
+struct psx_fdk_plan {
+    int n = 0;
+    double vcenter = 0.0, dso = 0.0;
+    psx_fbp_plan *base = nullptr;
+    DevBuf<float> Q;          // [A][n][m]
+    ~psx_fdk_plan() { delete base; }
+};
 
 extern "C" {
 
@@ -607,6 +723,61 @@ int psx_fbp_tv_step_f32(psx_fbp_plan *plan, int n, double lambda, int nonneg, co
         if (int rc = launch_check("k_fbp_tv_step")) return rc;
     }
     return 0;
+}
+
+int psx_fdk_plan_create(int A, int n, int m, const double *theta_deg, double center, double vcenter, double dso, int filter,
+                        int circle, psx_fdk_plan **plan) {
+    PSX_REQUIRE(plan != nullptr, "psx_fdk_plan_create: null plan pointer");
+    *plan = nullptr;
+    PSX_REQUIRE(filter == PSX_FBP_RAMP || filter == PSX_FBP_HANN || filter == PSX_FBP_NONE,
+                "psx_fdk_plan_create: filter %d is not PSX_FBP_RAMP, _HANN or _NONE (FDK has no differential form)", filter);
+    PSX_REQUIRE(n >= 1 && n <= 65535, "psx_fdk_plan_create: n=%d detector rows outside [1,65535]", n);
+    PSX_REQUIRE(A >= 1 && A <= PSX_FBP_MAX_ANGLES && m >= 2 && m <= PSX_FBP_MAX_M,
+                "psx_fdk_plan_create: A=%d angles outside [1,%d] or m=%d detector columns outside [2,%d]", A, PSX_FBP_MAX_ANGLES, m,
+                PSX_FBP_MAX_M);
+    PSX_REQUIRE((int64_t)A * n * m <= PSX_FDK_MAX_SAMPLES,
+                "psx_fdk_plan_create: the filtered sinogram of %d x %d x %d samples is outside [1, 2^31]", A, n, m);
+    PSX_REQUIRE(std::isfinite(vcenter) && std::fabs(vcenter) <= 1048576.0,
+                "psx_fdk_plan_create: vcenter=%g is not a finite row within 2^20", vcenter);
+    PSX_REQUIRE(dso >= (double)m && dso <= 1e30, "psx_fdk_plan_create: dso=%g outside [m=%d, 1e30] voxels", dso, m);
+    std::unique_ptr<psx_fdk_plan> p(new psx_fdk_plan());
+    if (int rc = psx_fbp_plan_create(A, m, theta_deg, center, filter, circle, 0, &p->base)) return rc;
+    p->n = n; p->vcenter = vcenter; p->dso = dso;
+    if (int rc = p->Q.alloc((size_t)A * n * m)) return rc;
+    *plan = p.release();
+    return 0;
+}
+
+int psx_fdk_plan_destroy(psx_fdk_plan *plan) {
+    delete plan;
+    return 0;
+}
+
+size_t psx_fdk_plan_bytes(const psx_fdk_plan *plan) { return plan ? plan->base->bytes + plan->Q.bytes() : 0; }
+
+int psx_fdk_f32(psx_fdk_plan *plan, const float *sino, float *vol, void *stream) {
+    PSX_REQUIRE(plan != nullptr, "psx_fdk_f32: null plan");
+    PSX_REQUIRE(sino != nullptr && vol != nullptr, "psx_fdk_f32: null sinogram or volume");
+    hipStream_t st = (hipStream_t)stream;
+    psx_fbp_plan *base = plan->base;
+    const int A = base->A, m = base->m, n = plan->n;
+    PSX_REQUIRE((int64_t)n * m * m <= (int64_t)1 << 40, "psx_fdk_f32: a volume of %d x %d x %d voxels is outside 2^40", n, m, m);
+    const ConeWeight wt{plan->dso, base->center, plan->vcenter};
+    for (int r0 = 0; r0 < n; r0 += base->max_rows) {
+        const int rows = n - r0 < base->max_rows ? n - r0 : base->max_rows;
+        const int npairs = (rows + 1) / 2;
+        if (int rc = fbp_filter_rows(base, sino, n, r0, npairs, base->filter != PSX_FBP_NONE, wt, st)) return rc;
+        PSX_TIMED("k_fdk_unpack", st, k_fdk_unpack<<<ew_grid((int64_t)npairs * A * m, 256), 256, 0, st>>>(
+                      base->Z.get(), plan->Q.get(), A, n, m, base->L, r0, npairs));
+        if (int rc = launch_check("k_fdk_unpack")) return rc;
+    }
+    FdkArgs a;
+    a.Q = plan->Q.get(); a.cs = base->cs.get(); a.vol = vol; a.center = base->center; a.vcenter = plan->vcenter; a.dso = plan->dso;
+    a.scale = (float)(M_PI / (2.0 * (double)A)); a.A = A; a.n = n; a.m = m; a.circle = base->circle;
+    const int tiles = (int)cdiv(m, FDK_TILE);
+    const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)cdiv(n, FDK_SLICES));
+    PSX_TIMED("k_fdk_backproject", st, k_fdk_backproject<<<grid, 256, 0, st>>>(a));
+    return launch_check("k_fdk_backproject");
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // volume.hip -- a stored volume of material labels projected at one angle: the contrast phantom's model (phantom.hip,
 // skimage radon of a slice: bilinear samples along the rotated rays, summed in row order) fed from memory instead of from 13
-// analytic discs.  The contract is in include/paresis_hip.h ("labelled voxel volume").
+// analytic discs.  The contract is in include/paresis_hip.h ("labelled voxel volume").  k_volume_project walks parallel rays,
+// k_volume_project_cone the rays that diverge from a point source ("the same volume under a point source").
 #include "common.hpp"
 
 using namespace psx;
@@ -155,11 +156,77 @@ __global__ __launch_bounds__(BLOCK) void k_volume_project(psx_volume_desc d, con
     }
 }
 
-}  // namespace
+// The divergent projection of the same volume (psx_volume_project_cone_u8): the source at depth -dso on the optical axis, the
+// study grid on the plane through the rotation axis.  One block (one wave) per (study row x, 64 study columns), a thread
+// per column y, the per-material sums in LDS as above.  A ray crosses slices and every row has its own rays, so nothing of
+// k_volume_project's sharing carries over: no run of rows on one slice, no staged box -- the labels are read from global
+// memory.  The step's magnification g and its slice z depend on (x, r) alone: they are the same for the whole wave, and so
+// is the branch on the slice's occupied box, which spares only steps whose four labels are empty (exact zeros).
+__global__ __launch_bounds__(BLOCK) void k_volume_project_cone(psx_volume_desc d, double dso, const uint8_t *__restrict__ labels,
+                                                               double *__restrict__ lines, float *__restrict__ geom) {
+#pragma clang fp contract(off)
+    extern __shared__ double acc[];                     // [nmat][BLOCK]
+    const int x = blockIdx.x, tid = threadIdx.x;
+    const int y = blockIdx.y * BLOCK + tid;
+    if (y >= d.dimY) return;                            // no barrier below: a thread only touches its own column of acc
+    for (int k = 0; k < d.nmat; ++k) acc[k * BLOCK + tid] = 0.0;
 
-extern "C" int psx_volume_project_u8(const psx_volume_desc *desc, const uint8_t *labels, double *lines, float *geom,
-                                     void *stream) {
-    const char *fn = "psx_volume_project_u8";
+    const int m = d.m, c0 = m / 2;
+    const double dc0 = (double)c0;
+    const double t0 = (double)(y - d.dimY / 2) * d.s, z0 = (double)(x - d.dimX / 2) * d.s;
+    for (int r = 0; r < m; ++r) {
+        const double rd = (double)r;
+        const double g = (dso + (double)(r - c0)) / dso;               // in (0, 2]: dso >= m
+        const double zd = (double)(d.n / 2) + floor(z0 * g + 0.5);     // |.| <= 2^31 + 2^15: compared as a double
+        if (zd < 0.0 || zd >= (double)d.n) continue;
+        const int z = (int)zd;
+        int row0 = 0, row1 = m, col0 = 0, col1 = m;
+        if (d.box) {
+            const int32_t *b = d.box + 4 * (int64_t)z;
+            row0 = b[0], row1 = b[1], col0 = b[2], col1 = b[3];
+            if (row1 <= row0) continue;
+        }
+        const uint8_t *__restrict__ sl = labels + (int64_t)z * m * m;
+        const double cpos = t0 * g + dc0;
+        const double X = d.cos_a * cpos + d.sin_a * rd + d.off_x;
+        const double Y = (-d.sin_a * cpos) + d.cos_a * rd + d.off_y;
+        // |X|, |Y| < 2^29 (|cpos| <= 2^27 + 2^13, m <= 2^13): the floors fit an int
+        const double fY = floor(Y), fX = floor(X);
+        const int minr = (int)fY, minc = (int)fX, maxr = minr + (Y > fY ? 1 : 0), maxc = minc + (X > fX ? 1 : 0);
+        if (maxr < row0 || minr >= row1 || maxc < col0 || minc >= col1) continue;
+        auto label_at = [&](int i, int j) -> int {                    // 0 outside the slice
+            if ((unsigned)i >= (unsigned)m || (unsigned)j >= (unsigned)m) return 0;
+            return sl[i * m + j];
+        };
+        const int l0 = label_at(minr, minc), l1 = label_at(minr, maxc);
+        const int l2 = label_at(maxr, minc), l3 = label_at(maxr, maxc);
+        if ((l0 | l1 | l2 | l3) == 0) continue;
+        const double dr = Y - fY, dc = X - fX;
+        const double wr = 1.0 - dr, wc = 1.0 - dc;
+        auto add = [&](int L) {                                       // k_volume_project's term
+            if (L == 0 || L > d.nmat) return;
+            const double tl = l0 == L ? 1.0 : 0.0, tr = l1 == L ? 1.0 : 0.0, bl = l2 == L ? 1.0 : 0.0, br = l3 == L ? 1.0 : 0.0;
+            const double top = wc * tl + dc * tr;
+            const double bottom = wc * bl + dc * br;
+            acc[(L - 1) * BLOCK + tid] += wr * top + dr * bottom;
+        };
+        add(l0);
+        if (l1 != l0) add(l1);
+        if (l2 != l0 && l2 != l1) add(l2);
+        if (l3 != l0 && l3 != l1 && l3 != l2) add(l3);
+    }
+    const double L = sqrt(1.0 + (t0 * t0 + z0 * z0) / (dso * dso));   // the path of a unit step in depth
+    const int64_t plane = (int64_t)d.dimX * d.dimY;
+    for (int k = 0; k < d.nmat; ++k) {
+        const double a = acc[k * BLOCK + tid] * L;
+        const int64_t o = k * plane + (int64_t)x * d.dimY + y;
+        geom[o] = (float)(a * d.voxel_m);
+        if (lines) lines[o] = a;
+    }
+}
+
+// What both entry points ask of (descriptor, labels, geometry buffer); fn is the entry point's name in the messages.
+int volume_check(const char *fn, const psx_volume_desc *desc, const uint8_t *labels, const float *geom) {
     PSX_REQUIRE(desc != nullptr, "%s: null descriptor", fn);
     PSX_REQUIRE(labels != nullptr && geom != nullptr, "%s: null labels or geometry buffer", fn);
     const psx_volume_desc d = *desc;
@@ -174,9 +241,30 @@ extern "C" int psx_volume_project_u8(const psx_volume_desc *desc, const uint8_t 
     PSX_REQUIRE(std::isfinite(d.voxel_m), "%s: voxel_m=%g", fn, d.voxel_m);
     PSX_REQUIRE(std::isfinite(d.cos_a) && std::isfinite(d.sin_a) && std::isfinite(d.off_x) && std::isfinite(d.off_y),
                 "%s: non-finite angle scalars", fn);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int psx_volume_project_u8(const psx_volume_desc *desc, const uint8_t *labels, double *lines, float *geom,
+                                     void *stream) {
+    if (int rc = volume_check("psx_volume_project_u8", desc, labels, geom)) return rc;
+    const psx_volume_desc d = *desc;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)d.dimX, (unsigned)cdiv(d.dimY, BLOCK));
     PSX_TIMED("k_volume_project", st,
               k_volume_project<<<grid, BLOCK, sizeof(double) * BLOCK * d.nmat, st>>>(d, labels, lines, geom));
     return launch_check("k_volume_project");
+}
+
+extern "C" int psx_volume_project_cone_u8(const psx_volume_desc *desc, double dso, const uint8_t *labels, double *lines,
+                                          float *geom, void *stream) {
+    if (int rc = volume_check("psx_volume_project_cone_u8", desc, labels, geom)) return rc;
+    const psx_volume_desc d = *desc;
+    PSX_REQUIRE(dso >= (double)d.m && dso <= 1e30, "psx_volume_project_cone_u8: dso=%g outside [m=%d, 1e30] voxels", dso, d.m);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)d.dimX, (unsigned)cdiv(d.dimY, BLOCK));
+    PSX_TIMED("k_volume_project_cone", st,
+              k_volume_project_cone<<<grid, BLOCK, sizeof(double) * BLOCK * d.nmat, st>>>(d, dso, labels, lines, geom));
+    return launch_check("k_volume_project_cone");
 }

@@ -7,7 +7,8 @@
                                [--retrieve-propagation [--material NAME]]
                                [--decompose [--decompose-materials A,B]]
                                [--tomography A [--tomography-modality attenuation|phase [--tomography-differential]]
-                                [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]]]
+                                [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]]
+                                [--tomography-beam parallel|cone]]
 
 With torchrun (one process per GPU) the membrane positions are strided over the ranks and the detector images are
 gathered on rank 0 over RCCL (paresis_amd/dist.py); results do not depend on the number of GPUs because every position
@@ -35,6 +36,9 @@ total-variation reconstruction (tomography.tv) with --tomography-weight W >= 0, 
 model of the phantom's piecewise constant slices, for fewer angles still.  --tomography-differential (with
 --tomography-modality phase and --tomography-method fbp only) skips the phase integration: the tracked gradient across the
 rotation axis is back-projected through a Hilbert filter, and tomography/delta_<expID> is written as before.
+--tomography-beam cone (a getVolumeFromFile sample, --tomography-method fbp, no --tomography-differential) projects the volume
+from the experiment's point source instead -- distSourceToMembrane + distMembraneToObject from the rotation axis --, takes
+the A angles on [0, 360) and reconstructs by FDK.
 """
 import argparse
 import datetime
@@ -47,7 +51,7 @@ import numpy as np
 def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False, max_shift=None, dark_field=False,
         method='lcs', window=2, search=3, propagation=False, material=None, tomography=0, tomography_modality='attenuation',
         tomography_method='fbp', tomography_iterations=0, tomography_weight=None, tomography_differential=False,
-        decompose=False, decompose_materials=None):
+        decompose=False, decompose_materials=None, tomography_beam='parallel'):
     """main.py:58-115.  Returns on rank 0 {position: (Sample, Reference[, Propag, White, ...])} with host tensors.
 
     retrieve (extension): rank 0 retrieves every bin from the run's own positions after the gather
@@ -81,12 +85,15 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
     (relative to the sinogram's largest value, as tomography.reconstruct takes it; refused for the other methods)
     reconstructs with total variation.  tomography_differential (modality 'phase' and method 'fbp' only): the scan keeps
     the tracked gradient across the rotation axis instead of the integrated phase (tomography.scan(..., differential=True))
-    and the reconstruction goes through the Hilbert filter.  exp_dict['tomographyParams'] then holds the angles, the centre,
+    and the reconstruction goes through the Hilbert filter.  tomography_beam 'cone' (a label volume, method 'fbp', not
+    differential): the volume is projected from the experiment's point source (tomography.scan(..., beam='cone')), the A
+    angles lie on [0, 360) and the reconstruction is FDK; tomographyParams then also holds 'beam', 'source_px' and
+    'row_center'.  exp_dict['tomographyParams'] then holds the angles, the centre,
     the voxel size, the modality, whether the scan was differential, the method, its iterations and its weight (None but for
     'tv'), and exp_dict['tomographyVolumes'] the {bin: [n, m, m] device tensor} volumes."""
     from . import tomography as tomo
     tomo.check_run_options(tomography, tomography_modality, tomography_method, tomography_iterations, tomography_weight,
-                           differential=tomography_differential)
+                           differential=tomography_differential, beam=tomography_beam)
     if tomography and tomography_modality == 'phase':
         from .retrieval import check_method
         check_method(method, int(exp_dict['nbExpPoints']), max_shift, dark_field)
@@ -129,6 +136,8 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
         spectral_model = spectral.model_of(experiment, decompose_materials)   # a model error fails before the images are computed
     if tomography:
         tomo._phantom(experiment.mySampleofInterest)                # another sample fails before the images are computed
+        if tomography_beam == 'cone':
+            tomo.check_diverging(experiment.mySampleofInterest)     # and so does a sample that cannot diverge
     sim = exp_dict['simulation_type']
     root = exp_dict['filepath'] + ('Fresnel_' if sim == "Fresnel" else 'RayTracing_') + str(exp_dict['expID']) + '/'
     if save:
@@ -246,7 +255,8 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
         if save:
             spectral.save_decomposition(decomposed, spectral_model.names, paths[0], exp_dict['expID'], saving_format)
     if rank == 0 and tomography:
-        angles = [180.0 * a / int(tomography) for a in range(int(tomography))]
+        turn = 360.0 if tomography_beam == 'cone' else 180.0
+        angles = [turn * a / int(tomography) for a in range(int(tomography))]
         options = {}
         if tomography_modality == 'phase':
             from .retrieval import TRACKERS
@@ -255,10 +265,13 @@ def run(exp_dict, save=True, saving_format=".tif", backend=None, retrieve=False,
             options = {k: v for k, v in options.items() if k in keep}
             if tomography_differential:
                 options['differential'] = True
+        if tomography_beam != 'parallel':
+            options['beam'] = tomography_beam
         scanned = tomo.scan(experiment, angles, modality=tomography_modality, **options)
         volumes = tomo.reconstruct(scanned, method=tomography_method, iterations=tomography_iterations or None,
                                    weight=tomography_weight)
-        exp_dict['tomographyParams'] = {k: scanned[k] for k in ('angles', 'center', 'voxel_m', 'modality', 'differential', 'energy_keV')}
+        exp_dict['tomographyParams'] = {k: scanned[k] for k in ('angles', 'center', 'voxel_m', 'modality', 'differential', 'energy_keV',
+                                                                 'beam', 'source_px', 'row_center') if k in scanned}
         exp_dict['tomographyParams'].update(method=tomography_method, iterations=int(tomography_iterations),
                                              weight=None if tomography_weight is None else float(tomography_weight))
         if save:
@@ -334,7 +347,8 @@ def main(argv=None):
         dark_field=a.dark_field, method=a.method, window=a.window, search=a.search, propagation=a.retrieve_propagation,
         material=a.material, tomography=a.tomography, tomography_modality=a.tomography_modality,
         tomography_method=a.tomography_method, tomography_iterations=a.tomography_iterations,
-        tomography_weight=a.tomography_weight, tomography_differential=a.tomography_differential, decompose=a.decompose,
+        tomography_weight=a.tomography_weight, tomography_differential=a.tomography_differential,
+        tomography_beam=a.tomography_beam, decompose=a.decompose,
         decompose_materials=None if a.decompose_materials is None else [m.strip() for m in a.decompose_materials.split(",")])
 
 

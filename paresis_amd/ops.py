@@ -1389,6 +1389,54 @@ def fbp_tv_step(plan, weight, nonneg, u, c, x, xbar_in, xbar_out, px_in, py_in, 
                                         _stream()), "psx_fbp_tv_step_f32")
     return x, xbar_out, px_out, py_out
 
+# ------------------------------------------------------------------------------------------------------ FDK
+class FdkPlan(_Plan):
+    """psx_fdk_plan (the contract is in include/paresis_hip.h): FDK reconstruction of [A, n, m] cone-beam sinograms on the
+    virtual detector through the rotation axis, taken at the A angles `theta_deg` (degrees, a full turn) from a point source
+    `dso` voxels (m <= dso <= 1e30) from the axis, about detector column `center` (None: m // 2) and optical-axis row
+    `vcenter` (None: (n - 1)/2; any real), with filter 'ramp', 'hann' or 'none', onto [n, m, m] volumes.  The plan owns the
+    filtered sinogram of all n rows besides a parallel plan's tables; `bytes` reports them."""
+    _destroy = "psx_fdk_plan_destroy"
+
+    def __init__(self, theta_deg, n, m, dso, center=None, vcenter=None, filter="ramp", circle=True, device=None):
+        try:
+            theta = [float(v) for v in theta_deg]
+        except (TypeError, ValueError):
+            raise PsxError("theta_deg must be a sequence of angles in degrees, got %r" % (theta_deg,))
+        if filter not in _lib.FBP_FILTERS:
+            raise PsxError("filter must be one of %s, got %r" % (sorted(_lib.FBP_FILTERS), filter))
+        self.theta, self.n, self.m, self.filter, self.circle = tuple(theta), int(n), int(m), filter, bool(circle)
+        self.dso = float(dso)
+        self.center = float(self.m // 2 if center is None else center)
+        self.vcenter = float((self.n - 1) / 2.0 if vcenter is None else vcenter)
+        self._create(device, "psx_fdk_plan_create", len(theta), self.n, self.m, (c_double * len(theta))(*theta),
+                     c_double(self.center), c_double(self.vcenter), c_double(self.dso), _lib.FBP_FILTERS[filter],
+                     int(self.circle))
+        self.bytes = lib().psx_fdk_plan_bytes(self._h)
+
+    def fdk(self, sino, out=None):
+        """ops.fdk on this plan."""
+        return fdk(sino, self, out=out)
+
+
+def fdk(sino, plan, out=None):
+    """FDK reconstruction (psx_fdk_f32): sino, an [A, n, m] float32 tensor in HBM (A, n, m the plan's) -> the [n, m, m]
+    float32 volume, slice Z at height Z - vcenter.  out: a caller-owned [n, m, m] float32 tensor to write into.
+    Deterministic; calls on one plan are ordered on the current stream (they share its buffers)."""
+    if not isinstance(plan, FdkPlan):
+        raise PsxError("plan must be an ops.FdkPlan, got %r" % type(plan))
+    _need(sino, torch.float32, "sino", (len(plan.theta), plan.n, plan.m))
+    _on(sino, "sino", plan.device)
+    shape = (plan.n, plan.m, plan.m)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=plan.device)
+    else:
+        _need(out, torch.float32, "out", shape)
+        _on(out, "out", plan.device)
+    with torch.cuda.device(plan.device):
+        check(lib().psx_fdk_f32(plan._h, _ptr(sino), _ptr(out), _stream()), "psx_fdk_f32")
+    return out
+
 
 class VolumeDesc(ctypes.Structure):
     """psx_volume_desc (include/paresis_hip.h)."""
@@ -1413,13 +1461,16 @@ def volume_desc(n, m, nmat, angle_deg, dims, scale, voxel_m, box=None):
     return d
 
 
-def volume_project(labels, nmat, angle_deg, dims, scale, voxel_m, want_lines=False, box=None):
+def volume_project(labels, nmat, angle_deg, dims, scale, voxel_m, want_lines=False, box=None, dso=None):
     """The thickness maps of a labelled voxel volume at one angle (psx_volume_project_u8; the contract is in
     include/paresis_hip.h): labels [n, m, m] uint8 in HBM, label k + 1 = material k < nmat -> geom [nmat, dimX, dimY]
     float32 (metres) on the dims = (dimX, dimY) study grid, whose pixel is `scale` voxels of voxel_m metres; with want_lines
     also the float64 line integrals in voxels, (geom, lines).  box: an [n, 4] int32 tensor of each slice's occupied
     (row0, row1, col0, col1), half-open, which only spares work; None: the whole slice.  The kernel applies no circle mask
-    and ignores labels above nmat: Samples.getVolumeFromFile.check_volume is the loader's check."""
+    and ignores labels above nmat: Samples.getVolumeFromFile.check_volume is the loader's check.
+    dso: None for the parallel beam; otherwise the distance in voxels, m <= dso <= 1e30, from a point source to the rotation
+    axis, and the projection is the divergent one (psx_volume_project_cone_u8): the study grid is the virtual detector
+    through the axis, the lines are path lengths in voxels along the diverging rays."""
     _need(labels, torch.uint8, "labels")
     if labels.dim() != 3 or labels.shape[1] != labels.shape[2]:
         raise PsxError("labels must be [n, m, m], got shape %s" % (tuple(labels.shape),))
@@ -1433,6 +1484,10 @@ def volume_project(labels, nmat, angle_deg, dims, scale, voxel_m, want_lines=Fal
     with torch.cuda.device(labels.device):
         geom = torch.empty((d.nmat, d.dimX, d.dimY), dtype=torch.float32, device=labels.device)
         lines = torch.empty((d.nmat, d.dimX, d.dimY), dtype=torch.float64, device=labels.device) if want_lines else None
-        check(lib().psx_volume_project_u8(ctypes.byref(d), _ptr(labels), _ptr(lines), _ptr(geom), _stream()),
-              "psx_volume_project_u8")
+        if dso is None:
+            check(lib().psx_volume_project_u8(ctypes.byref(d), _ptr(labels), _ptr(lines), _ptr(geom), _stream()),
+                  "psx_volume_project_u8")
+        else:
+            check(lib().psx_volume_project_cone_u8(ctypes.byref(d), c_double(float(dso)), _ptr(labels), _ptr(lines), _ptr(geom),
+                                                   _stream()), "psx_volume_project_cone_u8")
     return (geom, lines) if want_lines else geom

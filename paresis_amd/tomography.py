@@ -1,4 +1,4 @@
-"""Parallel-beam tomography of the contrast phantom or of a labelled voxel volume: the inverse of the projections the package simulates and retrieves.
+"""Parallel- and cone-beam tomography of the contrast phantom or of a labelled voxel volume: the inverse of the projections the package simulates and retrieves.
 
     fbp(sinogram, angles_deg, ...)      filtered back-projection on the GPU (csrc/fbp.hip, ops.FbpPlan; the contract is in
                                         include/paresis_hip.h): [A, n, m] maps, one per angle -> [n, m, m], a slice per
@@ -6,6 +6,8 @@
                                         map in physical units (phi in radians, -ln T) gives the quantity per voxel length.
                                         filter='hilbert' | 'hilbert-hann': the sinogram is DIFFERENTIAL, d/d(column) of
                                         those integrals per detector pixel, and is back-projected through a Hilbert filter.
+    fdk(sinogram, angles_deg, source_px, ...)   FDK of a full-turn cone-beam scan on the virtual detector through the axis
+                                        (ops.FdkPlan, k_fdk_backproject): the source source_px voxels from the axis
     forward_project(vol, angles_deg, ...)    the matched pair behind the iterative methods (ops.fbp_project / fbp_adjoint):
     back_project(sinogram, angles_deg, ...)  B^T vol, the exact transpose of fbp's interpolation, and B sinogram, unscaled
     sirt(sinogram, angles_deg, iterations, ..., nonneg)   SIRT and CGLS on min |B^T x - b|: what few angles call for,
@@ -15,12 +17,17 @@
     delta_volume(vol, energy_keV, voxel_m)   phi = -k * integral(delta) dl  ->  delta = -vol/(k*voxel), k = getk(E)
     mu_volume(vol, voxel_m)                  -ln T = integral(mu) dl         ->  mu = vol/voxel (1/m)
     project(sample, energy_keV, angles_deg, dims, pixel_um)   the sample's ideal sinograms phi and -ln T on the study grid
-    scan(experiment, angles_deg, modality, differential)      the real chain once per angle -> sinograms per energy bin
+    scan(experiment, angles_deg, modality, differential, beam)   the real chain once per angle -> sinograms per energy bin
     rotation_center(experiment)                               the detector column of the rotation axis of such a scan
+    optical_row(experiment), source_distance(experiment)      the detector row of the optical axis; the source's distance (m)
     save_volume(vol, path, fmt)
 
-The beam is treated as parallel: no fan- or cone-beam weighting.  At the magnification of the shipped experiments
-(M ~ 1.03) that is the synchrotron case.  Two samples have a three-dimensional description, projected at Sample.myAngle by
+By default the beam is treated as parallel.  At the magnification of the shipped experiments (M ~ 1.03) that is the
+synchrotron case.  A laboratory source is a point: scan(..., beam='cone') projects a label volume along the rays that diverge
+from it (the source at source_distance(experiment) from the rotation axis, the sinogram on the virtual detector through the
+axis, whose pixel is the voxel) over a full turn, and reconstruct undoes it by FDK (Feldkamp, Davis, Kress 1984): method
+'fbp' on a cone scan.  The contrast phantom's kernel is analytic and parallel; contrast_phantom_volume gives it as a label
+volume.  Two samples have a three-dimensional description, projected at Sample.myAngle by
 the same model (scikit-image radon of a slice): the contrast phantom (Samples/generateContrastPhantom.py: 13 material
 discs on a slice) and a volume of material labels the user brings (Samples/getVolumeFromFile.py: uint8 [n, m, m], from
 the sample's myVolumeFile or set as myVolume).  project and scan refuse every other sample.
@@ -33,9 +40,11 @@ followed by a Hilbert transform.  No two-dimensional integration, with its mirro
 along whole rows, is run.
 
     python -m paresis_amd.main --tomography A [--tomography-modality attenuation|phase [--tomography-differential]]
-                               [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]] ...
+                               [--tomography-method fbp|sirt|cgls|tv --tomography-iterations K [--tomography-weight W]]
+                               [--tomography-beam parallel|cone] ...
 """
 import collections
+import contextlib
 import os
 
 import numpy as np
@@ -44,10 +53,12 @@ from . import _lib
 from .getk import getk
 
 MODALITIES = ("attenuation", "phase")
+BEAMS = ("parallel", "cone")
 PHANTOM_FUNCTION = "generateContrastPhantom"
 VOLUME_FUNCTION = "getVolumeFromFile"
 ROTATABLE_FUNCTIONS = (PHANTOM_FUNCTION, VOLUME_FUNCTION)
 _plans = {}
+_fdk_plans = {}
 
 
 def _angles(angles_deg):
@@ -96,6 +107,29 @@ def fbp(sinogram, angles_deg, center=None, filter='ramp', circle=True):
     from . import ops
     sinogram, angles = _sinogram(sinogram, angles_deg)
     return ops.fbp(sinogram, _plan(sinogram.device, angles, int(sinogram.shape[2]), center, filter, circle))
+
+
+def fdk(sinogram, angles_deg, source_px, center=None, row_center=None, filter='ramp', circle=True):
+    """FDK reconstruction of an [A, n, m] float32 CUDA tensor (or a sequence of A n x m maps): a cone-beam scan on the
+    virtual detector through the rotation axis (pixel = voxel) at angles_deg, A angles in degrees that cover a full turn
+    evenly, from a point source source_px voxels from the axis (m <= source_px <= 1e30) -> the [n, m, m] float32 volume in
+    fbp's orientation and fbp's unit.  center: the axis's detector column (None: m // 2; rotation_center for a scan);
+    row_center: the detector row of the optical axis, any real (None: (n - 1)/2; optical_row for a scan); slice Z lies at
+    height Z - row_center.  filter: 'ramp', 'hann' or 'none'.  One plan per (device, A, n, m, angles, source_px, center,
+    row_center, filter, circle) is kept for the process's lifetime; it holds the filtered sinogram, A*n*m float32."""
+    import torch
+    from . import ops
+    sinogram, angles = _sinogram(sinogram, angles_deg)
+    n, m = int(sinogram.shape[1]), int(sinogram.shape[2])
+    dev = sinogram.device
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = (index, n, m, angles, float(source_px), float(m // 2 if center is None else center),
+           float((n - 1) / 2.0 if row_center is None else row_center), str(filter), bool(circle))
+    plan = _fdk_plans.get(key)
+    if plan is None:
+        plan = _fdk_plans[key] = ops.FdkPlan(angles, n, m, key[4], center=key[5], vcenter=key[6], filter=filter, circle=circle,
+                                             device=torch.device("cuda", index))
+    return ops.fdk(sinogram, plan)
 
 
 def forward_project(vol, angles_deg, center=None, circle=True):
@@ -292,24 +326,50 @@ def _turn(sample, angle, dims, pixel_um, ov=1):
     sample.getMyGeometry(dims, pixel_um, ov)
 
 
-def project(sample, energy_keV, angles_deg, dims, pixel_um):
+def check_diverging(sample):
+    """ValueError unless `sample` can be projected from a point source: a label volume."""
+    if getattr(sample, "myGeometryFunction", "") != VOLUME_FUNCTION:
+        raise ValueError("a diverging beam needs a %s sample (the contrast phantom's kernel is analytic and parallel; "
+                         "contrast_phantom_volume gives it as a label volume), got %r"
+                         % (VOLUME_FUNCTION, getattr(sample, "myGeometryFunction", "")))
+
+
+@contextlib.contextmanager
+def _diverging(sample, source_distance_m):
+    """A context in which `sample` projects from a point source source_distance_m metres from its axis (None: as it is)."""
+    if source_distance_m is None:
+        yield
+        return
+    check_diverging(sample)
+    before = getattr(sample, "mySourceDistance", None)
+    sample.mySourceDistance = float(source_distance_m)
+    try:
+        yield
+    finally:
+        sample.mySourceDistance = before
+
+
+def project(sample, energy_keV, angles_deg, dims, pixel_um, source_distance_m=None):
     """The ideal sinograms of `sample` (an AnalyticalSample with delta / beta at energy_keV whose geometry function is the
     contrast phantom's or getVolumeFromFile) on a dims = (dimX, dimY) grid of pixel_um pixels ->
     {'phi': [A, dimX, dimY] float32 (radians, -k*sum delta*t), 'logT': [A, dimX, dimY] float32 (-ln of the transmitted
     intensity, 2k*sum beta*t)}.  Per angle the sample is turned (myAngle), its geometry rebuilt (psx_contrast_phantom_f32
-    or psx_volume_project_u8) and a unit intensity sent through setWaveRT.  The sample is left at its last angle."""
+    or psx_volume_project_u8) and a unit intensity sent through setWaveRT.  The sample is left at its last angle.
+    source_distance_m: None for the parallel beam; otherwise a label volume is projected from a point source that many
+    metres from its axis (psx_volume_project_cone_u8; its mySourceDistance is set for the call and restored)."""
     import torch
     _phantom(sample)
     dims = (int(dims[0]), int(dims[1]))
     one = None
     phi, logT = [], []
-    for angle in _angles(angles_deg):
-        _turn(sample, angle, dims, pixel_um)
-        if one is None:
-            one = torch.ones(dims, dtype=torch.float32, device=sample.geometry_dev().device)
-        I, p, _ = sample.setWaveRT(one, energy_keV)
-        phi.append(p.to(torch.float32))
-        logT.append(-torch.log(I))
+    with _diverging(sample, source_distance_m):
+        for angle in _angles(angles_deg):
+            _turn(sample, angle, dims, pixel_um)
+            if one is None:
+                one = torch.ones(dims, dtype=torch.float32, device=sample.geometry_dev().device)
+            I, p, _ = sample.setWaveRT(one, energy_keV)
+            phi.append(p.to(torch.float32))
+            logT.append(-torch.log(I))
     return {'phi': torch.stack(phi), 'logT': torch.stack(logT)}
 
 
@@ -329,12 +389,27 @@ def rotation_center(experiment):
     return (dimY // 2 - (ov - 1) / 2.0) / ov
 
 
+def optical_row(experiment):
+    """The detector row of the optical axis of a scan of `experiment`: rotation_center's formula on the study grid's axis-0
+    length, (dimX // 2 - (ov - 1)/2)/ov.  The projectors put height 0 on study row dimX // 2.  Needs no GPU."""
+    ov = int(experiment.exp_dict['overSampling'])
+    dimX = int(experiment.exp_dict['studyDimensions'][0])
+    return (dimX // 2 - (ov - 1) / 2.0) / ov
+
+
+def source_distance(experiment):
+    """The distance from the source to the rotation axis in metres: distSourceToMembrane + distMembraneToObject, the
+    denominator of the chain's magnification.  Needs no GPU."""
+    ed = experiment.exp_dict
+    return float(ed['distSourceToMembrane']) + float(ed['distMembraneToObject'])
+
+
 def voxel_size(experiment):
     """The voxel of a scan's volume in metres: the detector pixel demagnified to the object, p/M."""
     return float(experiment.myDetector.det_param['myPixelSize']) * 1e-6 / float(experiment.exp_dict['magnification'])
 
 
-def scan(experiment, angles_deg, modality='attenuation', differential=False, **retrieve_options):
+def scan(experiment, angles_deg, modality='attenuation', differential=False, beam='parallel', **retrieve_options):
     """Run the chain of `experiment` (an Experiment, or the exp_dict of one) once per angle of angles_deg, all of its
     nbExpPoints membrane positions each time, and collect one map per angle and energy bin ->
     {'sinograms': {bin: [A, n, m] float32 tensor}, 'angles': the angles, 'center': rotation_center(experiment),
@@ -349,12 +424,18 @@ def scan(experiment, angles_deg, modality='attenuation', differential=False, **r
     through the Hilbert filter.
     The sample of interest must be the contrast phantom or a label volume (ValueError otherwise): per angle its myAngle is
     set and its geometry rebuilt on the study grid.  A membrane that has a geometry function gets its geometry per position as main.run
-    does; an injected one keeps the geometry it has."""
+    does; an injected one keeps the geometry it has.
+    beam='cone': the sample (a label volume; the contrast phantom is refused, and so is differential=True) is projected
+    from the experiment's point source, source_distance(experiment) from the rotation axis -- its mySourceDistance is set
+    for the scan and restored --, the angles are meant to cover a full turn, and the result also holds 'beam',
+    'source_px' (that distance in voxels of voxel_size) and 'row_center' (optical_row): what reconstruct's FDK needs.  A
+    parallel scan's result has none of the three."""
     import torch
     from . import retrieval
     if modality not in MODALITIES:
         raise ValueError("modality must be one of %s, got %r" % (", ".join(MODALITIES), modality))
     check_differential(differential, modality, DEFAULT_METHOD)
+    check_beam(beam, differential, DEFAULT_METHOD)
     if isinstance(experiment, dict):
         from .Experiment import Experiment
         experiment = Experiment(experiment)
@@ -367,8 +448,25 @@ def scan(experiment, angles_deg, modality='attenuation', differential=False, **r
     elif retrieve_options:
         raise ValueError("%s are options of modality='phase'" % ", ".join(sorted(retrieve_options)))
     angles = list(_angles(angles_deg))
-    membrane = experiment.myMembrane
     sinos = {}
+    cone = {}
+    if beam == 'cone':
+        cone = {'beam': beam, 'source_px': source_distance(experiment) / voxel_size(experiment),
+                'row_center': optical_row(experiment)}
+    with _diverging(sample, source_distance(experiment) if cone else None):
+        _scan_angles(experiment, sample, angles, modality, differential, retrieve_options, sinos)
+    return dict({'sinograms': {b: torch.stack(v) for b, v in sinos.items()}, 'angles': angles,
+                 'center': rotation_center(experiment), 'voxel_m': voxel_size(experiment), 'modality': modality,
+                 'differential': bool(differential), 'energy_keV': float(ed['meanEnergy'])}, **cone)
+
+
+def _scan_angles(experiment, sample, angles, modality, differential, retrieve_options, sinos):
+    """scan's loop: the chain at every angle, its maps appended to sinos[bin]."""
+    import torch
+    from . import retrieval
+    ed = experiment.exp_dict
+    npos = int(ed['nbExpPoints'])
+    membrane = experiment.myMembrane
     for angle in angles:
         _turn(sample, angle, ed['studyDimensions'], ed['studyPixelSize'], ed['overSampling'])
         ed['meanEnergy'] = 0                       # every angle is a run of its own (the chain folds the positions' means into it)
@@ -391,9 +489,6 @@ def scan(experiment, angles_deg, modality='attenuation', differential=False, **r
                 maps = {b: r['phi'].clone() for b, r in retrieval.retrieve(results, params, **retrieve_options).items()}
         for b, v in maps.items():
             sinos.setdefault(b, []).append(v)
-    return {'sinograms': {b: torch.stack(v) for b, v in sinos.items()}, 'angles': angles,
-            'center': rotation_center(experiment), 'voxel_m': voxel_size(experiment), 'modality': modality,
-            'differential': bool(differential), 'energy_keV': float(ed['meanEnergy'])}
 
 
 # The reconstruction methods, keyed by what the user says.  Each row: the solver, and whether the method takes (and then
@@ -443,11 +538,25 @@ def check_differential(differential, modality, method):
                          "iterative methods solve B^T x = b for integral data" % (method,))
 
 
-def check_run_options(angles, modality, method, iterations, weight, differential=False):
+def check_beam(beam, differential, method):
+    """The cone beam's rules (ValueError): an integral scan, reconstructed by method 'fbp', which is then FDK."""
+    if beam not in BEAMS:
+        raise ValueError("beam must be one of %s, got %r" % (", ".join(BEAMS), beam))
+    if beam == 'cone' and differential:
+        raise ValueError("a cone-beam scan has no differential form: the Hilbert-filter back-projection is parallel-beam")
+    if beam == 'cone' and method != 'fbp':
+        raise ValueError("method %r has no cone-beam form" % (method,))
+
+
+def check_run_options(angles, modality, method, iterations, weight, differential=False, beam='parallel'):
     """The rules of main.run's tomography options (ValueError; needs no GPU): `angles` projections, 0 for no tomography;
     iterations 0 for none."""
     if modality not in MODALITIES:
         raise ValueError("tomography_modality must be one of %s, got %r" % (", ".join(MODALITIES), modality))
+    if beam not in BEAMS:
+        raise ValueError("tomography_beam must be one of %s, got %r" % (", ".join(BEAMS), beam))
+    if beam != BEAMS[0] and not angles:
+        raise ValueError("tomography_beam is an option of tomography")
     if differential and not angles:
         raise ValueError("tomography_differential is an option of tomography")
     check_differential(differential, modality, method)
@@ -458,12 +567,14 @@ def check_run_options(angles, modality, method, iterations, weight, differential
     if weight is not None and not angles:
         raise ValueError("tomography_weight is an option of tomography")
     check_reconstruction(method, iterations or None, weight=weight)
+    check_beam(beam, differential, method)
     if int(angles) < 0 or int(angles) > _lib.PSX_FBP_MAX_ANGLES:
         raise ValueError("tomography takes 1 to %d angles, got %r" % (_lib.PSX_FBP_MAX_ANGLES, angles))
 
 
 def add_tomography_options(ap):
-    """--tomography and --tomography-modality, -differential, -method, -iterations, -weight on an argparse parser: main.py's."""
+    """--tomography and --tomography-modality, -differential, -method, -iterations, -weight, -beam on an argparse parser:
+    main.py's."""
     iterative = "|".join(m for m, row in RECONSTRUCTIONS.items() if row.iterations)
     ap.add_argument("--tomography", type=int, default=0, metavar="A",
                     help="contrast-phantom and label-volume (getVolumeFromFile) samples: scan A angles (1..%d) on [0, 180) after "
@@ -483,20 +594,25 @@ def add_tomography_options(ap):
     ap.add_argument("--tomography-weight", type=float, default=None, metavar="W",
                     help="--tomography-method %s: the weight of the total variation, relative to the sinogram's largest "
                          "value (>= 0)" % "|".join(REGULARISED_METHODS))
+    ap.add_argument("--tomography-beam", default=BEAMS[0], choices=BEAMS,
+                    help="--tomography: parallel rays (default), or cone: a label-volume sample is projected from the experiment's "
+                         "point source, the A angles lie on [0, 360) and --tomography-method fbp reconstructs by FDK")
 
 
 def check_tomography_options(ap, a):
-    """The rules of add_tomography_options' six, as ap.error: all are options of --tomography, and which of them the method
-    takes."""
+    """The rules of add_tomography_options' seven, as ap.error: all are options of --tomography, and which of them the
+    method and the beam take."""
     if a.tomography < 0:
         ap.error("--tomography takes a number of angles >= 1")
     for option, given in (("modality", a.tomography_modality != MODALITIES[0]), ("method", a.tomography_method != DEFAULT_METHOD),
                           ("iterations", a.tomography_iterations != 0), ("weight", a.tomography_weight is not None),
-                          ("differential", a.tomography_differential)):
+                          ("differential", a.tomography_differential), ("beam", a.tomography_beam != BEAMS[0])):
         if given and not a.tomography:
             ap.error("--tomography-%s is an option of --tomography" % option)
     if a.tomography_differential and (a.tomography_modality != 'phase' or a.tomography_method != DEFAULT_METHOD):
         ap.error("--tomography-differential goes with --tomography-modality phase and --tomography-method fbp, and only with them")
+    if a.tomography_beam == 'cone' and (a.tomography_differential or a.tomography_method != DEFAULT_METHOD):
+        ap.error("--tomography-beam cone goes with --tomography-method fbp (FDK) and without --tomography-differential")
     row = RECONSTRUCTIONS[a.tomography_method]
     if row.weight != (a.tomography_weight is not None):
         ap.error("--tomography-weight W >= 0 goes with --tomography-method tv, and only with it")
@@ -519,8 +635,13 @@ def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=No
     holds d(phi)/d(column) and goes through the Hilbert filter: filter 'ramp' then means 'hilbert' and 'hann' means
     'hilbert-hann', 'none' is refused, and so is every method but 'fbp' (ValueError): sirt, cgls and tv solve B^T x = b for
     integral data, and an iterative solver on the differentiated operator is out of scope here.  The conversion by
-    delta_volume is the same."""
+    delta_volume is the same.
+    A cone-beam scan (scanned['beam'] == 'cone', scan(..., beam='cone'); a dict without the key is a parallel one) is
+    reconstructed by FDK -- that is what method 'fbp' means for it -- with the scan's 'source_px' and 'row_center'; every
+    other method is refused (ValueError)."""
     check_reconstruction(method, iterations, nonneg, weight)
+    cone = scanned.get('beam', BEAMS[0]) == 'cone'
+    check_beam(scanned.get('beam', BEAMS[0]), scanned.get('differential', False), method)
     if scanned.get('differential', False):
         check_differential(True, scanned['modality'], method)
         if filter not in DIFFERENTIAL_FILTER_OF:
@@ -534,7 +655,11 @@ def reconstruct(scanned, filter='ramp', circle=True, method='fbp', iterations=No
     for b, s in scanned['sinograms'].items():
         if row.weight:
             options['weight'] = float(weight) * float(s.abs().max())
-        vol = row.solver(s, scanned['angles'], center=scanned['center'], circle=circle, **options)
+        if cone:
+            vol = fdk(s, scanned['angles'], scanned['source_px'], center=scanned['center'], row_center=scanned['row_center'],
+                      circle=circle, **options)
+        else:
+            vol = row.solver(s, scanned['angles'], center=scanned['center'], circle=circle, **options)
         out[b] = (mu_volume(vol, scanned['voxel_m']) if scanned['modality'] == 'attenuation'
                   else delta_volume(vol, scanned['energy_keV'], scanned['voxel_m']))
     return out

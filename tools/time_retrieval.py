@@ -1,6 +1,6 @@
 """Time the phase retrieval's kernels against their byte price.
 
-    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project] [--tv] [--volume] [--decompose]
+    python tools/time_retrieval.py [--reps 20] [--host] [--umpa-only] [--paganin] [--fbp] [--project] [--tv] [--volume] [--decompose] [--fdk]
 
 k_lcs reads 2K images and writes 3: 4*n*m*(2K + 3) bytes; k_lcs_df (LCS-DF, the dark-field column) reads the same and writes
 4: 4*n*m*(2K + 4).  The two are timed in the same process, alternating launch by launch on the same inputs.  The
@@ -48,6 +48,12 @@ and Gauss-Newton step plus one pass for the residual, counted from the steps the
 rate -- the time is given as float64 FMA slots per exp.  Beside it: the same iteration written with torch operations in
 float64 (torch_decompose below, kept in this tool only; every pixel takes the kernel's largest step count), timed with a host
 clock around a synchronised loop.
+
+--fdk times the cone beam's kernels beside their parallel counterparts at (A, n, m) = (360, 64, 512): k_fdk_backproject beside
+k_fbp_backproject on one sinogram (per voxel, angle and slice FDK reads four samples from cache where the parallel kernel
+reads two from LDS, and forms a row coordinate in float64), and k_volume_project_cone beside k_volume_project on a random
+8-material volume of 64 slices of 512 x 512 at 30 degrees (the cone kernel reads its labels from global memory and divides
+once per step).
 """
 import argparse
 import ctypes
@@ -411,6 +417,35 @@ def volume_case(dimX, dimY, pix_um, reps):
     run("random 8-material volume", v, 8, True)
 
 
+def fdk_case(A, n, m, reps):
+    """The cone beam's two kernels beside their parallel counterparts: k_fdk_backproject / k_fbp_backproject on one [A, n, m]
+    sinogram, k_volume_project_cone / k_volume_project on an n-slice random 8-material volume of m x m slices at 30 degrees
+    (s = 1, the study grid n x m), the source 3 m voxels from the axis."""
+    from paresis_amd.Samples.getVolumeFromFile import upload_volume
+    theta = [360.0 * a / A for a in range(A)]
+    dso = 3.0 * m
+    g = torch.Generator(device="cuda").manual_seed(A + n + m)
+    sino = torch.rand((A, n, m), device="cuda", generator=g, dtype=torch.float32)
+    flat, cone = ops.FbpPlan(theta, m), ops.FdkPlan(theta, n, m, dso)
+    (t_fbp,) = _kernel_us(("k_fbp_backproject",), lambda: ops.fbp(sino, flat), reps)
+    t_fdk, t_unpack = _kernel_us(("k_fdk_backproject", "k_fdk_unpack"), lambda: ops.fdk(sino, cone), reps)
+    updates = float(A) * n * m * m
+    print("A=%d n=%d m=%d  k_fbp_backproject %.1f us (%.2f G voxel-angles/s)  k_fdk_backproject %.1f us (%.2f G/s) = %.2f x; "
+          "k_fdk_unpack %.1f us; plans %.1f and %.1f MB"
+          % (A, n, m, t_fbp, updates / t_fbp / 1e3, t_fdk, updates / t_fdk / 1e3, t_fdk / t_fbp, t_unpack, flat.bytes / 1e6,
+             cone.bytes / 1e6))
+    d2 = (torch.arange(m, device="cuda") - m // 2) ** 2
+    inside = (d2[:, None] + d2[None, :] <= (m // 2) ** 2).to(torch.uint8)
+    lab = torch.randint(1, 9, (n, m, m), device="cuda", generator=g, dtype=torch.uint8) * inside
+    v = upload_volume(lab, 8)
+    (t_par,) = _kernel_us(("k_volume_project",), lambda: ops.volume_project(v.labels, 8, 30.0, (n, m), 1.0, 1e-6, box=v.box), reps)
+    (t_cone,) = _kernel_us(("k_volume_project_cone",),
+                           lambda: ops.volume_project(v.labels, 8, 30.0, (n, m), 1.0, 1e-6, box=v.box, dso=dso), reps)
+    steps = float(n) * m * m
+    print("    %d slices of %d x %d, 8 materials: k_volume_project %.1f us (%.2f G steps/s)  k_volume_project_cone %.1f us "
+          "(%.2f G steps/s) = %.2f x" % (n, m, m, t_par, steps / t_par / 1e3, t_cone, steps / t_cone / 1e3, t_cone / t_par))
+
+
 def _decompose_model():
     """20-80 keV at 2 keV in bins of 8, 8 and 15 energies; a soft and a bone-like material (1/m)."""
     E = np.arange(20.0, 81.0, 2.0)
@@ -482,7 +517,12 @@ def main():
     ap.add_argument("--tv", action="store_true", help="time psx_fbp_tv_step_f32 and an iteration of tomography.tv only")
     ap.add_argument("--volume", action="store_true", help="time psx_volume_project_u8 against psx_contrast_phantom_f32 only")
     ap.add_argument("--decompose", action="store_true", help="time psx_decompose_f32 against the same iteration in torch operations only")
+    ap.add_argument("--fdk", action="store_true",
+                    help="time k_fdk_backproject beside k_fbp_backproject and k_volume_project_cone beside k_volume_project only")
     a = ap.parse_args()
+    if a.fdk:
+        fdk_case(360, 64, 512, max(a.reps // 4, 2))
+        return
     if a.decompose:
         decompose_case(2048, 2048, a.reps)
         return

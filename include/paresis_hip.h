@@ -424,9 +424,12 @@ int psx_volume_project_cone_u8(const psx_volume_desc *desc, double dso, const ui
  * LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021) over K positions of one energy bin: per pixel,
  *   R_k ~ x0*S_k + x1*g0_k + x2*g1_k,  (g0, g1) = np.gradient(R_k) (unit spacing, edge_order=1, float32 differences),
  *   M = sum_k a_k a_k^T and v = sum_k a_k R_k with a_k = (S_k, g0_k, g1_k) in float64, M x = v solved in float64;
- *   x = (1, 0, 0) exactly when det M <= 1e-12*M00*M11*M22 or the solved x0 <= 0;
+ *   x = (1, 0, 0) exactly when det M <= 1e-12*M00*M11*M22 or the solved x0 <= 0 (or is not a finite number);
  *   transmission = 1/x0, dx = x1 (axis 0), dy = x2 (axis 1), detector pixels, the sign of the chain's Dxreal / Dyreal;
  *   max_shift > 0 clamps dx, dy into [-max_shift, max_shift] (0: no clamp).
+ *   Non-finite input (psx_lcs_df_f32 too): a pixel reads its own S_k and R_k and the four neighbours of R_k at the clamped
+ *   indices; if one of these samples is NaN or +-inf for some k, the pixel returns the fallback, (1, 0, 0) or (1, 0, 0, 0).
+ *   Every other pixel is untouched: it has the bits it has on finite images.
  * S, R: HOST arrays of K in [3, PSX_MAX_LCS] device pointers to n x m float32 images (n, m >= 3); one launch reads each
  * image once.  transmission, dx, dy: n x m float32, written. */
 #define PSX_MAX_LCS 64

@@ -4,7 +4,8 @@
 // LCS ("Low Coherence System", Quenot et al., Optica 8, 1412, 2021), per detector pixel, over K positions:
 //   R_k ~ x0*S_k + x1*g0_k + x2*g1_k,   (g0, g1) = np.gradient(R_k) (unit spacing, edge_order=1),
 //   M = sum_k a_k a_k^T, v = sum_k a_k R_k with a_k = (S_k, g0_k, g1_k), in float64;  M x = v;
-//   transmission = 1/x0, (dx, dy) = (x1, x2);  x = (1, 0, 0) when det M <= 1e-12 M00 M11 M22 or x0 <= 0.
+//   transmission = 1/x0, (dx, dy) = (x1, x2);  x = (1, 0, 0) when det M <= 1e-12 M00 M11 M22 or x0 <= 0, and where a sample
+//   the pixel reads is not finite (det or x0 is then NaN or infinite, and every test refuses those).
 // LCS-DF (psx_lcs_df_f32; the diffusion term of the X-ray Fokker-Planck model, Morgan & Paganin, Sci. Rep. 9, 17465, 2019):
 //   R_k ~ x0*S_k + x1*g0_k + x2*g1_k + x3*L_k, L_k the edge-replicated 5-point Laplacian of R_k in float64;
 //   4x4 LDL^T without pivoting; x = (1, 0, 0, 0) when a pivot <= 0, prod d_i <= 1e-12 M00 M11 M22 M33, or x0 <= 0;
@@ -72,7 +73,8 @@ __global__ __launch_bounds__(LCS_BX * LCS_BY) void k_lcs(SpecklePtrs p, int K, i
         const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
         const double inv = 1.0 / det;
         const double x0 = (c00 * v0 + c01 * v1 + c02 * v2) * inv;
-        if (x0 > 0.0) {
+        // x0 = +inf: an interior pixel whose own R_k is +inf has finite M and an infinite v, so only this test sees it
+        if (x0 > 0.0 && x0 < INFINITY) {
             t = (float)(1.0 / x0);
             x = (float)((c01 * v0 + c11 * v1 + c12 * v2) * inv);
             y = (float)((c02 * v0 + c12 * v1 + c22 * v2) * inv);

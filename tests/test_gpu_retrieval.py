@@ -169,6 +169,94 @@ def test_integrate_known_answer():
     assert err <= 1e-4
 
 
+# ------------------------------------------------------------------- against the exact and the restated references
+@pytest.mark.parametrize("n,m,K,seed,max_shift", orl.LCS_CASES)
+def test_lcs_matches_exact_reference(n, m, K, seed, max_shift):
+    """k_lcs against the contract solved in exact rational arithmetic, no pixel left out.  The bound is the float32 output's
+    rounding plus 8 times what float64 costs on the input (Y, measured on the CPU between the kernel's restatement and the
+    exact solution; tests/test_retrieval_host.py holds 8 Y <= 2^-24 and shows that float32 sums, a wrong border spacing, a
+    wrapped neighbour and a dropped last position exceed the bound 10 times and more)."""
+    S, R, ref, f64, Y = orl.lcs_parity(n, m, K, seed)
+    got = _gpu_lcs(S, R, max_shift=max_shift)
+    orl.check_parity("lcs %dx%d K=%d max_shift %s" % (n, m, K, max_shift), got, ref, Y, orl.MAPS, max_shift)
+
+
+def test_lcs_matches_exact_reference_on_steep_images():
+    """The same bound on images whose neighbours differ by more than a factor of two: there the float32 difference of the
+    gradient rounds, and differences formed in float64 miss the bound (tests/test_retrieval_host.py: 10 times and more)."""
+    n, m, K, seed = orl.LCS_STEEP_CASE
+    S, R, ref, f64, Y = orl.lcs_parity(n, m, K, seed, steep=True)
+    orl.check_parity("lcs %dx%d K=%d steep" % (n, m, K), _gpu_lcs(S, R), ref, Y, orl.MAPS)
+
+
+def test_lcs_nonfinite_pixels_fall_back():
+    """A NaN, a +inf and a -inf in S_k and in R_k at interior, edge and corner pixels: the pixels that read one return
+    (1, 0, 0), every other pixel keeps the bits of the run on the clean images (include/paresis_hip.h)."""
+    S, R = orl.case_inputs(orl.exact_model, 9, 66, 5, 2)
+    Sb, Rb = orl.nonfinite_inputs(S, R)
+    mask = orl.nonfinite_pixels(Sb, Rb)
+    clean, dirty = _gpu_lcs(S, R), _gpu_lcs(Sb, Rb)
+    for k, v in zip(orl.MAPS, (1.0, 0.0, 0.0)):
+        assert np.array_equal(dirty[k][mask], np.full(mask.sum(), v, np.float32)), (k, dirty[k][mask])
+        assert np.array_equal(dirty[k][~mask].view(np.uint32), clean[k][~mask].view(np.uint32)), k
+    c = _gpu_lcs(Sb, Rb, max_shift=0.2)
+    for k in ('dx', 'dy'):
+        assert np.all(c[k][mask] == 0.0) and np.all(np.abs(c[k]) <= np.float32(0.2))
+
+
+@pytest.mark.parametrize("k,i,j", [(0, 4, 30), (4, 0, 0), (2, 8, 64), (3, 3, 65)])
+def test_lcs_one_pixel_reaches_its_neighbours_only(k, i, j):
+    S, R = orl.case_inputs(orl.exact_model, 9, 66, 5, 2)
+    orl.check_isolation(_gpu_lcs, S, R, k, i, j)
+
+
+def _gpu_integrate(plan, gx, gy, scale=1.0):
+    return _np(plan.integrate(_cuda(gx), _cuda(gy), scale=scale))
+
+
+@pytest.mark.parametrize("n,m", orl.INTEGRATE_SHAPES)
+def test_integrate_matches_restatement_yardstick(n, m):
+    """psx_integrate_f32 on white-noise gradients (independent gx and gy: not integrable) and on single-pixel impulses of gx
+    and of gy at a corner and inside, and with scale = -2.5 and 1e-3 on the noise:
+        max|gpu - contract| <= 8 * max|integrate_f32 - contract|,
+    the contract in float64 on the pack's own float32 input, integrate_f32 the kernels restated in their number formats
+    on the CPU (not zero, below 2e-6 of the peak).  |mean(phi)| over the n x m result stays within the same bound."""
+    from paresis_amd import ops
+    plan = ops.IntegratePlan(n, m)
+    worst = 0.0
+    for name, gx, gy in orl.integrate_inputs(n, m):
+        for scale in (1.0,) if name != "noise" else (1.0, -2.5, 1e-3):
+            ref, y, peak = orl.integrate_yardstick(gx, gy, scale)
+            got = _gpu_integrate(plan, gx, gy, scale).astype(np.float64)
+            err, mean = np.abs(got - ref).max(), abs(got.mean())
+            print("integrate %dx%d %s scale %g: yardstick %.2e (%.2e of the peak), error / bound %.3f, |mean| / bound %.3f"
+                  % (n, m, name, scale, y, y / peak, err / (8 * y), mean / (8 * y)))
+            assert 0.0 < y < 2e-6 * peak
+            worst = max(worst, err / (8 * y), mean / (8 * y))
+    assert worst <= 1.0, worst
+
+
+@pytest.mark.parametrize("n,m", [(33, 47), (32, 48)])
+def test_one_plan_serves_integrate_and_paganin_in_turn(n, m):
+    """integrate, paganin, integrate, a pair of Paganin images on ONE plan, as retrieval._plan hands it out: every result has
+    the bits of the same call on a fresh plan (the calls share the plan's buffer and transforms, and leave nothing in them)."""
+    from paresis_amd import ops
+    rng = np.random.default_rng(n * m)
+    g = [_cuda(rng.standard_normal((n, m))) for _ in range(4)]
+    I = [_cuda(1.0 + 0.1 * rng.standard_normal((n, m))) for _ in range(3)]
+    calls = [lambda p: [p.integrate(g[0], g[1])],
+             lambda p: list(ops.paganin([I[0]], None, 3.0, 50.0, p)),
+             lambda p: [p.integrate(g[2], g[3], scale=-0.5)],
+             lambda p: list(ops.paganin(I[1:], None, [0.5, 20.0], [40.0, 80.0], p))]
+    shared = ops.IntegratePlan(n, m)
+    for call in calls:
+        a, b = call(shared), call(ops.IntegratePlan(n, m))
+        torch.cuda.synchronize()
+        assert len(a) == len(b)
+        for u, v in zip(a, b):
+            assert torch.isfinite(u).all() and torch.equal(u.view(torch.int32), v.view(torch.int32))
+
+
 def _run(sim, K, tmp_path, **kw):
     from paresis_amd import main
     ed = {"experimentName": "Fil_Nylon_ID17", "filepath": str(tmp_path) + "/" + sim + "/", "overSampling": 2,

@@ -150,6 +150,46 @@ def test_lcs_unchanged_by_lcs_df():
     assert np.abs(_np(after[1]) - o['dx']).max() <= 1e-5 * np.abs(o['dx']).max()
 
 
+# ------------------------------------------------------------------- against the exact and the restated references
+@pytest.mark.parametrize("n,m,K,seed,max_shift", odf.LCS_DF_CASES)
+def test_lcs_df_matches_exact_reference(n, m, K, seed, max_shift):
+    """k_lcs_df against the contract solved in exact rational arithmetic, as tests/test_gpu_retrieval.py
+    test_lcs_matches_exact_reference: every pixel within 2^-24 |x*| + 8 Y scale, the four corners (structural fallbacks)
+    exactly (1, 0, 0, 0) and the only fallbacks.  tests/test_retrieval_df_host.py holds 8 Y <= 2^-24 and shows that the wrong
+    kernels, a zero-padded Laplacian among them, exceed the bound 10 times and more."""
+    S, R, ref, f64, Y = odf.lcs_df_parity(n, m, K, seed)
+    got = _gpu_lcs_df(S, R, max_shift=max_shift)
+    assert np.array_equal(ref['fallback'], odf.corners(n, m))
+    orl.check_parity("lcs_df %dx%d K=%d max_shift %s" % (n, m, K, max_shift), got, ref, Y, odf.MAPS, max_shift)
+    if max_shift is not None:
+        assert np.array_equal(got['df'], _gpu_lcs_df(S, R)['df'])                      # df is not clamped
+
+
+def test_lcs_df_matches_exact_reference_on_steep_images():
+    """tests/test_gpu_retrieval.py test_lcs_matches_exact_reference_on_steep_images for k_lcs_df."""
+    n, m, K, seed = orl.LCS_STEEP_CASE
+    S, R, ref, f64, Y = odf.lcs_df_parity(n, m, K, seed, steep=True)
+    orl.check_parity("lcs_df %dx%d K=%d steep" % (n, m, K), _gpu_lcs_df(S, R), ref, Y, odf.MAPS)
+
+
+def test_lcs_df_nonfinite_pixels_fall_back():
+    """tests/test_gpu_retrieval.py test_lcs_nonfinite_pixels_fall_back for k_lcs_df: (1, 0, 0, 0) where a NaN or an infinity
+    is read (and at the corners), the clean run's bits everywhere else."""
+    S, R = orl.case_inputs(odf.exact_model, 9, 66, 5, 2)
+    Sb, Rb = orl.nonfinite_inputs(S, R)
+    mask = orl.nonfinite_pixels(Sb, Rb) | odf.corners(9, 66)
+    clean, dirty = _gpu_lcs_df(S, R), _gpu_lcs_df(Sb, Rb)
+    for k, v in zip(odf.MAPS, (1.0, 0.0, 0.0, 0.0)):
+        assert np.array_equal(dirty[k][mask], np.full(mask.sum(), v, np.float32)), (k, dirty[k][mask])
+        assert np.array_equal(dirty[k][~mask].view(np.uint32), clean[k][~mask].view(np.uint32)), k
+
+
+@pytest.mark.parametrize("k,i,j", [(0, 4, 30), (4, 0, 1), (2, 8, 64), (3, 3, 65)])
+def test_lcs_df_one_pixel_reaches_its_neighbours_only(k, i, j):
+    S, R = orl.case_inputs(odf.exact_model, 9, 66, 5, 2)
+    orl.check_isolation(_gpu_lcs_df, S, R, k, i, j)
+
+
 # --------------------------------------------------------------------------------------------------------- end to end
 def _run(name, K, root, xml_dir, **kw):
     from paresis_amd import main

@@ -87,6 +87,92 @@ def test_oracle_clamp_leaves_df():
     assert np.array_equal(c['df'], a['df']) and np.array_equal(c['transmission'], a['transmission'])
 
 
+# ----------------------------------------------------------------------- the references the GPU parity tests are held to
+def test_exact_reference_agrees_with_the_float64_oracles():
+    S, R = orl.case_inputs(odf.exact_model, 6, 7, 6, 9)
+    ref, o, f = odf.lcs_df_exact(S, R), odf.lcs_df(S, R, dtype=np.float64, return_mask=True), odf.lcs_df_f64(S, R)
+    c = odf.corners(6, 7)
+    assert np.array_equal(ref['fallback'], c) and np.array_equal(o['fallback'], c) and np.array_equal(f['fallback'], c)
+    for k in odf.MAPS:
+        assert np.abs(o[k] - ref[k]).max() < 1e-9 and np.abs(f[k] - ref[k]).max() < 1e-9, k
+    # the exact Laplacian is the float64 one (exact for float32 data), and the exact pivots are ldl_pivots' up to rounding
+    a, _ = orl.kernel_columns(S[0], R[0])
+    assert np.array_equal(a[3], odf.laplacian(R[0]))
+    M, _ = odf.normal_equations(S, R)
+    d = odf.ldl_pivots(M)
+    ratio = (d / np.stack([M[..., i, i] for i in range(4)], -1)).min(-1)
+    assert np.allclose(ref['pivot_ratio'][~c], ratio[~c], rtol=1e-6)
+    # the corners: L = g0 + g1 up to the float32 rounding of the two differences, so the last pivot is 0 or next to it
+    assert np.all(ref['pivot_ratio'][c] < 1e-9) and np.all(ref['det_ratio'][c] < 1.0)
+
+
+@pytest.mark.parametrize("n,m,K,seed,max_shift", odf.LCS_DF_CASES)
+def test_lcs_df_parity_case_conditions(n, m, K, seed, max_shift):
+    """tests/test_retrieval_host.test_lcs_parity_case_conditions for LCS-DF: 8 Y <= 2^-24; the four corners are structural
+    fallbacks in the exact reference and in the restatement, and the only ones; no other pixel is within a relative 1e-6 of a
+    fallback rule (a pivot against its diagonal entry, det against its threshold, x0 against the largest)."""
+    S, R, ref, f64, Y = odf.lcs_df_parity(n, m, K, seed)
+    c = odf.corners(n, m)
+    print("lcs_df %dx%d K=%d seed %d: Y = %.2e, min det/threshold %.2e, min pivot/diagonal %.2e" %
+          (n, m, K, seed, Y, ref['det_ratio'][~c].min(), ref['pivot_ratio'][~c].min()))
+    assert 0.0 < 8.0 * Y <= orl.EPS32
+    assert np.array_equal(ref['fallback'], c) and np.array_equal(f64['fallback'], c)
+    assert ref['det_ratio'][~c].min() > 1.0 + 1e-6 and ref['pivot_ratio'][~c].min() > 1e-6
+    assert ref['x0'].min() > 1e-6 * ref['x0'].max()
+    if max_shift is not None:
+        ms = float(np.float32(max_shift))
+        over = (np.abs(ref['dx']) > ms) | (np.abs(ref['dy']) > ms)
+        assert 0.1 * n * m < over.sum() < 0.9 * n * m
+
+
+@pytest.mark.parametrize("n,m,K,seed", [c[:4] for c in odf.LCS_DF_CASES if c[4] is None])
+def test_lcs_df_parity_bound_rejects_wrong_kernels(n, m, K, seed):
+    """float32 accumulation, a border spacing of 0.5, a wrapped border neighbour, (odd K) a dropped last position and a
+    zero-padded Laplacian each exceed the bound at least 10 times at some pixel; the right restatement stays within it."""
+    S, R, ref, f64, Y = odf.lcs_df_parity(n, m, K, seed)
+    bound = orl.parity_bound(ref, Y, odf.MAPS)
+    f32 = lambda r: {k: r[k].astype(np.float32) for k in odf.MAPS}
+    assert orl.worst_ratio(f32(f64), ref, bound, odf.MAPS) <= 1.0
+    for variant in odf.VARIANTS:
+        if variant == 'droplast' and K % 2 == 0:
+            continue
+        ratio = orl.worst_ratio(f32(odf.lcs_df_f64(S, R, variant)), ref, bound, odf.MAPS)
+        print("lcs_df %dx%d K=%d %s: %.1e bounds" % (n, m, K, variant, ratio))
+        assert ratio >= 10.0, variant
+
+
+def test_lcs_df_steep_case_rejects_float64_differences():
+    """tests/test_retrieval_host.test_lcs_steep_case_rejects_float64_differences for LCS-DF."""
+    n, m, K, seed = orl.LCS_STEEP_CASE
+    S, R, ref, f64, Y = odf.lcs_df_parity(n, m, K, seed, steep=True)
+    c = odf.corners(n, m)
+    assert orl.steep_fraction(R) > 0.1
+    assert 0.0 < 8.0 * Y <= orl.EPS32 and np.array_equal(ref['fallback'], c) and np.array_equal(f64['fallback'], c)
+    assert ref['det_ratio'][~c].min() > 1.0 + 1e-6 and ref['pivot_ratio'][~c].min() > 1e-6
+    assert ref['x0'].min() > 1e-6 * ref['x0'].max()
+    bound = orl.parity_bound(ref, Y, odf.MAPS)
+    f32 = lambda r: {k: r[k].astype(np.float32) for k in odf.MAPS}
+    assert orl.worst_ratio(f32(f64), ref, bound, odf.MAPS) <= 1.0
+    for variant in ('diff64', 'acc32', 'spacing', 'wrap', 'zeropad'):
+        ratio = orl.worst_ratio(f32(odf.lcs_df_f64(S, R, variant)), ref, bound, odf.MAPS)
+        print("lcs_df steep %s: %.1e bounds" % (variant, ratio))
+        assert ratio >= 10.0, variant
+
+
+def test_lcs_df_nonfinite_rule_on_the_host():
+    """The non-finite rule of include/paresis_hip.h in the three CPU references of LCS-DF (lcs_df_f64 follows the kernel's
+    own tests: a pivot turns NaN, and `d > 0` refuses it)."""
+    S, R = orl.case_inputs(odf.exact_model, 9, 66, 5, 2)
+    Sb, Rb = orl.nonfinite_inputs(S, R)
+    mask = orl.nonfinite_pixels(Sb, Rb) | odf.corners(9, 66)
+    for fn in (odf.lcs_df_exact, lambda s, r: odf.lcs_df(s, r, dtype=np.float64, return_mask=True), odf.lcs_df_f64):
+        clean, dirty = fn(S, R), fn(Sb, Rb)
+        assert np.array_equal(clean['fallback'], odf.corners(9, 66)) and np.array_equal(dirty['fallback'], mask)
+        for k, v in zip(odf.MAPS, (1.0, 0.0, 0.0, 0.0)):
+            assert np.all(dirty[k][mask] == v), k
+            assert np.array_equal(dirty[k][~mask], clean[k][~mask]), k
+
+
 def _blur_periodic(x, patch):
     s = patch.shape[0] // 2
     out = np.zeros_like(x)

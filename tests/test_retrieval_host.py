@@ -70,6 +70,128 @@ def test_oracle_integration_known_answer():
     assert np.abs(out - (phi - phi.mean())).max() < 1e-10
 
 
+# ----------------------------------------------------------------------- the references the GPU parity tests are held to
+def test_exact_reference_agrees_with_the_float64_oracles():
+    """lcs_exact against np.linalg.solve and against the kernel's restatement on a small case, and the restatement's
+    gradients against np.gradient bit for bit."""
+    S, R = orl.case_inputs(orl.exact_model, 6, 7, 5, 9)
+    ref, o, f = orl.lcs_exact(S, R), orl.lcs(S, R, dtype=np.float64, return_mask=True), orl.lcs_f64(S, R)
+    assert not ref['fallback'].any() and not o['fallback'].any() and not f['fallback'].any()
+    for k in orl.MAPS:
+        assert np.abs(o[k] - ref[k]).max() < 1e-10 and np.abs(f[k] - ref[k]).max() < 1e-10, k
+    g0, g1 = orl.gradients(R[0])
+    a, _ = orl.kernel_columns(S[0], R[0])
+    assert g0.dtype == np.float32 and np.array_equal(a[1], g0) and np.array_equal(a[2], g1)
+    # a 2 x 2 system by hand: det_exact and Cramer's numerators
+    F = orl.Fraction
+    M, minors, num = orl.solve_exact([orl.exact(np.array([[[1.0]], [[2.0]]])), orl.exact(np.array([[[3.0]], [[0.5]]]))],
+                                     orl.exact(np.array([[[1.0]], [[1.0]]])))
+    assert (M[0][0][0, 0], M[0][1][0, 0], M[1][1][0, 0]) == (F(5), F(4), F(37, 4))
+    assert minors[1][0, 0] == F(5) * F(37, 4) - 16 and num[0][0, 0] == 3 * F(37, 4) - 4 * F(7, 2)
+
+
+def test_lcs_cases_cover_the_kernel_paths():
+    from paresis_amd._lib import PSX_MAX_LCS
+    from tests._retrieval_df_oracle import LCS_DF_CASES
+    for cases, kmin in ((orl.LCS_CASES, 3), (LCS_DF_CASES, 4)):
+        shapes = [(n, m, K) for n, m, K, _, ms in cases if ms is None]
+        assert (3, 3) in [(n, m) for n, m, _ in shapes]                            # every pixel a border pixel
+        assert {64, 65, 66} <= {m for _, m, _ in shapes} and {3, 4, 5, 9} <= {n for n, _, _ in shapes}
+        assert {K % 2 for _, _, K in shapes} == {0, 1}
+        assert min(K for _, _, K in shapes) == kmin and max(K for _, _, K in shapes) == PSX_MAX_LCS
+        assert sum(ms is not None for *_, ms in cases) == 1
+
+
+@pytest.mark.parametrize("n,m,K,seed,max_shift", orl.LCS_CASES)
+def test_lcs_parity_case_conditions(n, m, K, seed, max_shift):
+    """What makes the GPU test's bound 2^-24 |x*| + 8 Y scale meaningful on this case: float64 costs at most 2^-27 of the
+    scale (8 Y <= 2^-24, so the bound is essentially the float32 output's rounding), and no pixel is a fallback or within
+    a relative 1e-6 of a fallback rule in the exact reference, so no pixel needs to be left out."""
+    S, R, ref, f64, Y = orl.lcs_parity(n, m, K, seed)
+    print("lcs %dx%d K=%d seed %d: Y = %.2e, min det/threshold %.2e, min x0 %.3f" % (n, m, K, seed, Y, ref['det_ratio'].min(),
+                                                                                    ref['x0'].min()))
+    assert 0.0 < 8.0 * Y <= orl.EPS32
+    assert not ref['fallback'].any() and not f64['fallback'].any()
+    assert ref['det_ratio'].min() > 1.0 + 1e-6 and ref['x0'].min() > 1e-6 * ref['x0'].max()
+    if max_shift is not None:
+        ms = float(np.float32(max_shift))
+        over = (np.abs(ref['dx']) > ms) | (np.abs(ref['dy']) > ms)
+        assert 0.1 * n * m < over.sum() < 0.9 * n * m
+
+
+@pytest.mark.parametrize("n,m,K,seed", [c[:4] for c in orl.LCS_CASES if c[4] is None])
+def test_lcs_parity_bound_rejects_wrong_kernels(n, m, K, seed):
+    """The bound tells a wrong kernel from a right one: float32 accumulation, a border spacing of 0.5, a wrapped border
+    neighbour and (odd K) a dropped last position each exceed it at least 10 times at some pixel; the right restatement,
+    rounded to float32 as the kernel's output is, stays within it."""
+    S, R, ref, f64, Y = orl.lcs_parity(n, m, K, seed)
+    bound = orl.parity_bound(ref, Y, orl.MAPS)
+    f32 = lambda r: {k: r[k].astype(np.float32) for k in orl.MAPS}
+    assert orl.worst_ratio(f32(f64), ref, bound, orl.MAPS) <= 1.0
+    for variant in orl.VARIANTS:
+        if variant == 'droplast' and K % 2 == 0:
+            continue
+        ratio = orl.worst_ratio(f32(orl.lcs_f64(S, R, variant)), ref, bound, orl.MAPS)
+        print("lcs %dx%d K=%d %s: %.1e bounds" % (n, m, K, variant, ratio))
+        assert ratio >= 10.0, variant
+
+
+def test_lcs_steep_case_rejects_float64_differences():
+    """On the speckle cases the float32 difference ru - rd is almost always exact, so a kernel that forms it in float64
+    hides within a few bounds.  On steep_model's images (neighbours more than a factor of two apart at over 10 % of the
+    pixels) it does not: the conditions of the parity cases hold, and float64 differences exceed the bound 10 times, as
+    the other wrong kernels do."""
+    n, m, K, seed = orl.LCS_STEEP_CASE
+    S, R, ref, f64, Y = orl.lcs_parity(n, m, K, seed, steep=True)
+    assert orl.steep_fraction(R) > 0.1
+    assert 0.0 < 8.0 * Y <= orl.EPS32 and not ref['fallback'].any() and not f64['fallback'].any()
+    assert ref['det_ratio'].min() > 1.0 + 1e-6 and ref['x0'].min() > 1e-6 * ref['x0'].max()
+    bound = orl.parity_bound(ref, Y, orl.MAPS)
+    f32 = lambda r: {k: r[k].astype(np.float32) for k in orl.MAPS}
+    assert orl.worst_ratio(f32(f64), ref, bound, orl.MAPS) <= 1.0
+    for variant in ('diff64',) + orl.VARIANTS[:3]:
+        ratio = orl.worst_ratio(f32(orl.lcs_f64(S, R, variant)), ref, bound, orl.MAPS)
+        print("lcs steep %s: %.1e bounds" % (variant, ratio))
+        assert ratio >= 10.0, variant
+
+
+def test_lcs_nonfinite_rule_on_the_host():
+    """The non-finite rule of include/paresis_hip.h in the three CPU references: a pixel that reads a NaN or an infinity
+    returns the fallback, every other pixel keeps its value.  lcs_f64 follows the kernel's own tests, so this is the
+    kernel's arithmetic too -- an interior pixel whose own R_k is +inf has a finite M and x0 = +inf, which `x0 > 0` alone
+    lets through (seed 2 meets that at two pixels)."""
+    S, R = orl.case_inputs(orl.exact_model, 9, 66, 5, 2)
+    Sb, Rb = orl.nonfinite_inputs(S, R)
+    mask = orl.nonfinite_pixels(Sb, Rb)
+    assert mask.sum() == 30 and not mask[0, 0] and mask[8, 65] and mask[4, 20] and not mask[4, 21] and mask[4, 40]
+    with np.errstate(all="ignore"):
+        M, v = orl.kernel_sums(Sb, Rb, 3)
+        c00 = M[1, 1] * M[2, 2] - M[1, 2] * M[1, 2]
+        x0 = (c00 * v[0] + (M[0, 2] * M[1, 2] - M[0, 1] * M[2, 2]) * v[1] + (M[0, 1] * M[1, 2] - M[0, 2] * M[1, 1]) * v[2])
+    assert (np.isposinf(x0) & mask).sum() >= 1                                   # the case `x0 > 0` alone lets through
+    for fn in (orl.lcs_exact, lambda s, r: orl.lcs(s, r, dtype=np.float64, return_mask=True), orl.lcs_f64):
+        clean, dirty = fn(S, R), fn(Sb, Rb)
+        assert not clean['fallback'].any() and np.array_equal(dirty['fallback'], mask)
+        for k, v in zip(orl.MAPS, (1.0, 0.0, 0.0)):
+            assert np.all(dirty[k][mask] == v), k
+            assert np.array_equal(dirty[k][~mask], clean[k][~mask]), k
+
+
+def test_integrate_f32_restatement_yardstick():
+    """integrate_f32 on every input of the GPU test: its distance from the float64 contract is the yardstick of the GPU's
+    bound.  It is not zero and stays below 2e-6 of the peak, so a broken restatement cannot widen the bound."""
+    worst = 0.0
+    for n, m in orl.INTEGRATE_SHAPES:
+        for name, gx, gy in orl.integrate_inputs(n, m):
+            for scale in (1.0,) if name != "noise" else (1.0, -2.5, 1e-3):
+                ref, y, peak = orl.integrate_yardstick(gx, gy, scale)
+                worst = max(worst, y / peak)
+                assert 0.0 < y < 2e-6 * peak, (n, m, name, scale, y, peak)
+                assert abs(ref.mean()) <= y
+    print("integrate_f32: worst yardstick %.2e of the peak" % worst)
+    assert orl.integrate_f32(np.zeros((4, 5), np.float32), np.zeros((4, 5), np.float32)).dtype == np.float32
+
+
 def test_phase_gradient_inverts_the_chain_displacement():
     """A linear phase ramp on the study grid (ov = 2) -> the chain's displacement (RF2:54-56) -> the detector's 2x2 binning ->
     phase_gradient returns the binned ramp's slope per detector pixel."""

@@ -1887,8 +1887,10 @@ int lds_engine_propagate(psx_fresnel_plan *p, const PropArgs &a) {
 
     // ---- pass 1: lines along axis 0 of the image = rows of the transposed source (contiguous reads); line y writes row
     // y of the blocked intermediate of each distance.  ONE launch covers all distances (work item = (distance, line
-    // group)): one prologue and one tail instead of n_dist.  The in-place middle stage consumes the forward spectrum, so the
-    // forward stages are repeated per distance (keeping it in registers needs 64 VGPRs the engine waves do not have).
+    // group)): one prologue and one tail instead of n_dist.  The middle stage consumes the forward spectrum, so forward stages B
+    // and C are repeated per pair of distances; forward stage A is not, on the power-of-two kernels: their loader waves keep the
+    // line behind it in registers (64 VGPRs the engine waves do not have) and hand it back for each later pair (fresnel_p2.hip,
+    // DUAL).  k_fresnel_lines repeats all three.
     const bool stamp_pass1 = debug_switch(DBG_STAMP_PASS1) != 0;   // diagnostics only (psx_debug_switch)
     const int stamp_round = debug_switch(DBG_STAMP_ROUND);
     {

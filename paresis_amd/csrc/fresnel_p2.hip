@@ -58,7 +58,7 @@ struct G2 {
     static constexpr int TPL = TLD / LINES, NCH = TPL >= 2 * LXM ? TPL / LXM : 1, CL = LXM / NCH;
     // LDS map, in float2 elements
     static constexpr int O_TP = LINES * MP, O_TB = O_TP + 256 * LDP, O_SA = O_TB + 16 * LDB, O_C = O_SA + LH * LXM,
-                         O_UQ = O_C + NCH * LINES * LXM, O_HT = O_UQ + 2;
+                         O_UQ = O_C + NCH * LINES * LXM, O_HT = O_UQ + 3;      // unit ring (4 ints) + the snapshot flag
     static constexpr size_t lds_bytes(int ntap) { return sizeof(float2) * (size_t)(O_HT + ntap * LXM); }
     static constexpr int max_taps = (160 * 1024 / (int)sizeof(float2) - O_HT) / LXM < MAX_LINE ? (160 * 1024 / (int)sizeof(float2) - O_HT) / LXM : MAX_LINE;
     static_assert(LINES >= 2 && NBA >= 1 && max_taps >= 16, "LDS budget");
@@ -68,9 +68,14 @@ struct G2 {
 
 // CONTIG: the samples of a line are adjacent in memory (pass 1 reads rows of the transposed source); otherwise the lanes of a
 // loader wave walk across the lines of the group (pass 2 reads columns of the blocked intermediate).
-// DUAL (pass 1 of a call with several distances): a round is HALF the LDS lines' worth of image lines and TWO distances -- the
-// lines are transformed forward once, the middle stage writes the product with the first distance's spectrum in place and the
-// product with the second one's into the same slab of the other half of the LDS lines, the inverse stages run at full width.
+// DUAL (pass 1 of a call with several distances): a round is HALF the LDS lines' worth of image lines and TWO distances.  Forward
+// stage A runs in the first half of the LDS lines, forward stage B reads it there and writes the SECOND half; the middle stage
+// writes the product with the pair's first distance in place there and the product with the second one's into the same slab of
+// the first half; the inverse stages run at full width.  So the first half holds the line after forward stage A, untouched, until
+// the middle stage: in the first round of a line group with further pairs the four loader waves copy it into registers (M * LH =
+// 8192 points, 32 per thread: 64 VGPRs of an allocation they use a quarter of) and write it back at the end of every round but
+// the group's last, and the later pairs skip forward stage A and its barrier.  round_plan() (fresnel_p2_dev.hpp) states which
+// phases and barriers a round has, for the engine and the loaders alike.
 // QUEUE: work units from per-workgroup queues with stealing inside the XCD (fresnel_lds.hip, k_fresnel_lines).
 template <int R1, bool CONTIG, bool DUAL, bool QUEUE>
 __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
@@ -87,6 +92,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
     v2f *const CF = Lb + GE::O_C;          // [NCH][LINES][LXM]: fix-up of the wrapped outputs of every LDS line, one partial sum per tap chunk
     v2f *const HT = Lb + GE::O_HT;         // [distances][LXM]: the first taps of every distance of the launch
     int *const uq = reinterpret_cast<int *>(Lb + GE::O_UQ);
+    int *const snap_flag = uq + 4;         // DUAL: loader waves that have a snapshot in registers, counted over the launch
     const int tid = threadIdx.x;
     const int N = a.N, mg = a.margin;
     const int Lx = a.L - M;                // outputs whose window wraps (<= 0: none)
@@ -318,7 +324,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             asm volatile("" : "+v"(lo));                            // opaque copy: what follows is re-derived every round, not kept across the loop
             const int lb = lo / TPL, r = lo % TPL;
             const int lbi = DUAL ? lb % LH : lb;                     // LDS line that holds the image line's samples
-            const int dd = DUAL ? 2 * d + lb / LH : d;
+            const int dd = DUAL ? 2 * d + 1 - lb / LH : d;          // DUAL: the second half of the LDS lines carries the pair's first distance
             const v2f *ht = HT + dd * LXM;
             const v2f *sa = SA + lbi * LXM;
             const v2f *sb = Lb + lbi * MP + M + M / 32;              // phys(M + j) = M + M/32 + j for j < 32
@@ -337,6 +343,25 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             }
         };
 
+        // DUAL: the snapshot of a line group after forward stage A -- the M * LH points of the first half of the LDS lines, 32 per
+        // thread, the lanes on consecutive points of the padded layout (point 256 k + lt of the half: its line and the pad term
+        // of its 256-point chunk are compile-time, so every access is the thread's one base + a constant).  LDS -> registers ->
+        // LDS: the pad slots and the tails behind the M points are neither read nor written.
+        constexpr int NSNAP = DUAL ? M * LH / TLD : 1;
+        static_assert(!DUAL || (M % TLD == 0 && NSNAP * TLD == M * LH && TLD % 32 == 0), "snapshot ownership covers the first half");
+        v2f snap[NSNAP];
+        v2f *const snap_base = Lb + phys(lt);
+        auto snap_off = [](int k) __attribute__((always_inline)) { return ((k * TLD) / M) * MP + phys((k * TLD) % M); };
+        auto snapshot = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < NSNAP; ++k) snap[k] = lds_read(snap_base + snap_off(k));
+        };
+        auto restore = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < NSNAP; ++k) snap_base[snap_off(k)] = snap[k];
+        };
+
+        if (lt == 0) uq[4] = 0;
         if (valid(0)) {
             fetch(0);
             spread(0);
@@ -347,8 +372,21 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
         for (int j = 0; DYN ? ring_ok(ucur) : j < nj; ++j) {
             const bool last_sub = usub + 1 == nsubr;
             const bool more = DYN ? ring_ok(last_sub ? ucur + 1 : ucur) : j + 1 < nj;
-            lds_barrier();                               // (1) engine: forward stage A done
+            const RoundPlan rp = round_plan(DUAL, usub, nsubr);
+            round_barrier(rp, RB_FWD_A);                 // (1) engine: forward stage A done
             if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 16] = wall_clock64();
+            if constexpr (DUAL) {
+                if (rp.snapshot) {
+                    __builtin_amdgcn_s_setprio(3);
+                    snapshot();
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the values are in registers
+                    __builtin_amdgcn_s_setprio(0);
+                    // published: the engine's middle stage may write into the first half.  Nothing lies between barrier (1) and
+                    // this line that waits for another wave, so the engine's wait for it ends
+                    if ((lt & 63) == 0) __hip_atomic_fetch_add(snap_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 24] = wall_clock64();
+            }
             const bool qround = DYN && lt < 64 && usub == 0;
             const bool claiming = qround && ring_ok(ucur + 1);
             unsigned mine = 0xffffffffu;
@@ -356,11 +394,20 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             if (more) fetch(j + 1);
             if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 17] = wall_clock64();
             fixup(j);
-            lds_barrier();                               // (2) engine: wave-private stages done
-            lds_barrier();                               // (3) engine: inverse stage A holds all of LDS in registers
+            round_barrier(rp, RB_PRIVATE);               // (2) engine: wave-private stages done
+            round_barrier(rp, RB_REGS);                  // (3) engine: inverse stage A holds all of LDS in registers
             if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 18] = wall_clock64();
-            __builtin_amdgcn_s_setprio(3);
-            if (more) spread(j + 1);
+            // (the write-back at the loaders' own priority: its 32 stores per thread in one burst at priority 3 held up the engine's
+            // twiddle reads -- pass 1 0.3037 -> 0.3012 ms without, profiles/history/r08_experiments.md)
+            if (!(DUAL && rp.restore)) __builtin_amdgcn_s_setprio(3);
+            if constexpr (DUAL) {
+                // the line group's next pair of distances starts from the snapshot: samples behind the M points, SA and the
+                // zero fill are as the spread left them
+                if (rp.restore) restore();
+                else if (more) spread(j + 1);
+            } else {
+                if (more) spread(j + 1);
+            }
             __builtin_amdgcn_s_setprio(0);
             if (qround) {
                 int unit = -1;
@@ -379,7 +426,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
                 ++usub;
             }
             if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 19] = wall_clock64();
-            lds_barrier();                               // (4) next group is in LDS
+            round_barrier(rp, RB_NEXT);                  // (4) next group (DUAL: or the snapshot) is in LDS
             if (a.stamps && lt == 0 && j == a.stamp_j) a.stamps[(size_t)blockIdx.x * 32 + 20] = wall_clock64();
         }
         if (DYN && lt < 64) {
@@ -407,8 +454,8 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
     const int slabw = spectrum::slab_of_lane(ln);
     const v2f *rowB = tB + n3 * LDB;
     // What a wave owns between the barriers after forward stage A and before inverse stage A: the same 1024 points (4 blocks of 256
-    // = 64 slabs) of TWO LDS lines -- lines 2p and 2p + 1 of the round (DUAL: an image line's buffer and the buffer of its second
-    // distance, LH lines further) -- so that one slab of the kernel spectrum, fetched once, meets both lines: half the spectrum
+    // = 64 slabs) of TWO LDS lines -- lines 2p and 2p + 1 of the round (DUAL: an image line's buffer and the buffer LH lines
+    // further, which takes forward stage B's output and then the pair's first distance) -- so that one slab of the kernel spectrum, fetched once, meets both lines: half the spectrum
     // loads of a one-line range, and the engine's loads share the CU's memory pipeline with the loaders' fetch.
     constexpr int RPL = R1 / 4;                        // ranges of 1024 points per line
     const int G0 = DUAL ? 4 * w + blk : 2 * (w / RPL) * R1 + 4 * (w % RPL) + blk, G1 = G0 + (DUAL ? 32 : R1);      // this lane's two blocks
@@ -430,19 +477,21 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 32 + 0] = wall_clock64();
     lds_barrier();                                       // (0) first group is in LDS
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 32 + 1] = wall_clock64();
-    int eu = 0, es = 0;
+    int eu = 0, es = 0, snaps_taken = 0;
     for (int j = 0; DYN ? uq[eu & 3] >= 0 : j < nj; ++j) {
         int d, g;
         item(j, d, g);
         const int l0 = g * LPG;
+        const RoundPlan rp = round_plan(DUAL, es, nsubr);
         if (++es == nsubr) {
             es = 0;
             ++eu;
         }
         PSX_STAMP(2);
 
-        // ---- forward stage A: radix R1 over stride 256, twiddle w_M^{n q} = w_M^{16 nh q} w_M^{nl q}
-        if (fwdA_on) {
+        // ---- forward stage A: radix R1 over stride 256, twiddle w_M^{n q} = w_M^{16 nh q} w_M^{nl q}  (DUAL: the first round of a
+        // line group only; the later ones find the line as this stage left it, written back by the loaders)
+        if (fwdA_on && rp.forward_a) {
             v2f v[NBAF][R1], pw[5];
 #pragma unroll
             for (int i = 0; i < NBAF; ++i) {
@@ -473,10 +522,11 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             for (int q = 0; q < 8; ++q) hh[q] = h4[64 * q];
         }
         PSX_STAMP(3);
-        lds_barrier();                               // (1)
+        round_barrier(rp, RB_FWD_A);                 // (1)
         PSX_STAMP(4);
 
-        // ---- forward stage B: radix 16 inside each block of 256, stride 16 (DUAL: the first distance's buffer only)
+        // ---- forward stage B: radix 16 inside each block of 256, stride 16 (DUAL: out of place, from the wave's blocks of the first
+        // half of the LDS lines into the same blocks of the second half -- the first half keeps the line as forward stage A left it)
         {
             v2f wt[16];
 #pragma unroll
@@ -498,7 +548,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             }
             fwdB_regs(v0, wt);
 #pragma unroll
-            for (int q = 0; q < 16; ++q) p0[offB(q)] = v0[q];
+            for (int q = 0; q < 16; ++q) (DUAL ? p1 : p0)[offB(q)] = v0[q];
             if constexpr (!DUAL) {
                 fwdB_regs(v1, wt);
 #pragma unroll
@@ -510,8 +560,10 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
         PSX_STAMP(6);
 
         // ---- middle stage, slab by slab: forward radix 16 on contiguous points, x FFT_M(h_d), inverse radix 16, back to LDS
+        // (DUAL: from the slab of the second half, where forward stage B left it; the first distance's product in place there,
+        // the second one's into the same slab of the first half)
         {
-            v2f *b0 = slab_ptr(S0), *b1 = slab_ptr(S1);
+            v2f *b0 = slab_ptr(DUAL ? S1 : S0), *b1 = slab_ptr(DUAL ? S0 : S1);
             v2f x[16], y[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) x[q] = lds_read(b0 + q);
@@ -530,6 +582,17 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
                 DftPk<16, true>::run(y);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) b0[q] = y[q];
+                if (rp.snapshot) {
+                    // the first write into the first half of the LDS lines: not before the four loader waves have published this
+                    // round's snapshot.  They do about 0.2 us after barrier (1), this point is reached 2 us after it, and they wait
+                    // for nothing before they publish (their next barrier is (2), which this wave has not reached): the wait is
+                    // bounded.  (A workgroup barrier here instead cost the round 0.3 us: r8s3.)
+                    snaps_taken += TLD / 64;
+                    PSX_STAMP(25);
+                    while (*(const volatile __attribute__((address_space(3))) int *)snap_flag - snaps_taken < 0) __builtin_amdgcn_s_sleep(1);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+                    PSX_STAMP(26);
+                }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     x[2 * q] = pk_cmul(x[2 * q], (v2f){hh1[q].x, hh1[q].y});
@@ -583,7 +646,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             for (int q = 0; q < 16; ++q) p1[offB(q)] = v1[q];
         }
         PSX_STAMP(9);
-        lds_barrier();                               // (2)
+        round_barrier(rp, RB_PRIVATE);               // (2)
         PSX_STAMP(10);
 
         // ---- inverse stage A; the wanted outputs leave for HBM straight from the registers.  Once every engine thread holds its
@@ -600,7 +663,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
 #pragma unroll
                 for (int c = 1; c < NCH; ++c) cf[i] += CF[(c * LINES + (b >> 8)) * LXM + (n & (LXM - 1))];
             }
-            lds_barrier();                           // (3)
+            round_barrier(rp, RB_REGS);              // (3)
             PSX_STAMP(11);
 #pragma unroll
             for (int i = 0; i < NBA; ++i) {
@@ -616,7 +679,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
                 // leg q holds y_c[n + 256 q] = output sample n + 256 q - (P - 1); leg 0 is also the wrapped output n + M - (P - 1)
                 const int ifirst = n - (a.P - 1);
                 const int lbu = __builtin_amdgcn_readfirstlane(lb);          // a wave's 64 butterflies belong to one LDS line
-                const int dd = DUAL ? 2 * d + lbu / LH : d;
+                const int dd = DUAL ? 2 * d + 1 - lbu / LH : d;             // DUAL: the pair's first distance is in the second half
                 const int l = l0 + (DUAL ? lbu % LH : lbu);
                 v2f *wo = reinterpret_cast<v2f *>(a.wave_out[dd]);
                 float *io = a.inten_out[dd];
@@ -634,7 +697,7 @@ __global__ __launch_bounds__(TT) void k_fresnel_p2(LineArgs a) {
             }
         }
         PSX_STAMP(12);
-        lds_barrier();                               // (4)
+        round_barrier(rp, RB_NEXT);                  // (4)
         PSX_STAMP(13);
     }
 }

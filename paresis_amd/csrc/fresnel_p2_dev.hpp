@@ -67,6 +67,47 @@ static_assert(is_bijection(point_index, 256 * 4) && is_bijection(point_index, 25
 static_assert(reader_meets_builder(256 * 4) && reader_meets_builder(256 * 32), "a lane's loads find its own slab");
 }  // namespace spectrum
 
+// ---- One round of k_fresnel_p2 as the engine waves AND the loader waves see it: which of its phases run and which workgroup
+// barriers it executes, by (DUAL, index of the round among the rounds of its line group, their number).  Both branches of the kernel
+// take every barrier through round_barrier() with the plan of round_plan() and nothing else: a barrier one side executes and the
+// other does not is a hang, so there is no second place to state it.
+//   plain rounds and the first round of a DUAL line group: forward stage A, barrier FWD_A behind it.
+//   DUAL, first round of several: the loaders copy the first half of the LDS lines -- the line after forward stage A, which forward
+//     stage B reads and no longer overwrites -- into registers.  No barrier for it: the loaders count themselves in an LDS flag
+//     once their reads have returned and an engine wave tests the flag before its middle stage's first write into that half.
+//   DUAL, every round but the last: behind barrier REGS the loaders write the snapshot back (restore) where they otherwise spread
+//     the next group's samples; the next round then starts at forward stage B: no forward stage A, no barrier FWD_A.
+enum RoundBarrier { RB_FWD_A = 0, RB_PRIVATE, RB_REGS, RB_NEXT, RB_COUNT };
+struct RoundPlan {
+    bool forward_a, snapshot, restore;
+    constexpr bool has(RoundBarrier b) const { return b == RB_FWD_A ? forward_a : true; }
+};
+__host__ __device__ constexpr RoundPlan round_plan(bool dual, int sub, int nsub) {
+    return RoundPlan{!dual || sub == 0, dual && sub == 0 && nsub > 1, dual && sub + 1 < nsub};
+}
+__device__ __forceinline__ void round_barrier(const RoundPlan &rp, RoundBarrier b) {
+    if (rp.has(b)) lds_barrier();
+}
+// a line group's rounds hang together: a round starts from the snapshot exactly when the round before it restored one, a
+// snapshot is taken exactly when one will be restored, and plain rounds are what they were
+constexpr bool rounds_consistent() {
+    for (int nsub = 1; nsub <= 16; ++nsub) {
+        bool held = false;
+        for (int s = 0; s < nsub; ++s) {
+            const RoundPlan rp = round_plan(true, s, nsub), pl = round_plan(false, s, nsub);
+            if (!pl.forward_a || pl.snapshot || pl.restore) return false;
+            if (rp.forward_a != (s == 0) || (s > 0 && !held)) return false;
+            if (rp.snapshot) held = true;
+            if (rp.snapshot && !rp.forward_a) return false;
+            if (rp.restore && !held) return false;
+            if (s > 0 && !round_plan(true, s - 1, nsub).restore) return false;
+        }
+        if (round_plan(true, nsub - 1, nsub).restore || held != (nsub > 1)) return false;
+    }
+    return true;
+}
+static_assert(rounds_consistent(), "the rounds of a DUAL line group");
+
 // Stage A's twiddles w_M^{n q}, q < R, from the LB = log2(R) powers w^(n 2^b) of the thread's row: w^(n q) is the product of the
 // powers of q's set bits, at most four multiplications deep -- 26 products for R = 32 where two factor tables cost 31 and 62 LDS
 // reads (fresnel_lds.hip, twiddle_A); 5 reads here.  The lower half is applied as it is built, the upper half takes w^(16 n) first.

@@ -58,6 +58,13 @@ base = s[:, 4:5]      # engine passed barrier 1
 print("loader wave 12 (relative to the engine leaving barrier 1):")
 for n, c in zip(["fetch start", "fetch issued", "spread start (barrier 3 passed)", "spread done", "barrier 4 passed"], range(5)):
     print("  %-34s %7.2f us" % (n, ((ld[:, c:c+1] - base) * 10.0).mean() / 1e3))
+if np.any(s[:, 24] > 0):       # DUAL rounds of k_fresnel_p2 (stamp_pass1=1; stamp_round picks the round: even = a line's first pair at 4 distances)
+    snap = ((s[:, 24] - ld[:, 0]) * 10.0).mean() / 1e3
+    print("  DUAL: snapshot in registers and published %.2f us after the loaders left barrier 1 (a round that takes none: ~0)" % snap)
+    if np.any(s[:, 26] > 0):
+        print("  DUAL: the engine tests the snapshot flag %.2f us after barrier 1 and waits %.2f us for it"
+              % (((s[:, 25:26] - base) * 10.0).mean() / 1e3, ((s[:, 26] - s[:, 25]) * 10.0).mean() / 1e3))
+    print("  DUAL: a round that starts from the snapshot has no forward stage A and no barrier 1 ('fwd A' = the spectrum request only)")
 if np.any(s[:, 21] > 0):       # partitioned / DIF loaders: the window moves in two halves between barriers (3) and (4)
     print("  first half spread %.2f, second half fetched (issued) %.2f us after barrier 3" %
           tuple(((s[:, c:c+1] - ld[:, 2:3]) * 10.0).mean() / 1e3 for c in (21, 22)))

@@ -326,7 +326,12 @@ int psx_repad_f32(const float *src, int margin_src, float *dst, int margin_dst, 
  * getMembraneSegmentedFromFile's sphere splat (Samples/getMembraneFromFile.py:143-159) for ONE layer:
  * out[i][j] (+)= scale * sum over spheres of 2*sqrt(r^2 - dist^2) on the cropped grid, with the reference's window and
  * placement rules.  xf, yf, rad are HOST arrays (pixels of the margin-extended grid: they come from a host-side list);
- * out is a DEVICE image.  Unlike the rest of the ABI this call synchronises the stream once (host staging buffers). */
+ * out is a DEVICE image.  Unlike the rest of the ABI this call synchronises the stream once (host staging buffers).
+ * The rule, as tests/_membrane_oracle.py states it and tests/test_gpu_membrane.py holds all three entry points to, per pixel:
+ * xi = rint(xf) (half to even), radInt = floor(r) + 1; a sphere is drawn iff r > 0, xf, yf, r are finite and
+ * margin2 < xi < dimX + margin + margin2 (the same for yi); it adds 2 sqrt(r^2 - d^2) where d^2 < r^2 on the pixels of
+ * [xi - radInt, xi + radInt) x [yi - radInt, yi + radInt); the map is cropped to [margin, margin + dim).  Chords are summed in
+ * float64 here, so any finite radius is taken. */
 int psx_membrane_f32(const double *xf, const double *yf, const double *rad, int64_t n, int dimX, int dimY, int margin,
                      int margin2, double scale, int accumulate, float *out, void *stream);
 
@@ -334,16 +339,28 @@ int psx_membrane_f32(const double *xf, const double *yf, const double *rad, int6
  * membrane position and layer with a new integer offset (getMembraneFromFile.py:139-142); a plan takes the list once
  * (HOST arrays x, y, r in pixels of the list frame, i.e. par/pixSize before the offset), bins it by 32-pixel cell, and
  * psx_membrane_layer_f32 renders one layer at offset (offx, offy) -- xfloat = x - offx, yfloat = y - offy -- without
- * touching the host: asynchronous on the stream like the rest of the ABI. */
+ * touching the host: asynchronous on the stream like the rest of the ABI.
+ * The plan path sums chords in 2^-36 pixel fixed point, which sets two limits on a radius.  psx_membrane_plan_create fails with
+ * PSX_E_ARG when a kept radius is 2^14 = 16384 pixels or more (a chord must stay below 2^15 pixels; psx_membrane_f32 takes such
+ * a list).  A sphere of radius 2^-38 pixel or less is left out of the plan: each of its chords is at most half an accumulator
+ * unit and rounds to zero, so no sum changes.  Entries with r <= 0 or a non-finite x, y or r are left out as well. */
 typedef struct psx_membrane_plan psx_membrane_plan;
 int psx_membrane_plan_create(const double *x, const double *y, const double *r, int64_t n, psx_membrane_plan **plan);
 int psx_membrane_plan_destroy(psx_membrane_plan *plan);
+/* What a plan holds and how this build stages it, for tests and tools (host only, no GPU call): fills info[0 .. min(cap,
+ * PSX_MEMBRANE_PLAN_INFO)) and returns how many it wrote (0 for a null plan or info, or cap <= 0), in this order:
+ *   0    spheres kept;   1-2  cells of the list frame along axis 0 and 1;   3  floor(largest kept radius) + 1;
+ *   4    cell side, pixels;   5-6  tile rows and columns of the layers kernel;   7  spheres per job and batch;
+ *   8    (layer, cell row) jobs staged per round;   9  layers per launch. */
+#define PSX_MEMBRANE_PLAN_INFO 10
+int psx_membrane_plan_info(const psx_membrane_plan *plan, int *info, int cap);
 int psx_membrane_layer_f32(psx_membrane_plan *plan, int offx, int offy, int dimX, int dimY, int margin, int margin2,
                            double scale, int accumulate, float *out, void *stream);
 /* Every layer of a membrane position in ONE launch (getMembraneFromFile.py:139-159 loops over nbOfLayers offsets and adds
- * into one float64 map): the chords of all nlayers offsets (offx, offy: HOST arrays) are summed in float64 and stored
- * once; nlayers = 0 stores zeros.  support (may be NULL) is the position's second map, the uniform support thickness
- * (getMembraneFromFile.py:163), filled with support_value by the same launch. */
+ * into one float64 map): the chords of all nlayers offsets (offx, offy: HOST arrays) are summed as integers of 2^-36 pixel --
+ * the same bits whatever the order of the list or of the layers -- and stored once, eight layers per launch (a later launch
+ * adds its float32 sum to the map); nlayers = 0 stores zeros.  support (may be NULL) is the position's second map, the uniform
+ * support thickness (getMembraneFromFile.py:163), filled with support_value by the first launch. */
 int psx_membrane_layers_f32(psx_membrane_plan *plan, int nlayers, const int *offx, const int *offy, int dimX, int dimY,
                             int margin, int margin2, double scale, int accumulate, float *out, float *support,
                             float support_value, void *stream);

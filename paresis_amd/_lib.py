@@ -27,11 +27,12 @@ PSX_MAX_DIST = 8
 PSX_MAX_POISSON = 8
 PSX_MAX_DETECT = 4
 PSX_DETECTOR_PLAN_INFO = 12
+PSX_MEMBRANE_PLAN_INFO = 10
 PSX_MAX_SRC = 16
 PSX_SUM_SLOTS, PSX_SUM_STRIDE = 32, 16
 ENGINE_AUTO, ENGINE_ROCFFT, ENGINE_LDS = 0, 1, 2
 STATUS_NONFINITE = 1
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class PsxError(RuntimeError):
@@ -103,6 +104,7 @@ PROTOTYPES = {
     "psx_membrane_f32": (c_int, [_dp, _dp, _dp, c_int64, c_int, c_int, c_int, c_int, c_double, c_int, _vp, _vp]),
     "psx_membrane_plan_create": (c_int, [_dp, _dp, _dp, c_int64, _vpp]),
     "psx_membrane_plan_destroy": (c_int, [_vp]),
+    "psx_membrane_plan_info": (c_int, [_vp, POINTER(c_int), c_int]),
     "psx_membrane_layer_f32": (c_int, [_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, _vp, _vp]),
     "psx_membrane_layers_f32": (c_int, [_vp, c_int, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_double, c_int,
                                         _vp, _vp, c_float, _vp]),

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void psx_clock_probe_kernel(unsigned long long
 
 extern "C" {
 
-int psx_abi_version(void) { return 24; }   // 3: psx_debug_switch(es_active), psx_set_deterministic(1) allocation-free; 4: psx_darkfield_split_f32(num, den); 5: psx_get_deterministic; 6: psx_refract_split_f32, psx_darkfield_blur_prepared_f32(accumulate); 7: psx_set_deterministic_scale; 8: psx_detect_multi_f32; 9: psx_get_deterministic_scale; 10: psx_clock_probe; 11: psx_fold_materials_f32, psx_contrast_phantom_f32, psx_contrast_phantom_slices_u8; 12: psx_lcs_f32, psx_integrate_plan_create/_bytes/_destroy, psx_integrate_f32; 13: psx_lcs_df_f32; 14: psx_umpa_f32; 15: psx_umpa_df_f32; 16: psx_paganin_f32; 17: psx_fbp_plan_create/_bytes/_destroy, psx_fbp_f32; 18: psx_fbp_project_f32, psx_fbp_adjoint_f32; 19: psx_fbp_tv_step_f32; 20: psx_volume_project_u8; 22: psx_decompose_f32; 23: psx_detector_plan_info; 24: psx_volume_project_cone_u8, psx_fdk_plan_create/_destroy/_bytes, psx_fdk_f32
+int psx_abi_version(void) { return 25; }   // 3: psx_debug_switch(es_active), psx_set_deterministic(1) allocation-free; 4: psx_darkfield_split_f32(num, den); 5: psx_get_deterministic; 6: psx_refract_split_f32, psx_darkfield_blur_prepared_f32(accumulate); 7: psx_set_deterministic_scale; 8: psx_detect_multi_f32; 9: psx_get_deterministic_scale; 10: psx_clock_probe; 11: psx_fold_materials_f32, psx_contrast_phantom_f32, psx_contrast_phantom_slices_u8; 12: psx_lcs_f32, psx_integrate_plan_create/_bytes/_destroy, psx_integrate_f32; 13: psx_lcs_df_f32; 14: psx_umpa_f32; 15: psx_umpa_df_f32; 16: psx_paganin_f32; 17: psx_fbp_plan_create/_bytes/_destroy, psx_fbp_f32; 18: psx_fbp_project_f32, psx_fbp_adjoint_f32; 19: psx_fbp_tv_step_f32; 20: psx_volume_project_u8; 22: psx_decompose_f32; 23: psx_detector_plan_info; 24: psx_volume_project_cone_u8, psx_fdk_plan_create/_destroy/_bytes, psx_fdk_f32; 25: psx_membrane_plan_info
 
 const char *psx_last_error(void) { return psx::err_buf(); }
 

@@ -103,6 +103,19 @@ constexpr int MLT = 256;         // threads per workgroup
 constexpr int ML_SEGS = MLT / 32;             // jobs staged per round: one per half-wave
 constexpr int ML_CAP = 32;       // spheres per job and batch
 constexpr int ML_FRAC = 36;      // fractional bits of the accumulators: chords below 2^14 pixels, sums below 2^27
+// The radii the fixed-point path holds.  Above: a chord 2 sqrt(.) * 2^ML_FRAC has to stay below 2^51 for the 2^52 + 2^51 rounding
+// offset of the splat, so a radius is below 2^(50 - ML_FRAC) = 2^14 pixels; psx_membrane_plan_create refuses a larger one
+// (psx_membrane_f32 sums in float64 and takes it).  Below: a sphere whose longest chord 2 r is at most half an accumulator unit
+// adds 0 to every pixel, and below r ~ 1.6e-30 the scaled r^2 - d^2 leaves the float32 range of chord_sqrt's reciprocal square
+// root (NaN bits into the accumulator): the plan leaves such a sphere out of its list, which changes no sum.
+constexpr double ML_RADIUS_END = (double)(1 << (50 - ML_FRAC));
+constexpr double ML_RADIUS_NIL = 0.25 / (double)(1ull << ML_FRAC);
+
+// what a plan keeps of a list: the entries that the splat admits somewhere (getMembraneFromFile.py:152 needs finite numbers and
+// r > 0) and whose chords are not all zero in the accumulator's unit
+bool plan_keeps(double x, double y, double r) {
+    return r > ML_RADIUS_NIL && std::isfinite(x) && std::isfinite(y) && std::isfinite(r);
+}
 
 struct LayerArgs {
     int offx[ML_MAX], offy[ML_MAX];
@@ -255,7 +268,7 @@ int psx_membrane_plan_create(const double *x, const double *y, const double *r, 
     double xmin = 0, xmax = 0, ymin = 0, ymax = 0, rmax = 0;
     bool any = false;
     for (int64_t s = 0; s < n; ++s) {
-        if (!(r[s] > 0.0) || !std::isfinite(x[s]) || !std::isfinite(y[s]) || !std::isfinite(r[s])) continue;
+        if (!plan_keeps(x[s], y[s], r[s])) continue;
         if (!any) { xmin = xmax = x[s]; ymin = ymax = y[s]; any = true; }
         xmin = std::min(xmin, x[s]); xmax = std::max(xmax, x[s]);
         ymin = std::min(ymin, y[s]); ymax = std::max(ymax, y[s]);
@@ -263,15 +276,18 @@ int psx_membrane_plan_create(const double *x, const double *y, const double *r, 
     }
     p->x0 = std::floor(xmin); p->y0 = std::floor(ymin);
     const double ex = xmax - p->x0, ey = ymax - p->y0;
-    if (!(ex / MC < 60000.0 && ey / MC < 60000.0 && (ex / MC + 1) * (ey / MC + 1) < 4.0e8 && rmax < 1.0e6))
-        return fail(PSX_E_ARG, "psx_membrane_plan_create: sphere list spans %.3g x %.3g pixels (radius up to %.3g)", ex, ey, rmax);
+    if (!(ex / MC < 60000.0 && ey / MC < 60000.0 && (ex / MC + 1) * (ey / MC + 1) < 4.0e8))
+        return fail(PSX_E_ARG, "psx_membrane_plan_create: sphere list spans %.3g x %.3g pixels", ex, ey);
+    if (!(rmax < ML_RADIUS_END))
+        return fail(PSX_E_ARG, "psx_membrane_plan_create: radius %.17g pixels; the fixed-point accumulator holds radii below %g "
+                               "(psx_membrane_f32 takes larger ones)", rmax, ML_RADIUS_END);
     p->ncx = (int)(ex / MC) + 1; p->ncy = (int)(ey / MC) + 1;
     p->rmax_int = (int)std::floor(rmax) + 1;
     const size_t nc = (size_t)p->ncx * p->ncy;
     std::vector<int> off(nc + 1, 0);
     std::vector<int> cell(n > 0 ? n : 1, -1);
     for (int64_t s = 0; s < n; ++s) {
-        if (!(r[s] > 0.0) || !std::isfinite(x[s]) || !std::isfinite(y[s]) || !std::isfinite(r[s])) continue;
+        if (!plan_keeps(x[s], y[s], r[s])) continue;
         const int cx = (int)((x[s] - p->x0) / MC), cy = (int)((y[s] - p->y0) / MC);
         cell[s] = cx * p->ncy + cy;
         off[cell[s] + 1]++;
@@ -291,6 +307,15 @@ int psx_membrane_plan_create(const double *x, const double *y, const double *r, 
 int psx_membrane_plan_destroy(psx_membrane_plan *p) {
     delete p;
     return 0;
+}
+
+int psx_membrane_plan_info(const psx_membrane_plan *p, int *info, int cap) {
+    if (!p || !info || cap <= 0) return 0;
+    const int v[PSX_MEMBRANE_PLAN_INFO] = {(int)p->n, p->ncx, p->ncy, p->rmax_int,   // n: a sum of int counts
+                                           MC, MLX, MLY, ML_CAP, ML_SEGS, ML_MAX};
+    const int n = std::min(cap, (int)PSX_MEMBRANE_PLAN_INFO);
+    std::copy(v, v + n, info);
+    return n;
 }
 
 int psx_membrane_layers_f32(psx_membrane_plan *p, int nlayers, const int *offx, const int *offy, int dimX, int dimY, int margin,
@@ -334,11 +359,14 @@ int psx_membrane_f32(const double *xf, const double *yf, const double *rad, int6
     std::vector<std::pair<int, int>> pairs;   // (tile, sphere)
     for (int64_t s = 0; s < n; ++s) {
         const double r = rad[s];
-        if (!(r > 0.0) || !std::isfinite(xf[s]) || !std::isfinite(yf[s])) continue;
-        const int xi = (int)std::nearbyint(xf[s]), yi = (int)std::nearbyint(yf[s]);      // np.round: half to even
+        if (!(r > 0.0) || !std::isfinite(xf[s]) || !std::isfinite(yf[s]) || !std::isfinite(r)) continue;
+        // np.round: half to even.  A centre beyond 2^30 pixels is on no grid and would not convert to int
+        if (!(std::fabs(xf[s]) < 1073741824.0 && std::fabs(yf[s]) < 1073741824.0)) continue;
+        const int xi = (int)std::nearbyint(xf[s]), yi = (int)std::nearbyint(yf[s]);
         if (!(margin2 < xi && xi < dimX + margin + margin2 && margin2 < yi && yi < dimY + margin + margin2))
             continue;                                                                      // getMembraneFromFile.py:152
-        const int radInt = (int)std::floor(r) + 1;
+        // the window is clipped to the grid below: a reach beyond 2^29 pixels is as good as that (and xi + radInt stays an int)
+        const int radInt = (int)std::min(std::floor(r), 536870912.0) + 1;
         // window on the cropped grid
         const int x0 = std::max(0, xi - radInt - margin), x1 = std::min(dimX - 1, xi + radInt - 1 - margin);
         const int y0 = std::max(0, yi - radInt - margin), y1 = std::min(dimY - 1, yi + radInt - 1 - margin);
